@@ -25,7 +25,11 @@ N > 1: one process per GPU (torchrun), every rank holds a full replica of the gr
 scaling, no data-path collective: requests are independent -- SURVEY.md 8(e)); the timed region is bracketed by barrier +
 synchronize and the MAX over ranks is reported.
 
-Prints ONE JSON line (rank 0).  Extra objects: `roofline` (algorithmic bytes of the WHOLE batch from the oracle's byte model,
+A plain run sets up, warms up, times --steps steps of `value`'s leg and prints its line; `--dump-outputs DIR` also writes the answers
+of the timed path's last step as DIR/<name>.npy (C4 and the other Check workloads: perm.npy, err.npy).  Everything below beside `value`
+-- the other legs, the CPU oracle's baseline and answer check, the roofline and the other configurations -- runs with `--full`.
+
+Prints ONE JSON line (rank 0).  Extra objects (--full): `roofline` (algorithmic bytes of the WHOLE batch from the oracle's byte model,
 multi-threaded, with its per-level split / HIP-event kernel time vs HBM peak; `traffic` = HBM bytes per launch MEASURED IN THE RUN at N=1 --
 the device leg of this very command re-run under two rocprofv3 --pmc passes, ~5 s -- or, for the other configurations and N > 1, the
 figure of profiles/traffic.json from an earlier run's passes, labelled), `cpu_baseline` (the CPU oracle, a restatement of
@@ -183,8 +187,10 @@ def c3_cpu_reverse_walk(w, subjects):
 
 def filter_bench(args, w, eng, steps, warmup):
     """BASELINE config 3: one step = LookupResources(pod, view, user:U) for the 64 power users as ONE batched reverse walk
-    (acl_lookup_resources_batch: bitmaps come back to the host, as the Go side consumes them).  Returns the C3 record."""
+    (acl_lookup_resources_batch: bitmaps come back to the host, as the Go side consumes them).  Returns the C3 record; its "_outputs" are the
+    last timed step's bitmaps and counts.  Without --full only the timed batched walk runs (no roofline, no CPU baseline or parity)."""
     import torch
+    full = getattr(args, "full", True)
     rt, perm_name, st = w.check
     subs = np.asarray(w.lookup_subjects, dtype=np.uint32)
     # result buffers: allocated once with acl_host_alloc (pinned) and reused across steps, as the Go shim does -- the single-launch walk then
@@ -207,7 +213,7 @@ def filter_bench(args, w, eng, steps, warmup):
     eng.set_timing(False)
     stats = eng.stats()
     assert bms is bufs[0]
-    only_batched = args.legs == "device"  # (rocprofv3 runs: every launch of the process is then a 64-lookup launch, so the profiler's average is the roofline's)
+    only_batched = args.legs == "device" or not full  # (rocprofv3 runs: every launch of the process is then a 64-lookup launch, so the profiler's average is the roofline's)
     pg_bufs = None
     pg = []
     for _ in range(0 if only_batched else max(5, warmup)):
@@ -269,12 +275,11 @@ def filter_bench(args, w, eng, steps, warmup):
         kname, kms, launches = "k_rev_local", stats["rev_local_ms"], max(1, stats["rev_local_passes"])
     else:
         kname, kms, launches = "k_rev_expand", stats["expand_ms"], max(1, stats["expand_launches"])
-    lb = c3_lookup_bytes(w, subs)
-    batch_bytes = float(lb.sum())
-    ach = batch_bytes * steps / (kms * 1e-3) / 1e9 if kms > 0 else None
+    batch_bytes = float(c3_lookup_bytes(w, subs).sum()) if full else None
+    ach = batch_bytes * steps / (kms * 1e-3) / 1e9 if full and kms > 0 else None
     traffic = traffic_bounds = None
     tr = os.path.join(ROOT, "profiles", "traffic.json")
-    if os.path.exists(tr):
+    if full and os.path.exists(tr):
         try:
             tj = json.load(open(tr))
             det = tj.get("C3_detail") or {}
@@ -300,11 +305,12 @@ def filter_bench(args, w, eng, steps, warmup):
            "bitmap_bytes_per_lookup": int(bms.shape[1] * 4),
            "roofline": {"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": (ach / HBM_PEAK_GBS) if ach else None, "traffic": traffic,
                         "traffic_detail": traffic_bounds, "kernel": kname, "kernel_avg_us": 1e3 * kms / launches,
-                        "algorithmic_bytes_per_lookup": batch_bytes / subs.size, "algorithmic_bytes_per_launch": batch_bytes * steps / launches,
-                        "model": "SURVEY.md 8(d) LookupResources formula on the generator's arrays: 17 + sum over reverse rows (8 + 4 deg) + N_pod / 8"}}
+                        "algorithmic_bytes_per_lookup": batch_bytes / subs.size if full else None, "algorithmic_bytes_per_launch": batch_bytes * steps / launches if full else None,
+                        "model": "SURVEY.md 8(d) LookupResources formula on the generator's arrays: 17 + sum over reverse rows (8 + 4 deg) + N_pod / 8"} if full else None,
+           "_outputs": {"bitmaps": bms, "counts": counts}}
     if not pageable_equal or (conc and not conc["equal_to_sequential_run"]):
         out.setdefault("parity", {})["pageable_vs_pinned_mismatch" if not pageable_equal else "concurrent_vs_sequential_mismatch"] = True
-    if not args.no_cpu:
+    if full and not args.no_cpu:
         from oracle import orc
         o = orc.Oracle(w.schema)
         w.load(o)
@@ -396,6 +402,11 @@ def c5_bench(args, w, world, rank, local_rank, t_gen):
         barrier()
         el = time.perf_counter() - t0
         st_ = e.stats()
+        last_bm = bm[0].cpu().numpy()
+        rec = {"elapsed": el, "check_s": tc, "filter_s": tf, "perm": p.cpu().numpy(), "err": er.cpu().numpy(), "last_filter": last_bm,
+               "local_relationships": int(st_["snapshot_edges_local"]), "recv": se.exchanged_entries, "levels": se.levels_last}
+        if not args.full:
+            return rec
         # cross-path property at full size: the last Filter bitmap must agree with sharded Checks of the same subject
         last_f = [o for o in ops if o != "C"][-1][1]
         rng = np.random.default_rng(7)
@@ -404,17 +415,16 @@ def c5_bench(args, w, world, rank, local_rank, t_gen):
         bits = np.unpackbits(bm[0].cpu().numpy().view(np.uint8), bitorder="little")
         cp, _ = se.check_bulk_ids(e.make_items(rt, perm_name, pods, st, "", np.full(pods.size, last_f, dtype=np.uint32)))
         cross = int(((cp.cpu().numpy() == 2) != (bits[pods] == 1)).sum())
-        return {"elapsed": el, "check_s": tc, "filter_s": tf, "perm": p.cpu().numpy(), "err": er.cpu().numpy(), "cross_mismatch": cross,
-                "allowed_last_filter": int(bits.sum()), "local_relationships": int(st_["snapshot_edges_local"]), "recv": se.exchanged_entries,
-                "levels": se.levels_last}
+        rec.update(cross_mismatch=cross, allowed_last_filter=int(bits.sum()))
+        return rec
 
     t0 = time.time()
     if world > 1:
         se = sharded.ShardedEngine(make(rank, world), sharded.TorchComm(device=f"cuda:{local_rank}"), exchange=c5_exchange)
         o = run(se, dist.barrier)
         outs = [None] * world
-        dist.all_gather_object(outs, {k: v for k, v in o.items() if k not in ("perm", "err")})
-        outs[rank].update(perm=o["perm"], err=o["err"])
+        dist.all_gather_object(outs, {k: v for k, v in o.items() if k not in ("perm", "err", "last_filter")})
+        outs[rank].update(perm=o["perm"], err=o["err"], last_filter=o["last_filter"])
     else:
         def fn(se):
             return run(se, se.comm.barrier)
@@ -433,10 +443,13 @@ def c5_bench(args, w, world, rank, local_rank, t_gen):
                "check_batches": nC, "filter_requests": len(ops) - nC,
                "ms_per_check_batch": 1e3 * outs[0]["check_s"] / max(1, nC), "ms_per_filter_request": 1e3 * outs[0]["filter_s"] / max(1, len(ops) - nC),
                "levels": outs[0]["levels"], "shard_relationships": [o["local_relationships"] for o in outs],
-               "recv_entries_by_shard": [o["recv"] for o in outs], "allowed_ids_last_filter": outs[0]["allowed_last_filter"],
+               "recv_entries_by_shard": [o["recv"] for o in outs], "allowed_ids_last_filter": outs[0].get("allowed_last_filter"),
                "setup_s": {"generate": round(t_gen, 1), "load+run": round(t_all, 1)}}
-        parity = {"filter_vs_check_cross_mismatches": int(sum(o["cross_mismatch"] for o in outs)), "cross_checked_pods": 20000}
-        if not args.no_cpu:
+        if args.dump_outputs:  # the last Check batch's answers and the last Filter's bitmap (words), as the stream's caller gets them
+            dump_outputs(args.dump_outputs, {"perm": outs[0]["perm"], "err": outs[0]["err"],
+                                             "last_filter_bitmap": np.frombuffer(np.ascontiguousarray(outs[0]["last_filter"]).tobytes(), dtype=np.uint32)})
+        parity = {"filter_vs_check_cross_mismatches": int(sum(o["cross_mismatch"] for o in outs)), "cross_checked_pods": 20000} if args.full else {}
+        if args.full and not args.no_cpu:
             from oracle import orc
             o = orc.Oracle(w.schema)
             w.load(o)
@@ -445,14 +458,15 @@ def c5_bench(args, w, world, rank, local_rank, t_gen):
             op_, oe_ = o.check_bulk_ids_mt(usable_cores() if usable_cores() <= 16 else 16, rt, perm_name, w.res[:m], st, "", w.subj[:m])
             parity["checked_against_oracle"] = m
             parity["mismatches"] = int((op_ != outs[0]["perm"][:m]).sum() + (oe_ != outs[0]["err"][:m]).sum())
-        out["parity"] = parity
+        if parity:
+            out["parity"] = parity
         print(json.dumps(out))
     for e in engines:
         e.close()
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
-    if rank == 0 and (out["parity"].get("mismatches") or out["parity"]["filter_vs_check_cross_mismatches"]):
+    if rank == 0 and (out.get("parity", {}).get("mismatches") or out.get("parity", {}).get("filter_vs_check_cross_mismatches")):
         raise SystemExit("PARITY FAILURE in the sharded mixed stream")
 
 
@@ -702,8 +716,10 @@ def _local_edges(engine):
 
 
 def check_bench(args, w, eng, steps, warmup, world, rank, label, legs, dist=None):
-    """All Check legs of one workload on one engine.  Returns (record, gpu_perm, gpu_err) -- the answers of batch 0."""
+    """All Check legs of one workload on one engine.  Returns (record, gpu_perm, gpu_err) -- the answers of batch 0; record["_outputs"] holds
+    the answers of the timed leg's last step.  Without --full only the timed leg runs (gpu_perm / gpu_err are then None)."""
     import torch
+    full = getattr(args, "full", True)
     rt, perm_name, st = w.check
     n = int(w.res.size)
     nrep = max(1, len(getattr(args, "replica_devices", []) or []))  # in-process replicas (--devices): callers and batches per step scale with them
@@ -711,7 +727,9 @@ def check_bench(args, w, eng, steps, warmup, world, rank, label, legs, dist=None
     items0 = eng.make_items(rt, perm_name, w.res, st, "", w.subj)
     rec = {"workload": WORKLOAD_DESC[label], "batch": n, "relationships": w.ntuples, "objects": int(sum(w.nobjects.values()))}
 
-    # ---------------- (i) device-resident, sequential, HIP events on: the roofline's kernel time
+    # ---------------- (i) device-resident, sequential, HIP events on: the roofline's kernel time (the timed leg itself with --legs device)
+    if legs != "device" and not full:
+        return check_host_ids(args, eng, items0, n, NB, nrep, steps, warmup, rec, dist)
     d_batches = [torch.from_numpy(np.roll(items0, b * 4099).view(np.uint8).copy()).cuda() for b in range(NB)]
     d_perm = torch.zeros(n, dtype=torch.uint8, device="cuda")
     d_err = torch.zeros(n, dtype=torch.int32, device="cuda")
@@ -731,6 +749,12 @@ def check_bench(args, w, eng, steps, warmup, world, rank, label, legs, dist=None
     el_dev = time.perf_counter() - t0
     eng.set_timing(False)
     st_dev = eng.stats()
+    if legs == "device":
+        rec["_outputs"] = {"perm": d_perm.cpu().numpy(), "err": d_err.cpu().numpy()}
+    if legs == "device" and not full:
+        rec["value"] = n * steps / el_dev
+        rec["elapsed"] = el_dev
+        return rec, None, None
     eng.check_bulk_ids_device(d_batches[0].data_ptr(), n, d_perm.data_ptr(), d_err.data_ptr())
     gpu_perm, gpu_err = d_perm.cpu().numpy(), d_err.cpu().numpy()
     # the dominant kernel: the single-launch walk (k_check_local: every level of the batch in ONE launch) unless the batch took the
@@ -781,87 +805,8 @@ def check_bench(args, w, eng, steps, warmup, world, rank, label, legs, dist=None
         return rec, gpu_perm, gpu_err
 
     # ---------------- (ii) host ids, pipelined: THE timed region (`value`)
-    hb = eng.host_alloc(NB * n * 21)
-    h_items = hb[:NB * n * 16].view(aclgpu_item_dtype()).reshape(NB, n)
-    h_perm = hb[NB * n * 16:NB * n * 17].reshape(NB, n)
-    h_err = hb[NB * n * 17:].view(np.int32).reshape(NB, n)
-    for b in range(NB):
-        h_items[b] = np.roll(items0, b * 4099)
-    window = max(1, min(args.window, NB))
-    callers = max(1, args.callers) * nrep
-    steps_all = steps * nrep  # a step = one batch per replica
-
-    def submit_wait(k_steps):  # acl_check_bulk_ids_submit / acl_ticket_wait: `window` batches in flight from ONE host thread
-        q = []
-        for k in range(k_steps):
-            if len(q) == window:
-                eng.wait(q.pop(0))
-            b = k % NB
-            q.append(eng.submit_ids(h_items[b], h_perm[b], h_err[b]))
-        for t in q:
-            eng.wait(t)
-
-    def blocking(k_steps):  # `callers` host threads, each in a blocking acl_check_bulk_ids (what goroutines behind the cgo shim do)
-        """-> fire(): the caller threads exist and are parked before the clock starts (a server's callers are not created per request)"""
-        if callers == 1:
-            def fire1():
-                for k in range(k_steps):
-                    b = k % NB
-                    eng.check_bulk_ids_into(h_items[b], h_perm[b], h_err[b])
-            return fire1
-        nxt = [0]
-        lk = threading.Lock()
-        go = [False]
-
-        def run():
-            # (the callers are on their marks when the clock starts: a yield loop, not an Event -- waking three sleeping Python threads costs
-            #  0.1-0.3 ms, 3-5 % of a 20-step region that is 5 ms long, and is the harness's time, not the engine's)
-            while not go[0]:
-                time.sleep(0)
-            while True:
-                with lk:
-                    k = nxt[0]
-                    nxt[0] += 1
-                if k >= k_steps:
-                    return
-                b = k % NB
-                eng.check_bulk_ids_into(h_items[b], h_perm[b], h_err[b])
-
-        # (two callers never share a batch's output buffers at the same time: steps are handed out in order, NB >= callers)
-        ts = [threading.Thread(target=run) for _ in range(callers)]
-        for t in ts:
-            t.start()
-
-        def fire():
-            go[0] = True
-            for t in ts:
-                t.join()
-        return fire
-
-    pipelined = (lambda k_: (lambda: submit_wait(k_))) if args.pipeline == "submit" else blocking
-    # warm-up long enough to reach the steady state of the mode: the HIP runtime sets up its copy paths lazily -- the first time a 2nd, then a
-    # 3rd host<->device copy is in flight at once, hipMemcpyAsync blocks ~7 ms (profiles/r03_submit_window_trace.txt); a `window`-ticket
-    # warm-up left the second of them for the timed region (the "630 M/s at windows 3-4" of earlier runs was that one stall averaged over 40 steps)
-    pipelined(max(warmup * nrep, 3 * window, 3 * callers, 12))()
-    fire = pipelined(steps_all)
-    # (no cyclic-GC pass of the interpreter inside the K-step region: the harness holds lists of a million name strings, and a full collection
-    #  that walks them is milliseconds of a region that is 4-5 ms long)
-    import gc
-    gc.collect()
-    gc.disable()
-    if dist is not None:
-        dist.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    fire()
-    torch.cuda.synchronize()
-    if dist is not None:
-        dist.barrier()
-    elapsed = time.perf_counter() - t0
-    gc.enable()
+    hb, h_items, h_perm, h_err, window, callers, steps_all, pipelined, elapsed = check_host_ids(args, eng, items0, n, NB, nrep, steps, warmup, rec, dist, keep=True)
     host_ok = bool(np.array_equal(h_perm[0], gpu_perm) and np.array_equal(h_err[0], gpu_err))
-    rec["value"] = n * steps_all / elapsed
-    rec["elapsed"] = elapsed
     # the same leg over >= 200 steps (VERDICT r3 weak #9: the driver's 20-step region is 5.6 ms): reported beside the K-step figure, never as `value`
     long_steps = max(200, steps) * nrep
     fire_long = pipelined(long_steps)
@@ -1032,6 +977,99 @@ def check_bench(args, w, eng, steps, warmup, world, rank, label, legs, dist=None
         rec["string_path"] = {"skipped": "objects of this run have no names (--legs / workload without name_objects)"}
     rec["kernel"] = kern
     return rec, gpu_perm, gpu_err
+
+
+def check_host_ids(args, eng, items0, n, NB, nrep, steps, warmup, rec, dist=None, keep=False):
+    """(ii) host ids, pipelined: THE timed region (`value`).  Fills rec["value"], rec["elapsed"] and rec["_outputs"] (the answers of the last
+    timed step).  keep=False (the plain run): frees the pinned buffers and returns (rec, None, None); keep=True: hands them and the leg's
+    pieces to check_bench's other legs."""
+    import torch
+    hb = eng.host_alloc(NB * n * 21)
+    h_items = hb[:NB * n * 16].view(aclgpu_item_dtype()).reshape(NB, n)
+    h_perm = hb[NB * n * 16:NB * n * 17].reshape(NB, n)
+    h_err = hb[NB * n * 17:].view(np.int32).reshape(NB, n)
+    for b in range(NB):
+        h_items[b] = np.roll(items0, b * 4099)
+    window = max(1, min(args.window, NB))
+    callers = max(1, args.callers) * nrep
+    steps_all = steps * nrep  # a step = one batch per replica
+
+    def submit_wait(k_steps):  # acl_check_bulk_ids_submit / acl_ticket_wait: `window` batches in flight from ONE host thread
+        q = []
+        for k in range(k_steps):
+            if len(q) == window:
+                eng.wait(q.pop(0))
+            b = k % NB
+            q.append(eng.submit_ids(h_items[b], h_perm[b], h_err[b]))
+        for t in q:
+            eng.wait(t)
+
+    def blocking(k_steps):  # `callers` host threads, each in a blocking acl_check_bulk_ids (what goroutines behind the cgo shim do)
+        """-> fire(): the caller threads exist and are parked before the clock starts (a server's callers are not created per request)"""
+        if callers == 1:
+            def fire1():
+                for k in range(k_steps):
+                    b = k % NB
+                    eng.check_bulk_ids_into(h_items[b], h_perm[b], h_err[b])
+            return fire1
+        nxt = [0]
+        lk = threading.Lock()
+        go = [False]
+
+        def run():
+            # (the callers are on their marks when the clock starts: a yield loop, not an Event -- waking three sleeping Python threads costs
+            #  0.1-0.3 ms, 3-5 % of a 20-step region that is 5 ms long, and is the harness's time, not the engine's)
+            while not go[0]:
+                time.sleep(0)
+            while True:
+                with lk:
+                    k = nxt[0]
+                    nxt[0] += 1
+                if k >= k_steps:
+                    return
+                b = k % NB
+                eng.check_bulk_ids_into(h_items[b], h_perm[b], h_err[b])
+
+        # (two callers never share a batch's output buffers at the same time: steps are handed out in order, NB >= callers)
+        ts = [threading.Thread(target=run) for _ in range(callers)]
+        for t in ts:
+            t.start()
+
+        def fire():
+            go[0] = True
+            for t in ts:
+                t.join()
+        return fire
+
+    pipelined = (lambda k_: (lambda: submit_wait(k_))) if args.pipeline == "submit" else blocking
+    # warm-up long enough to reach the steady state of the mode: the HIP runtime sets up its copy paths lazily -- the first time a 2nd, then a
+    # 3rd host<->device copy is in flight at once, hipMemcpyAsync blocks ~7 ms (profiles/r03_submit_window_trace.txt); a `window`-ticket
+    # warm-up left the second of them for the timed region (the "630 M/s at windows 3-4" of earlier runs was that one stall averaged over 40 steps)
+    pipelined(max(warmup * nrep, 3 * window, 3 * callers, 12))()
+    fire = pipelined(steps_all)
+    # (no cyclic-GC pass of the interpreter inside the K-step region: the harness holds lists of a million name strings, and a full collection
+    #  that walks them is milliseconds of a region that is 4-5 ms long)
+    import gc
+    gc.collect()
+    gc.disable()
+    if dist is not None:
+        dist.barrier()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fire()
+    torch.cuda.synchronize()
+    if dist is not None:
+        dist.barrier()
+    elapsed = time.perf_counter() - t0
+    gc.enable()
+    rec["value"] = n * steps_all / elapsed
+    rec["elapsed"] = elapsed
+    b_last = (steps_all - 1) % NB  # (steps are handed out in order and NB >= callers + 2: the last step's buffers are no other step's)
+    rec["_outputs"] = {"perm": h_perm[b_last].copy(), "err": h_err[b_last].copy()}
+    if not keep:
+        eng.host_free(hb)
+        return rec, None, None
+    return hb, h_items, h_perm, h_err, window, callers, steps_all, pipelined, elapsed
 
 
 def postfilter_c3_leg(local_rank):
@@ -1305,7 +1343,7 @@ def measure_traffic(args, label, kernel, n_items=0):
     if not exe:
         return {"error": "rocprofv3 not found"}
     child = [sys.executable, os.path.abspath(__file__), "--workload", args.workload, "--scale", str(args.scale), "--steps", "3", "--warmup", "1", "--no-cpu", "--legs", "device",
-             "--configs", "off", "--strings", "off", "--traffic", "static"]
+             "--configs", "off", "--strings", "off", "--traffic", "static", "--full"]
     if label == "C2":
         child[child.index("--workload") + 1] = "C2"
     if args.batch and label != "C2":
@@ -1540,6 +1578,7 @@ def c5r_leg(args, local_rank, budget_s):
     sub.workload, sub.scale, sub.batch, sub.replica = "C5", 1.0, 0, True
     r5, p5, er5 = check_bench(sub, w5, e5, max(10, min(args.steps, 40)), max(3, args.warmup), 1, 0, "C5R", "device")
     r5.pop("elapsed", None)
+    r5.pop("_outputs", None)
     r5.pop("value", None)
     snap_bytes = int(e5.stats()["snapshot_bytes"])
     mix = None
@@ -1585,6 +1624,30 @@ def c5r_leg(args, local_rank, budget_s):
     return r5
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: `arrays` (what the timed path returned in its last step) as d/<name>.npy -- float32 where it holds every value exactly,
+    float64 otherwise.  Above DUMP_LIMIT_BYTES in all, each array is cut to a fixed, seeded sample of its elements (flattened, in index
+    order), written beside it as d/<name>_index.npy."""
+    os.makedirs(d, exist_ok=True)
+    conv = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        exact32 = a.dtype.kind == "f" and a.dtype.itemsize <= 4 or a.dtype.kind in "biu" and (a.size == 0 or int(np.abs(a.astype(np.int64)).max()) < (1 << 24))
+        conv[name] = a.astype(np.float32 if exact32 else np.float64)
+    total = sum(a.nbytes for a in conv.values())
+    cost = sum(a.size * (a.itemsize + 8) for a in conv.values())  # (a sampled element: its value and its float64 index)
+    for name, a in conv.items():
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, int(a.size * (DUMP_LIMIT_BYTES - 4096) / cost))
+            idx = np.sort(np.random.default_rng(0x5ACE).choice(a.size, size=min(keep, a.size), replace=False))
+            np.save(os.path.join(d, f"{name}_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(d, f"{name}.npy"), a)
+
+
 def launch_ranks(n, dry):
     """`python bench.py --gpus N` outside a launcher: start the N ranks here (python -m torch.distributed.run, one process per GPU,
     rendezvous on 127.0.0.1 -- the container's hostname may not resolve) and hand their exit code back.  Rank 0 prints the line."""
@@ -1607,7 +1670,7 @@ def launch_ranks(n, dry):
         raise SystemExit(rc)
 
 
-def dry_spawn(world, rank, local_rank):
+def dry_spawn(world, rank, local_rank, full=False):
     """--dry-spawn: the launch path without a GPU (tests/test_bench_spawn.py).  The ranks meet over gloo, agree on who is there, rank 0
     prints ONE line."""
     import torch
@@ -1645,7 +1708,7 @@ def dry_spawn(world, rank, local_rank):
     if rank == 0:
         print(json.dumps({"dry_spawn": True, "n_gpus": world, "local_ranks_seen": seen, "metric": "check_decisions_per_sec", "value": None, "scaling": "weak",
                           "max_elapsed_s": elapsed, "per_rank": per_rank, "shard_of_type": owners,
-                          "sharded_leg": "on" if world == 8 else "off (auto: the type-hash sharded leg runs at 8 ranks; replicas are `value` at every N)",
+                          "sharded_leg": "on" if world == 8 and full else "off (auto: the type-hash sharded leg runs at 8 ranks with --full; replicas are `value` at every N)",
                           "distinct_request_streams": len({r_["first_resource"] for r_ in per_rank})}), flush=True)
 
 
@@ -1667,7 +1730,7 @@ def main():
                     help="roofline.traffic: measure = two rocprofv3 --pmc passes of this command's device leg, now (about 25 s); static = profiles/traffic.json "
                          "(an earlier run's passes, labelled); auto = measure for the headline workload at N=1 with the CPU legs on")
     ap.add_argument("--replica", action="store_true", help="with --workload C5: the 100 M-relationship graph as one unsharded replica (the beyond-L3 data point)")
-    ap.add_argument("--stream", action="store_true", help="with --workload C5 --replica: also run the 90 / 10 Check + Filter stream (what the default run's C5R leg does)")
+    ap.add_argument("--stream", action="store_true", help="with --workload C5 --replica: also run the 90 / 10 Check + Filter stream (what the --full run's C5R leg does; implies --full)")
     ap.add_argument("--legs", default="all", choices=["all", "device"], help="device: only the device-resident leg (for rocprofv3 runs: every k_expand "
                     "launch of the process is then a sequential one, so the profiler's average equals the roofline's)")
     ap.add_argument("--native-loop", default="on", choices=["on", "off"], help="sharded leg: also time the level loop inside libaclgpu.so (acl_shard_check_bulk)")
@@ -1687,7 +1750,13 @@ def main():
     ap.add_argument("--logical-shards", type=int, default=0, help="with 1 GPU: run the sharded leg as G logical shards on this device (emulated)")
     ap.add_argument("--exchange", default="both", choices=["allgather", "alltoall", "both"],
                     help="sharded leg: how Check frontiers cross shards (allgather = the north star's form; alltoall moves G x fewer bytes)")
+    ap.add_argument("--full", action="store_true", help="everything beside the timed leg: the other legs (device-resident, >= 200-step run, latency, string path), "
+                    "the CPU oracle's baseline and parity check, the roofline and its traffic passes, C2 / C3 / C5R, single_checks and the sharded leg at 8 ranks.  "
+                    "Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy "
+                    "(float32, or float64 where float32 is not exact; at most 64 MB in all: a fixed, seeded sample of a larger array)")
     args = ap.parse_args()
+    args.full = args.full or args.stream  # (the stream is checked against the device leg's answers)
 
     under_launcher = "WORLD_SIZE" in os.environ and "RANK" in os.environ
     args.replica_devices = [int(x) for x in args.devices.split(",") if x.strip() != ""]
@@ -1712,7 +1781,7 @@ def main():
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     if args.dry_spawn:
-        return dry_spawn(world, rank, local_rank)
+        return dry_spawn(world, rank, local_rank, args.full)
     if args.traffic == "auto":  # (every rank of an N > 1 run would need a profiler pass of its own; the other configurations keep the committed figures)
         args.traffic = "measure" if (world == 1 and not args.no_cpu and args.legs == "all" and not args.sharded_child) else "static"
     if not torch.cuda.is_available():
@@ -1787,6 +1856,9 @@ def main():
     t_load = time.time() - t0
     if args.workload == "C3":
         out = filter_bench(args, w, eng, args.steps, args.warmup)
+        outputs = out.pop("_outputs")
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, outputs)
         out.update({"n_gpus": world, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32", "data": "synthetic",
                     "config": {"workload": out.pop("workload"), "lookups_per_step": out.pop("lookups_per_step"), "relationships": out.pop("relationships"),
                                "objects": out.pop("objects"), "scale": args.scale}})
@@ -1799,6 +1871,9 @@ def main():
 
     rec, gpu_perm, gpu_err = check_bench(args, w, eng, args.steps, args.warmup, world, rank, label, args.legs, dist if world > 1 else None)
     elapsed = rec.pop("elapsed")
+    outputs = rec.pop("_outputs")
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, outputs)
     if label == "C5R" and args.stream and rank == 0:
         mm = c5r_mixed_stream(args, w, eng, gpu_perm, gpu_err, max(40, args.steps))
         mm.pop("_fsub", None)
@@ -1812,12 +1887,12 @@ def main():
         k_ = rec.get("kernel") or {}
         dist.all_gather_object(per_rank, {"rank": rank, "elapsed_s": elapsed, "decisions_per_s": n * args.steps / elapsed,
                                           "kernel": k_.get("name"), "kernel_avg_us": 1e3 * k_["ms"] / k_["launches"] if k_.get("launches") else None,
-                                          "device_resident_decisions_per_s": rec["device_resident"]["decisions_per_s"]})
+                                          "device_resident_decisions_per_s": rec.get("device_resident", {}).get("decisions_per_s")})
         elapsed = float(tt.item())
     stats = eng.stats()
 
     # ---- extra leg (outside the timed region above): the sharded graph
-    want_sharded = (args.sharded == "on" or (args.sharded == "auto" and world == 8)) and (world > 1 or args.logical_shards > 1)
+    want_sharded = (args.sharded == "on" or (args.sharded == "auto" and world == 8 and args.full)) and (world > 1 or args.logical_shards > 1)
 
     out = None
     if rank == 0:
@@ -1833,13 +1908,13 @@ def main():
                                                                       if args.replica_devices else f"replicas x{world} (request-level data parallel)"), "numa_node_of_rank0": numa_node,
                        "timed": "host-id ABI calls (host buffers in, host buffers out: PCIe both ways inside the call) over 8 distinct pinned batches, " + (f"submit/wait window {args.window}" if args.pipeline == "submit" else f"{args.callers * nrep} blocking caller thread(s)") if args.legs == "all"
                                 else "device-resident calls only (--legs device)"},
-            "p50_batch_ms": rec.get("latency", {}).get("p50_batch_ms", rec["device_resident"]["p50_batch_ms"]),
+            "p50_batch_ms": rec.get("latency", {}).get("p50_batch_ms", rec.get("device_resident", {}).get("p50_batch_ms")),
             "setup_s": {"generate": round(t_gen, 2), "name_objects": round(t_names, 2), "load+snapshot": round(t_load, 2)},
             "snapshot_bytes": int(stats["snapshot_bytes"]),
         }
         kernel = rec.get("kernel")
         out.update(rec)
-        if not args.no_cpu:
+        if args.full and not args.no_cpu:
             # at EVERY N: rank 0 times the CPU oracle on its own batch and prices the roofline from the oracle's byte model (the other ranks
             # wait at the barrier below -- outside every timed region)
             out["_steps"] = args.steps
@@ -1866,7 +1941,7 @@ def main():
                 rf["frac_min_over_gpus"] = min(ok_) / HBM_PEAK_GBS if ok_ else None
                 rf["aggregate_achieved"] = float(np.sum(ok_)) if ok_ else None
                 rf["note"] = "achieved / frac are PER GPU (mean over the ranks' own HIP-event kernel times); every rank runs the same request multiset"
-        else:
+        elif args.full:
             out.pop("kernel", None)
             rot = out.pop("rotations", None)
             if rot:
@@ -1878,7 +1953,7 @@ def main():
     eng.close()
 
     # ---- the other single-GPU BASELINE configurations, same run (never part of `value`)
-    if rank == 0 and world == 1 and args.legs == "all" and (args.configs == "on" or (args.configs == "auto" and args.workload == "C4" and args.scale == 1.0 and not args.batch)):
+    if args.full and rank == 0 and world == 1 and args.legs == "all" and (args.configs == "on" or (args.configs == "auto" and args.workload == "C4" and args.scale == 1.0 and not args.batch)):
         cfgs = {}
         try:
             w2 = workloads.c2()
@@ -1889,6 +1964,7 @@ def main():
             e2.snapshot()
             r2, p2, er2 = check_bench(args, w2, e2, max(args.steps, 50), args.warmup, 1, 0, "C2", "all")
             r2.pop("elapsed")
+            r2.pop("_outputs")
             r2["metric"], r2["unit"] = "check_decisions_per_sec", "decisions/s"
             if not args.no_cpu:
                 r2["_steps"] = max(args.steps, 50)
@@ -1905,6 +1981,7 @@ def main():
             w3.load(e3)
             e3.snapshot()
             cfgs["C3"] = filter_bench(args, w3, e3, max(args.steps, 20), args.warmup)
+            cfgs["C3"].pop("_outputs")
             e3.close()
             if args.strings != "off":
                 cfgs["C3"]["postfilter_one_user"] = postfilter_c3_leg(local_rank)

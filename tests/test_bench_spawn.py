@@ -68,8 +68,9 @@ def test_gpus_flag_must_match_world_size():
 def test_eight_ranks_from_a_cold_start():
     """`bench.py --gpus 8` -- what the driver runs on an 8-GPU node -- starts its eight ranks without manual steps: every rank opens an engine
     (store-only here: no GPU), loads the graph through the ABI, takes ITS rotation of the request stream, configures the 8-way type-hash sharding of the extra
-    leg, and the ranks agree on the max-over-ranks clock and gather their records over gloo; rank 0 prints ONE line with n_gpus == 8."""
-    pr = subprocess.run([sys.executable, BENCH, "--gpus", "8", "--dry-spawn"], capture_output=True, text=True, timeout=600, env=_env(OMP_NUM_THREADS="1"))
+    leg, and the ranks agree on the max-over-ranks clock and gather their records over gloo; rank 0 prints ONE line with n_gpus == 8.  (The sharded
+    leg is one of the --full legs.)"""
+    pr = subprocess.run([sys.executable, BENCH, "--gpus", "8", "--dry-spawn", "--full"], capture_output=True, text=True, timeout=600, env=_env(OMP_NUM_THREADS="1"))
     assert pr.returncode == 0, pr.stderr[-3000:]
     lines = _json_lines(pr.stdout)
     assert len(lines) == 1, pr.stdout

@@ -6,6 +6,7 @@ import os
 import re
 import shutil
 import subprocess
+import tempfile
 
 import pytest
 
@@ -15,7 +16,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_host_side_is_race_free_under_tsan(aclgpu_lib):
     if not (os.path.exists("/opt/rocm/bin/hipcc") and os.path.exists("/opt/rocm/lib/llvm/bin/clang++") and shutil.which("make")):
         pytest.skip("no ROCm clang here")
-    pr = subprocess.run(["bash", os.path.join(ROOT, "tools", "tsan.sh"), "20"], capture_output=True, text=True, timeout=600)
+    with tempfile.TemporaryDirectory(prefix="aclgpu_tsan_") as t:  # (a directory of this run's own: tools/tsan.sh's default one may belong to another user)
+        pr = subprocess.run(["bash", os.path.join(ROOT, "tools", "tsan.sh"), "20"], capture_output=True, text=True, timeout=600, env=dict(os.environ, T=t))
     if pr.returncode:
         pytest.skip("the instrumented build did not link here: " + pr.stderr.strip()[-300:])
     out = pr.stdout

@@ -11,10 +11,10 @@ for SAN in thread address,undefined; do
   T=/tmp/aclgpu_san_$(echo $SAN | tr , _)
   mkdir -p $T
   for f in schema store plan plan_reverse engine engine_shard engine_shard_native engine_callers engine_async engine_list bootstrap_yaml; do
-    /opt/rocm/bin/hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -fPIC -fsanitize=$SAN -fno-sanitize=vptr -Wno-option-ignored -x hip -c $P/csrc/$f.cpp -o $T/$f.o 2> /dev/null &
+    /opt/rocm/bin/hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -fPIC -fsanitize=$SAN -fno-gpu-sanitize -fno-sanitize=vptr -Wno-option-ignored -x hip -c $P/csrc/$f.cpp -o $T/$f.o 2> /dev/null &
   done
   wait
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -fsanitize=$SAN -Wno-option-ignored -shared -o $T/libaclgpu.so $T/*.o $P/build/kernels.hip.o -ldl 2> /dev/null
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -fsanitize=$SAN -fno-gpu-sanitize -Wno-option-ignored -shared -o $T/libaclgpu.so $T/*.o $P/build/kernels.hip.o -ldl 2> /dev/null
   $CXX -O1 -g -std=c++17 -fsanitize=$SAN $R/tools/list_stress.cpp -I$R/include -L$T -laclgpu -lpthread -Wl,-rpath,$T -o $T/list_stress
   set +e
   TSAN_OPTIONS="halt_on_error=0" ASAN_OPTIONS="detect_leaks=0" UBSAN_OPTIONS="print_stacktrace=1" timeout 900 $T/list_stress ${1:-4000} ${2:-3} ${3:-4} > $T/out.txt 2> $T/err.txt; rc=$?

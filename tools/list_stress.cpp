@@ -2,8 +2,8 @@
 // A PodList and a Table of a few MB with strings full of quotes, backslash runs, brackets and commas; acl_selfcheck_json_array over them with chunks from 64 bytes
 // up (every answer must be the same spans), acl_prefilter_response (lists and tables) and acl_bitmap_test_names from several threads at once, each output compared
 // with the first one's.  tools/tsan.sh-style builds:
-//   hipcc ... -fsanitize=thread            (races between the pool's workers: items, spans, keep bytes, the spliced output)
-//   hipcc ... -fsanitize=address,undefined (the 16- / 64-byte loads at chunk ends and body ends, the tail buffer, span arithmetic)
+//   hipcc ... -fsanitize=thread -fno-gpu-sanitize            (races between the pool's workers: items, spans, keep bytes, the spliced output)
+//   hipcc ... -fsanitize=address,undefined -fno-gpu-sanitize (the 16- / 64-byte loads at chunk ends and body ends, the tail buffer, span arithmetic)
 // usage: list_stress [items = 4000] [threads = 3] [rounds = 6]
 #include <atomic>
 #include <cstdio>

@@ -2,7 +2,7 @@
 // Writers (WriteRelationships with TOUCH / DELETE / CREATE + preconditions, activity.go:47-149), readers (ReadRelationships, name lookups,
 // the Watch feed), the snapshot self-checks (in-place patch, background compaction) and single checks through the micro-batcher (refused:
 // no GPU) all at once.  Exit code 0 = every call returned what it must; run under TSan for the races:
-//   hipcc/clang++ -fsanitize=thread over csrc/*.cpp and this file (tools/tsan.sh)
+//   hipcc/clang++ -fsanitize=thread (hipcc: -fno-gpu-sanitize, host code only) over csrc/*.cpp and this file (tools/tsan.sh)
 #include <atomic>
 #include <chrono>
 #include <cstdio>

@@ -15,10 +15,10 @@ mkdir -p $T
 T=$(cd $T && pwd)
 make -C $P -j8 lib/libaclgpu.so > /dev/null
 for f in schema store plan plan_reverse engine engine_shard engine_shard_native engine_callers engine_async engine_list bootstrap_yaml; do
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -fPIC -fsanitize=thread -Wno-option-ignored -x hip -c $P/csrc/$f.cpp -o $T/$f.o 2> /dev/null &
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -fPIC -fsanitize=thread -fno-gpu-sanitize -Wno-option-ignored -x hip -c $P/csrc/$f.cpp -o $T/$f.o 2> /dev/null &
 done
 wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -fsanitize=thread -Wno-option-ignored -shared -o $T/libaclgpu.so $T/*.o $P/build/kernels.hip.o -ldl 2> /dev/null
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -fsanitize=thread -fno-gpu-sanitize -Wno-option-ignored -shared -o $T/libaclgpu.so $T/*.o $P/build/kernels.hip.o -ldl 2> /dev/null
 CXX=/opt/rocm/lib/llvm/bin/clang++
 $CXX -O1 -g -std=c++17 -fsanitize=thread $R/tools/store_stress.cpp -I$R/include -L$T -laclgpu -lpthread -Wl,-rpath,$T -o $T/store_stress
 $CXX -O1 -g -std=c++17 -fsanitize=thread $R/tools/batcher_bench.cpp -I$R/include -L$T -laclgpu -lpthread -Wl,-rpath,$T -o $T/batcher_bench

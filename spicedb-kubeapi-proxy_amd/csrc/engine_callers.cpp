@@ -635,6 +635,7 @@ int acl_selfcheck_snapshot(acl_engine_t *h, int *patched_out) {
         if (p.off + p.n > sz) return fail(ACL_ERR_INTERNAL, "patch region outside its array");
     }
     if (patched_out) *patched_out = patched ? 1 : current ? 2 : 0;  // 1: patched in place, 0: rebuilt, 2: was current already
+    if (patched || current) debug_rows_report(h->store, h->snap);  // (a rebuild reported itself in build_forward)
     std::string why;
     if (!verify_snapshot(h->store, now, h->snap, h->shard, &why)) return fail(ACL_ERR_INTERNAL, "snapshot does not match the store: " + why);
     return ACL_OK;

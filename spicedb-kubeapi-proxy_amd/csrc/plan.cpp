@@ -325,6 +325,49 @@ void collect(const Node &n, Node::Kind kind, std::vector<const Node *> *out) {
 // 10 M graph finishes (9 synchronous rebuilds in 37 k kube writes, profiles/r03_dual_write_before.json).  8 B per spare id and class.
 uint32_t with_headroom(uint32_t n) { return n + n / 4 + 16384; }
 
+void debug_rows_report(const Store &store, const Snapshot &s) {
+    const char *env = getenv("ACL_DEBUG_ROWS");
+    if (!env) return;
+    const int level = atoi(env);
+    const Schema &sc = store.schema();
+    uint64_t rows = 0, two = 0, ids = 0, nbs = 0, nb_two = 0, slow = 0;
+    uint32_t nb_max = 0, nb_max_fast = 0;
+    for (int slot = 0; slot < sc.nslots && (size_t)slot < s.lay.size(); slot++) {
+        const auto [t, m] = sc.slot_owner[slot];
+        const Member &mem = sc.defs[t].members[m];
+        for (size_t k = 0; k < s.lay[slot].cls.size(); k++) {
+            const ClassLayout &c = s.lay[slot].cls[k];
+            if (!c.live || !c.hashed) continue;
+            for (uint32_t sid = 0; sid < c.nsubjects; sid++) {
+                const uint32_t *md = s.meta.data() + 2 * ((size_t)c.smeta_base + sid);
+                if (!md[1]) continue;
+                const uint32_t nb = hrow_nb(md[1]);
+                uint64_t n = 0;
+                for (size_t i = 4 * (size_t)md[0]; i < 4 * ((size_t)md[0] + nb); i++) n += s.buckets[i] != kEmpty;
+                rows++;
+                ids += n;
+                nbs += nb;
+                nb_max = std::max(nb_max, nb);
+                if (md[1] & kRowTwoBit) two++, nb_two += nb;
+                if (!hrow_is_slow(md[1])) {
+                    nb_max_fast = std::max(nb_max_fast, nb);
+                    continue;
+                }
+                slow++;
+                if (level >= 2)
+                    fprintf(stderr, "[aclgpu] slow row: %s#%s@%s%s sid=%u nb=%u two=%d seed=%u ids=%llu\n", sc.defs[t].name.c_str(), mem.name.c_str(),
+                            sc.defs[mem.classes[k].stype].name.c_str(), mem.classes[k].wildcard ? ":*" : "", sid, nb, (md[1] & kRowTwoBit) ? 1 : 0,
+                            md[1] >> 24, (unsigned long long)n);
+            }
+        }
+    }
+    fprintf(stderr, "[aclgpu] hashed rows: %llu (%llu two-choice holding %llu buckets), %llu ids in %llu buckets (load %.3f), %.1f MB; "
+                    "slow %llu, largest %u buckets, largest fast %u buckets\n",
+            (unsigned long long)rows, (unsigned long long)two, (unsigned long long)nb_two, (unsigned long long)ids, (unsigned long long)nbs,
+            nbs ? ids / (4.0 * nbs) : 0.0, nbs * 16 / 1e6, (unsigned long long)slow, nb_max, nb_max_fast);
+    fflush(stderr);
+}
+
 uint32_t shard_of_type(const std::string &type_name, uint32_t world) {
     uint32_t h = 2166136261u;  // FNV-1a ...
     for (unsigned char c : type_name) h = (h ^ c) * 16777619u;
@@ -604,25 +647,9 @@ void build_forward(Store &store, int64_t now, Snapshot *snap, ShardSpec shard) {
             }
         }
     }
-    if (getenv("ACL_DEBUG_ROWS")) {  // how the hashed rows were placed (tools/row_stats.py)
-        uint64_t rows = 0, two = 0, ids = 0, nbs = 0, nb_two = 0;
-        for (int slot = 0; slot < sc.nslots; slot++)
-            for (const ClassLayout &c : lay[slot].cls) {
-                if (!c.live || !c.hashed) continue;
-                for (uint32_t sid = 0; sid < c.nsubjects; sid++) {
-                    const uint32_t *md = s.meta.data() + 2 * ((size_t)c.smeta_base + sid);
-                    if (!md[1]) continue;
-                    rows++;
-                    nbs += hrow_nb(md[1]);
-                    if (md[1] & kRowTwoBit) two++, nb_two += hrow_nb(md[1]);
-                    for (size_t i = 4 * (size_t)md[0]; i < 4 * ((size_t)md[0] + hrow_nb(md[1])); i++) ids += s.buckets[i] != kEmpty;
-                }
-            }
-        fprintf(stderr, "[aclgpu] hashed rows: %llu (%llu two-choice holding %llu buckets), %llu ids in %llu buckets (load %.3f), %.1f MB\n", (unsigned long long)rows,
-                (unsigned long long)two, (unsigned long long)nb_two, (unsigned long long)ids, (unsigned long long)nbs, nbs ? ids / (4.0 * nbs) : 0.0, nbs * 16 / 1e6);
-    }
     s.lay = std::move(lay);
     *snap = std::move(s);
+    debug_rows_report(store, *snap);
 }
 
 

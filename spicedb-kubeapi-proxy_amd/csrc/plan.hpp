@@ -237,5 +237,9 @@ bool patch_reverse(Store &store, int64_t now, uint64_t from_revision, Snapshot *
 uint32_t with_headroom(uint32_t n);
 bool verify_snapshot(Store &store, int64_t now, const Snapshot &snap, ShardSpec shard, std::string *why);
 void build_reverse(Store &store, int64_t now, Snapshot *snap, ShardSpec shard = ShardSpec());
+// ACL_DEBUG_ROWS=1: one stderr line on how the snapshot's hashed rows are placed (rows, two-choice rows, load, slow rows, the largest row and
+// the largest fast row in buckets); ACL_DEBUG_ROWS=2: also one line per SLOW row (type#relation@subject type, subject id, buckets, two-choice
+// flag, seed, ids).  build_forward reports every build; acl_selfcheck_snapshot reports a patched snapshot (tests/test_hashed_rows_cpu.py).
+void debug_rows_report(const Store &store, const Snapshot &snap);
 
 }  // namespace acl

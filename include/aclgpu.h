@@ -282,6 +282,25 @@ void acl_free(void *p);
 int acl_lookup_resources_batch(acl_engine_t *h, int rtype, int permission, int stype, int srel, const uint32_t *subject_ids, size_t n,
                                uint32_t *bitmaps_out, size_t bitmap_words, uint64_t *counts_out);
 
+/* ---- LookupSubjects (PermissionsService.LookupSubjects): who holds `permission` on ONE resource ----
+ * Result = dense bitmap over the subject type's local ids: bit s set <=> Check(resource#permission @ stype:s[#srel]) is HAS_PERMISSION and s is
+ * reached through relationships that name it (within the dispatch-depth limit; for a permission with `-`, `&` or `.all()`: reached by the
+ * positive relaxation `a - b` -> a, `a & b` -> a + b, `a.all(b)` -> a->b, then confirmed by a forward Check).  flags bit 0 (ACL_SUBJECTS_WILDCARD):
+ * a `stype:*` relationship grants it to every subject of the type -- except those of the `excluded` row, which is only computed when asked for
+ * (NULL: not computed) and only non-empty for a permission with `-`, `&` or `.all()`.  A reached subject whose Check runs into the depth limit fails
+ * the call with ACL_ERR_DEPTH, unless the engine was opened with ACL_FLAG_LENIENT_LOOKUP (then it is left out).  An id beyond the resource type's
+ * objects: ACL_ERR_INVALID_ARGUMENT; a resource without relationships: an empty answer.  Sharded engines: ACL_ERR_FAILED_PRECONDITION. */
+#define ACL_SUBJECTS_WILDCARD 1u
+/* batched form: n resources of one (rtype, permission); bitmaps_out (and excluded_out when given) are n * bitmap_words; flags_out may be NULL */
+int acl_lookup_subjects_batch(acl_engine_t *h, int rtype, int permission, int stype, int srel /* -1 none */, const uint32_t *resource_ids, size_t n,
+                              uint32_t *bitmaps_out, size_t bitmap_words, uint64_t *counts_out, uint8_t *flags_out, uint32_t *excluded_out,
+                              const acl_call_opts_t *opts);
+/* string form with engine-owned rows (release with acl_free; names through acl_bitmap_names).  An unknown resource name: an empty row.
+ * excluded_out may be NULL (not computed); *excluded_out is NULL when the answer has no wildcard. */
+int acl_lookup_subjects(acl_engine_t *h, const char *resource_type, const char *resource_id, const char *permission, const char *subject_type,
+                        const char *subject_relation, const acl_call_opts_t *opts, uint32_t **bitmap_out, size_t *words_out, uint64_t *count_out,
+                        int *wildcard_out, uint32_t **excluded_out);
+
 /* ---- the callers either side of the kernels ----
  * PostFilter: filterItemsWithBulkPermissions (postfilter.go:58-182).  The K list items' resolved pairs are ONE bulk
  * check; pairs [item_off[i], item_off[i+1]) belong to list item i (itemToRequestMap, postfilter.go:65,117-119);

@@ -288,10 +288,86 @@ func (s *relStream) Context() context.Context     { return s.ctx }
 func (s *relStream) SendMsg(any) error            { return nil }
 func (s *relStream) RecvMsg(any) error            { return io.EOF }
 
-// Never called by the proxy (SURVEY.md 8(b)): Unimplemented, as a real server without the feature would answer.
-func (p *permissionsClient) LookupSubjects(context.Context, *v1.LookupSubjectsRequest, ...grpc.CallOption) (v1.PermissionsService_LookupSubjectsClient, error) {
-	return nil, status.Error(codes.Unimplemented, "not implemented by the GPU ACL engine")
+// LookupSubjects: who holds a permission on ONE resource (acl_lookup_subjects).  One HAS_PERMISSION message per subject, names fetched a block at a
+// time as for LookupResources; a `T:*` grant comes first as the subject "*" with the subjects it leaves out (unless the request excludes wildcards).
+// Limits and cursors are not supported: Unimplemented, as DeleteRelationships with a limit.
+func (p *permissionsClient) LookupSubjects(ctx context.Context, in *v1.LookupSubjectsRequest, _ ...grpc.CallOption) (v1.PermissionsService_LookupSubjectsClient, error) {
+	if in.OptionalConcreteLimit != 0 || in.OptionalCursor != nil {
+		return nil, status.Error(codes.Unimplemented, "LookupSubjects with a limit or a cursor is not implemented by the GPU ACL engine")
+	}
+	var cs cstrings
+	defer cs.free()
+	var rt, rid string
+	if in.Resource != nil {
+		rt, rid = in.Resource.ObjectType, in.Resource.ObjectId
+	}
+	st := cs.add(in.SubjectObjectType)
+	typeID := C.acl_type_id(p.e.h, st)
+	var bmp, exp *C.uint32_t
+	var words C.size_t
+	var count C.uint64_t
+	var wild C.int
+	opts, stop := callOpts(ctx)
+	defer stop()
+	if rc := C.acl_lookup_subjects(p.e.h, cs.add(rt), cs.add(rid), cs.add(in.Permission), st, cs.add(in.OptionalSubjectRelation), opts, &bmp, &words, &count, &wild, &exp); rc != 0 {
+		return nil, status.Error(itemCode(C.int32_t(rc)), C.GoString(C.acl_last_error()))
+	}
+	bm := make([]C.uint32_t, int(words))
+	copy(bm, unsafe.Slice(bmp, int(words)))
+	C.acl_free(unsafe.Pointer(bmp))
+	at := p.e.zedToken()
+	s := &subjectStream{names: &bitmapStream{ctx: ctx, e: p.e, typeID: typeID, bm: bm, at: at}, at: at}
+	if exp != nil {
+		ex := make([]C.uint32_t, int(words))
+		copy(ex, unsafe.Slice(exp, int(words)))
+		C.acl_free(unsafe.Pointer(exp))
+		if wild != 0 && in.WildcardOption != v1.LookupSubjectsRequest_WILDCARD_OPTION_EXCLUDE_WILDCARDS {
+			s.wild = true
+			exs := &bitmapStream{ctx: ctx, e: p.e, typeID: typeID, bm: ex, at: at}
+			for {
+				r, err := exs.Recv()
+				if err == io.EOF {
+					break
+				}
+				if err != nil {
+					return nil, err
+				}
+				s.excluded = append(s.excluded, &v1.ResolvedSubject{SubjectObjectId: r.ResourceObjectId,
+					Permissionship: v1.LookupPermissionship_LOOKUP_PERMISSIONSHIP_NO_PERMISSION})
+			}
+		}
+	}
+	return s, nil
 }
+
+// subjectStream: the wildcard message (if any), then one message per subject of the row
+type subjectStream struct {
+	names    *bitmapStream
+	wild     bool
+	excluded []*v1.ResolvedSubject
+	at       *v1.ZedToken
+}
+
+func (s *subjectStream) Recv() (*v1.LookupSubjectsResponse, error) {
+	if s.wild {
+		s.wild = false
+		return &v1.LookupSubjectsResponse{LookedUpAt: s.at, SubjectObjectId: "*", Permissionship: v1.LookupPermissionship_LOOKUP_PERMISSIONSHIP_HAS_PERMISSION,
+			Subject:          &v1.ResolvedSubject{SubjectObjectId: "*", Permissionship: v1.LookupPermissionship_LOOKUP_PERMISSIONSHIP_HAS_PERMISSION},
+			ExcludedSubjects: s.excluded}, nil
+	}
+	r, err := s.names.Recv()
+	if err != nil {
+		return nil, err
+	}
+	return &v1.LookupSubjectsResponse{LookedUpAt: s.at, SubjectObjectId: r.ResourceObjectId, Permissionship: r.Permissionship,
+		Subject: &v1.ResolvedSubject{SubjectObjectId: r.ResourceObjectId, Permissionship: r.Permissionship}}, nil
+}
+func (s *subjectStream) Header() (metadata.MD, error) { return nil, nil }
+func (s *subjectStream) Trailer() metadata.MD         { return nil }
+func (s *subjectStream) CloseSend() error             { return nil }
+func (s *subjectStream) Context() context.Context     { return s.names.ctx }
+func (s *subjectStream) SendMsg(any) error            { return nil }
+func (s *subjectStream) RecvMsg(any) error            { return io.EOF }
 func (p *permissionsClient) ExpandPermissionTree(context.Context, *v1.ExpandPermissionTreeRequest, ...grpc.CallOption) (*v1.ExpandPermissionTreeResponse, error) {
 	return nil, status.Error(codes.Unimplemented, "not implemented by the GPU ACL engine")
 }

@@ -29,6 +29,7 @@ SYMBOLS = [
     "acl_shard_rccl_destroy", "acl_shard_check_bulk_rccl", "acl_shard_lookup_bulk", "acl_shard_lookup_bulk_rccl", "acl_selfcheck_compaction", "acl_check_one_submit", "acl_check_completions",
     "acl_lookup_one_submit", "acl_lookup_completions", "acl_prefilter_response", "acl_open_replicas", "acl_replica_calls", "acl_watch_wait", "acl_watch_recheck", "acl_load_bootstrap_yaml",
     "acl_check_bulk_v_opts", "acl_object_name_copy", "acl_resolve_bulk_v", "acl_check_bulk_packed", "acl_check_bulk_keep_v", "acl_check_bulk_keep_packed", "acl_selfcheck_json_array", "acl_bitmap_names",
+    "acl_lookup_subjects_batch", "acl_lookup_subjects",
 ]
 
 
@@ -213,6 +214,10 @@ def load():
     L.acl_prefilter_response.argtypes = [H, C.c_int, C.c_void_p, C.c_size_t, C.c_char_p, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                                          C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.acl_free.argtypes = [C.c_void_p]
+    L.acl_lookup_subjects_batch.argtypes = [H, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.POINTER(CallOpts)]
+    L.acl_lookup_subjects.argtypes = [H, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(CallOpts), C.POINTER(C.POINTER(C.c_uint32)),
+                                      C.POINTER(C.c_size_t), C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.POINTER(C.c_uint32))]
     L.acl_free.restype = None
     L.acl_check_one_opts.argtypes = [H, C.POINTER(CheckItem), C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(CallOpts)]
     L.acl_check_one_submit.argtypes = [H, C.POINTER(CheckItem), C.c_uint64]

@@ -653,6 +653,43 @@ class Engine:
         bms, _ = self.lookup_ids_batch(rtype, perm, stype, srel, [subject_id])
         return np.flatnonzero(np.unpackbits(bms[0].view(np.uint8), bitorder="little")).astype(np.uint32)
 
+    # ---- LookupSubjects (not Workload.lookup_subjects: that is C3's list of LookupResources subjects)
+    def lookup_subjects_ids_batch(self, rtype, perm, stype, srel, resource_ids, want_excluded=False, cancel=None, timeout_s=None):
+        """n resources of one (type, permission) -> (bitmaps [n, words] u32 over the subject type's ids, counts [n] u64, flags [n] u8 (bit 0: a
+        `stype:*` wildcard grants it)[, excluded [n, words] u32: who the wildcard leaves out, when want_excluded])."""
+        rids = np.ascontiguousarray(resource_ids, dtype=np.uint32)
+        words = max(1, (self.object_count(stype) + 31) // 32)
+        bms = np.zeros((rids.size, words), dtype=np.uint32)
+        counts = np.zeros(rids.size, dtype=np.uint64)
+        flags = np.zeros(rids.size, dtype=np.uint8)
+        ex = np.zeros((rids.size, words), dtype=np.uint32) if want_excluded else None
+        o = self._opts(cancel, timeout_s)
+        self._check(self._L.acl_lookup_subjects_batch(self._h, self.type_id(rtype), self.relation_id(rtype, perm), self.type_id(stype), self.relation_id(stype, srel),
+                                                      rids.ctypes.data, rids.size, bms.ctypes.data, words, counts.ctypes.data, flags.ctypes.data,
+                                                      ex.ctypes.data if ex is not None else None, C.byref(o) if o else None))
+        return (bms, counts, flags, ex) if want_excluded else (bms, counts, flags)
+
+    def lookup_subjects_bitmap(self, rt, rid, perm, st, srel="", want_excluded=True, cancel=None, timeout_s=None):
+        """acl_lookup_subjects -> (bitmap u32, count, wildcard, excluded bitmap or None); the rows are the engine's (acl_free)."""
+        bm, words, cnt, wild = C.POINTER(C.c_uint32)(), C.c_size_t(), C.c_uint64(), C.c_int()
+        ex = C.POINTER(C.c_uint32)()
+        o = self._opts(cancel, timeout_s)
+        self._check(self._L.acl_lookup_subjects(self._h, _b(rt), _b(rid), _b(perm), _b(st), _b(srel or ""), C.byref(o) if o else None, C.byref(bm), C.byref(words),
+                                                C.byref(cnt), C.byref(wild), C.byref(ex) if want_excluded else None))
+        try:
+            a = np.ctypeslib.as_array(bm, shape=(words.value,)).copy() if words.value else np.zeros(0, dtype=np.uint32)
+            e = np.ctypeslib.as_array(ex, shape=(words.value,)).copy() if (want_excluded and bool(ex)) else None
+        finally:
+            self._L.acl_free(bm)
+            if want_excluded and bool(ex):
+                self._L.acl_free(ex)
+        return a, cnt.value, bool(wild.value), e
+
+    def lookup_subjects(self, rt, rid, perm, st, srel=""):
+        """LookupSubjects(rt:rid#perm, subject type st[#srel]) -> (subject names, wildcard: bool, excluded names); names through acl_bitmap_names."""
+        a, _, wild, e = self.lookup_subjects_bitmap(rt, rid, perm, st, srel)
+        return set(self.bitmap_names(st, a)), wild, (set(self.bitmap_names(st, e)) if e is not None else set())
+
     def selfcheck_snapshot(self) -> bool:
         """Test hook (store-only engines): update + verify the host snapshot; True when the update was an in-place patch."""
         return self.selfcheck_snapshot_code() == 1

@@ -461,7 +461,7 @@ int device_of(acl_engine *h, const void *p) {
     return a.device;
 }
 
-int Eval::begin(acl_engine *h_, bool need_reverse, const CallOpts &opts, int rev_key_slot, int on_device) {
+int Eval::begin(acl_engine *h_, bool need_reverse, const CallOpts &opts, int rev_key_slot, int on_device, bool need_subjects) {
     h = h_;
     if (h->store_only) return fail(ACL_ERR_UNAVAILABLE, "engine was opened store-only (no GPU): Check / LookupResources are unavailable");
     int rc = check_opts(opts);
@@ -473,6 +473,7 @@ int Eval::begin(acl_engine *h_, bool need_reverse, const CallOpts &opts, int rev
         if (ok && need_reverse && rev_key_slot >= 0 &&
             h->store.objects(h->store.schema().slot_owner[rev_key_slot].first).count() > h->snap.slot_nobjects[rev_key_slot])
             ok = false;
+        if (ok && need_subjects && !subjects_current(h)) ok = false;
         if (ok) {
             locked = true;
             break;
@@ -480,6 +481,7 @@ int Eval::begin(acl_engine *h_, bool need_reverse, const CallOpts &opts, int rev
         h->state_mu.unlock_shared();
         std::lock_guard<RwLock> lk(h->state_mu);
         rc = need_reverse ? ensure_reverse(h) : ensure_snapshot(h);
+        if (rc == ACL_OK && need_subjects) rc = ensure_subjects(h);
         if (rc) return rc;
     }
     // a context from the pool (created on demand up to max_ctx per replica)

@@ -239,6 +239,7 @@ struct PassCtx {
     DevArray<int32_t> d_errout;
     DevArray<uint4> d_items;
     DevArray<uint32_t> d_sids, d_visited, d_rows;
+    DevArray<uint32_t> d_subj_visited, d_subj_rows, d_subj_flags;  // LookupSubjects (k_subj_local): visited regions, result rows, wildcard flags
     // result rows beyond the block's LDS (kernels.hpp RevBigRows): the lookups' deferred terminal rows, their counts / levels, the id-count accumulators
     DevArray<uint8_t> d_big_bytes;  // the lookups' byte maps, zero between launches (bytes_zeroed: the leading bytes known to be)
     size_t big_bytes_zeroed = 0;
@@ -327,6 +328,10 @@ struct DevState {
     DevArray<RevOp> d_rops;
     DevArray<RevProg> d_rprogs, d_rseeds;
     DevArray<uint64_t> d_rdest;
+    // subject rows (LookupSubjects; built on demand for acl_engine::subj, engine_subjects.cpp)
+    DevArray<uint32_t> d_smeta, d_sids, d_svbase, d_svn;
+    DevArray<SubjOp> d_sops;
+    uint64_t subj_epoch = ~0ull;  // acl_engine::subj.epoch these arrays hold
     // evaluation contexts of this device (the pool's lock and condition variable are the engine's)
     std::vector<std::unique_ptr<PassCtx>> ctxs;  // created lazily up to max_ctx
     std::vector<PassCtx *> free_ctxs;
@@ -371,6 +376,7 @@ struct acl_engine {
     // The pair form of that route on a RECURSIVE permission (Snapshot::slot_deep: the schema alone cannot rule a depth error out) needs to know that THE DATA rules it
     // out: no object of the type whose Check runs into the dispatch-depth limit.  That is a property of the snapshot, not of the subject (engine.cpp
     // no_object_is_deep): one forward sweep over the type's objects for a subject nobody is, remembered per (type, permission, subject type) and snapshot epoch.
+    SubjectRows subj;         // LookupSubjects' rows for the snapshot of subj.epoch (built lazily under state_mu exclusive)
     uint64_t snap_epoch = 0;  // counts the snapshot's changes (ensure_snapshot, under state_mu exclusive; read under state_mu shared)
     struct DeepKnown {
         int rt = -1, pm = -1, st = -1;
@@ -493,6 +499,8 @@ void ev_collect(PassCtx *c);  // stream must be synchronized
 // snapshot maintenance; caller holds state_mu EXCLUSIVE
 int ensure_snapshot(acl_engine *h);
 int ensure_reverse(acl_engine *h);
+int ensure_subjects(acl_engine *h);     // engine_subjects.cpp; the snapshot is current
+bool subjects_current(acl_engine *h);   // caller holds state_mu at least shared
 // true when the device snapshot answers for the store as it is now (caller holds state_mu at least shared)
 bool snapshot_current(acl_engine *h, bool need_reverse);
 void compaction_join(acl_engine *h);  // acl_close / schema reload: waits for a build in flight and drops its result
@@ -508,7 +516,8 @@ struct Eval {
     ~Eval() { end(); }
     // rev_key_slot >= 0: the lookup's subject is `type#relation` of that slot -- the reverse rows must cover its id space
     // on_device >= 0: only a replica on that HIP device will do (calls that are handed device pointers)
-    int begin(acl_engine *h_, bool need_reverse, const CallOpts &opts = CallOpts(), int rev_key_slot = -1, int on_device = -1);
+    // need_subjects: the subject rows of LookupSubjects must be current too (engine_subjects.cpp ensure_subjects)
+    int begin(acl_engine *h_, bool need_reverse, const CallOpts &opts = CallOpts(), int rev_key_slot = -1, int on_device = -1, bool need_subjects = false);
     void end();
 };
 

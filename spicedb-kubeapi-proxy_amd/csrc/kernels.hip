@@ -2916,4 +2916,277 @@ void launch_rev_import(hipStream_t s, const DevReverse &r, const DevFrontier &f,
     hipLaunchKernelGGL(k_import<false>, dim3(import_blocks(n)), dim3(256), 0, s, f, iter, in, n, (const SlotProg *)nullptr, r.rprogs, 0u);
 }
 
+// ---- LookupSubjects: k_subj_local (plan.hpp SubjectRows).  One block walks one lookup -- the resource's own state and everything the FORWARD programs
+// reach from it -- and writes the subjects of type T (of `key`) it finds into a row of T's ids.  The walk is the positive relaxation of the Check the
+// programs encode: ops inside the subtracted operand of an exclusion are skipped (SubjOp kSubjSkip), both sides of `&` and the tupleset of `.all()` are
+// walked.  Emission rules per op, at dispatch level L = the state's level + op.dlevel <= kMaxLevels (k_check_local's rule: a Check answers HAS there):
+//   OP_PROBE_HASH of key T      -> every id of the class's subject row for the state's object (OP_WILD: the row is the wildcard's -> the flag)
+//   OP_PROBE of key T (sorted)  -> every id of the sorted row
+//   OP_REFLEX of key T#r        -> the state's own id
+//   OP_ENUM / OP_PUSH_SAME      -> child states at L + 1 (when L + 1 <= kMaxLevels); a userset row of key T#r is emitted through its children's REFLEX
+//                                  ops, or, when the children would lie beyond the limit, by the probe itself
+// Depth: a state counts at the LEAST level it can be reached at.  The log is processed level by level; a child one level below the current one gets its
+// visited bit when it is appended (nothing of a lower level is still to come), a child further down (an inlined computed userset's offset) is appended
+// unmarked and decides its visit when its own level comes round -- after every state of the levels before it has been marked.
+constexpr int kSubjThreads = 1024;
+constexpr uint32_t kSubjMaxRow = 1u << 21;        // ids of one row a task may enumerate (1 024 tasks x 2 M stay inside 32-bit prefix sums)
+constexpr uint32_t kSubjMarked = 0x80000000u;     // log entry: its visit was decided when it was appended
+constexpr uint32_t kSubjDead = 0x40000000u;       // log entry: a second visit, or moved behind the current level: not expanded here
+constexpr uint32_t kSubjEmitEdges = 1u << 30, kSubjEmitIds = 2u << 30, kSubjChild = 3u << 30;  // task kinds (tag bits 30-31)
+namespace {
+struct SubjTaskLds {
+    uint32_t start[kSubjThreads];
+    uint32_t prefix[kSubjThreads + 1];
+    uint32_t tag[kSubjThreads];  // kind | child level << 16 | child slot
+};
+// ORs bit `id` into the result row; lanes holding the same 32-bit word (ascending ids of one row) fold their bits first and one lane issues the atomic.
+// Call in wave-uniform control flow.
+__device__ __forceinline__ void subj_mark(uint32_t *row, bool lds, uint32_t id, bool valid, uint32_t nbits, uint32_t lane) {
+    valid = valid && id < nbits;
+    const uint32_t w = valid ? id >> 5 : 0xFFFFFFFFu;
+    uint32_t b = valid ? 1u << (id & 31u) : 0u;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t ow = (uint32_t)__shfl_down((int)w, d), ob = (uint32_t)__shfl_down((int)b, d);
+        if (lane + (uint32_t)d < 64u && ow == w) b |= ob;
+    }
+    const uint32_t pw = (uint32_t)__shfl_up((int)w, 1);
+    if (valid && (lane == 0u || pw != w)) {
+        if (lds) atomicOr(row + w, b);
+        else __hip_atomic_fetch_or(row + w, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+}  // namespace
+
+__global__ __launch_bounds__(kSubjThreads) void k_subj_local(DevSubjects g, const uint32_t *__restrict__ rids, uint32_t target_slot, uint32_t key, uint2 *logs,
+                                                             uint32_t cap, uint32_t *visited_all, uint32_t *rows, uint32_t row_words, uint32_t lds_words, uint32_t prog_lds,
+                                                             uint32_t *flags_out, uint32_t *status) {
+    __shared__ SubjTaskLds t;
+    __shared__ uint32_t s_end, s_stop, s_wild, s_wave_tot[kSubjThreads / 64];
+    // dynamic LDS: [programs | ops | side table] when prog_lds, then the result row when lds_words
+    extern __shared__ uint4 s_dyn[];
+    const uint32_t tid = threadIdx.x, lane = lane_id(), wib = tid >> 6;
+    const uint32_t req = blockIdx.x;
+    const SlotProg *progs = g.progs;
+    const FwdOp *ops = g.ops;
+    const SubjOp *sops = g.sops;
+    uint32_t *dyn_words = reinterpret_cast<uint32_t *>(s_dyn);
+    if (prog_lds) {
+        SlotProg *lp = reinterpret_cast<SlotProg *>(s_dyn);
+        FwdOp *lo = reinterpret_cast<FwdOp *>(lp + g.nslots);
+        SubjOp *ls = reinterpret_cast<SubjOp *>(lo + g.nops);
+        for (uint32_t i = tid; i < g.nslots; i += kSubjThreads) lp[i] = g.progs[i];
+        for (uint32_t i = tid; i < g.nops; i += kSubjThreads) {
+            lo[i] = g.ops[i];
+            ls[i] = g.sops[i];
+        }
+        progs = lp;
+        ops = lo;
+        sops = ls;
+        dyn_words = reinterpret_cast<uint32_t *>(ls + g.nops);
+    }
+    const bool row_lds = lds_words != 0u;
+    uint32_t *const row = row_lds ? dyn_words : rows + (size_t)req * row_words;
+    const uint32_t nbits = row_words * 32u;
+    uint32_t *__restrict__ visited = visited_all + (size_t)req * g.visited_words;
+    uint2 *const log = logs + (size_t)req * cap;
+    for (uint32_t i = tid; i < lds_words; i += kSubjThreads) row[i] = 0u;
+    if (tid == 0) {
+        s_end = 1;
+        s_stop = 0;
+        s_wild = 0;
+        log[0] = make_uint2(rids[req], target_slot | (1u << 16));
+    }
+    __syncthreads();
+    const bool rel_key = key < g.nslots;  // the subject carries a relation: REFLEX ops count
+    const uint32_t W = rel_key ? g.max_ops_rel : g.max_ops;
+    const uint2 *__restrict__ meta2 = reinterpret_cast<const uint2 *>(g.meta);
+    const uint2 *__restrict__ smeta2 = reinterpret_cast<const uint2 *>(g.smeta);
+
+    // wave-cooperative append to the block's log (wave-uniform control flow)
+    auto append = [&](bool push, uint32_t id, uint32_t y) {
+        const uint64_t b = __ballot(push);
+        if (!b) return;
+        uint32_t base = 0;
+        if (lane == 0) base = atomicAdd(&s_end, (uint32_t)__popcll(b));
+        base = uniform(base);
+        if (base + (uint32_t)__popcll(b) > cap) {
+            if (lane == 0) s_stop = 1u;
+            return;
+        }
+        if (push) log[base + lanes_below(b)] = make_uint2(id, y);
+    };
+    // first visit of state (slot, id)?  (workgroup scope: the region is this block's own)
+    auto first_visit = [&](uint32_t slot, uint32_t id) -> bool {
+        const uint32_t vb = g.slot_vbase[slot];
+        if (vb == kSubjNoBits) return true;  // (the root's slot when nothing else produces its states)
+        if (id >= g.slot_vn[slot]) return false;
+        const uint32_t m = 1u << (id & 31u);
+        return !(__hip_atomic_fetch_or(visited + vb + (id >> 5), m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) & m);
+    };
+    // child (slot, id) at level lvl, produced while level `cur` is expanded
+    auto child = [&](uint32_t id, uint32_t slot, uint32_t lvl, uint32_t cur, bool valid) {
+        bool push = false;
+        uint32_t y = slot | (lvl << 16);
+        if (valid) {
+            if (lvl == cur + 1u) {
+                push = first_visit(slot, id);
+                y |= kSubjMarked;
+            } else {
+                push = true;
+            }
+        }
+        append(push, id, y);
+    };
+
+    uint32_t lo = 0, level = 1;
+    int stop = 0;
+    for (; level <= kMaxLevels; level++) {
+        const uint32_t hi = s_end;  // (behind the previous round's closing barrier)
+        __syncthreads();            // (every wave has read it before the first append of this level moves it)
+        if (hi == lo || hi > cap) break;
+        // ---- stage A: entries of later levels move behind this one; unmarked entries of this level decide their visit now
+        for (uint32_t b0 = lo; b0 < hi; b0 += kSubjThreads) {
+            const uint32_t i = b0 + tid;
+            bool later = false;
+            uint2 en = make_uint2(0u, 0u);
+            if (i < hi) {
+                en = log[i];
+                const uint32_t lv = (en.y >> 16) & 63u;
+                if (lv > level) {
+                    later = true;
+                    log[i].y = en.y | kSubjDead;
+                } else if (!(en.y & kSubjMarked) && !first_visit(en.y & 0xFFFFu, en.x)) {
+                    log[i].y = en.y | kSubjDead;
+                }
+            }
+            append(later, en.x, en.y & ~(kSubjMarked | kSubjDead));
+        }
+        __syncthreads();
+        // ---- stage B: (state, op) pairs, one per thread and round
+        const uint32_t npairs = (hi - lo) * W;
+        for (uint32_t pb = 0; pb < npairs; pb += kSubjThreads) {
+            const uint32_t q = pb + tid;
+            uint32_t deg = 0, start = 0, tag = 0, id = 0, one_slot = 0, one_lvl = 0;
+            bool one_child = false, one_emit = false;
+            if (q < npairs) {
+                const uint32_t e = q / W, j = q - e * W;
+                const uint2 en = log[lo + e];
+                if (!(en.y & kSubjDead)) {
+                    const SlotProg p = progs[en.y & 0xFFFFu];
+                    const uint32_t nops = rel_key ? p.n_total : p.n_main;
+                    id = en.x;
+                    if (j < nops && !(sops[p.first + j].flags & kSubjSkip)) {
+                        const FwdOp op = ops[p.first + j];
+                        const uint32_t L = level + op.dlevel;
+                        if (L <= kMaxLevels) {
+                            if (op.flags & OP_REFLEX) {
+                                one_emit = op.key == key;
+                            } else if (op.flags & OP_PUSH_SAME) {
+                                if (L + 1u <= kMaxLevels) {
+                                    one_child = true;
+                                    one_slot = op.key;
+                                    one_lvl = L + 1u;
+                                }
+                            } else if (op.flags & OP_PROBE_HASH) {
+                                const SubjOp so = sops[p.first + j];
+                                if (op.key == key && id < so.nrows) {
+                                    const uint2 rd = smeta2[so.base + id];
+                                    if (rd.y > rd.x) {
+                                        if (op.flags & OP_WILD) s_wild = 1u;
+                                        else if (rd.y - rd.x > kSubjMaxRow) s_stop = 2u;
+                                        else {
+                                            start = rd.x;
+                                            deg = rd.y - rd.x;
+                                            tag = kSubjEmitIds;
+                                        }
+                                    }
+                                }
+                            } else if (id < op.nrows) {
+                                const uint2 md = meta2[op.base + id * op.K + op.k];
+                                if (md.y > md.x) {
+                                    const bool probe = (op.flags & OP_PROBE) && op.key == key;
+                                    const bool enm = (op.flags & OP_ENUM) && L + 1u <= kMaxLevels;
+                                    if (md.y - md.x > kSubjMaxRow) {
+                                        if (probe || enm) s_stop = 2u;
+                                    } else if (enm) {
+                                        start = md.x;
+                                        deg = md.y - md.x;
+                                        tag = kSubjChild | ((L + 1u) << 16) | op.key;
+                                    } else if (probe) {
+                                        start = md.x;
+                                        deg = md.y - md.x;
+                                        tag = kSubjEmitEdges;
+                                    }
+                                }
+                            }
+                        }
+                    }
+                }
+            }
+            subj_mark(row, row_lds, id, one_emit, nbits, lane);
+            child(id, one_slot, one_lvl, level, one_child);
+            // ---- block-wide exclusive prefix of the degrees
+            const uint32_t incl = wave_incl_scan(deg, lane);
+            if (lane == 63) s_wave_tot[wib] = incl;
+            __syncthreads();
+            uint32_t before = 0, total = 0;
+#pragma unroll
+            for (uint32_t w = 0; w < kSubjThreads / 64; w++) {
+                const uint32_t wt = s_wave_tot[w];
+                before += w < wib ? wt : 0u;
+                total += wt;
+            }
+            if (total) {  // (block-uniform)
+                t.prefix[tid] = before + incl - deg;
+                t.start[tid] = start;
+                t.tag[tid] = tag;
+                __syncthreads();
+                // lanes walk the concatenated rows: consecutive lanes, consecutive ids of one row (one task: "the last whose prefix is <= w")
+                for (uint32_t wb = 0; wb < total; wb += kSubjThreads) {
+                    const uint32_t w = wb + tid;
+                    const bool valid = w < total;
+                    const uint32_t wv = valid ? w : total - 1u;
+                    uint32_t jt = 0;
+#pragma unroll
+                    for (uint32_t step = kSubjThreads / 2; step >= 1; step >>= 1)
+                        if (t.prefix[jt + step] <= wv) jt += step;
+                    const uint32_t tg = t.tag[jt], kind = tg & (3u << 30);
+                    const uint32_t pos = t.start[jt] + (wv - t.prefix[jt]);
+                    const uint32_t v = kind == kSubjEmitIds ? gld(g.sids, pos) : (gld(g.edges, pos) & kIdMask);
+                    subj_mark(row, row_lds, v, valid && kind != kSubjChild, nbits, lane);
+                    child(v, tg & 0xFFFFu, (tg >> 16) & 63u, level, valid && kind == kSubjChild);
+                }
+            }
+            // (also the barrier behind the task list: every lane is done with it before the next round overwrites it)
+            stop = __syncthreads_or(s_stop != 0u);
+            if (stop) break;
+        }
+        if (stop) break;
+        lo = hi;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        if (s_stop) *status = s_stop;
+        flags_out[req] = s_wild;
+    }
+    if (row_lds) {
+        uint32_t *orow = rows + (size_t)req * row_words;
+        for (uint32_t i = tid; i < row_words; i += kSubjThreads) orow[i] = i < lds_words ? row[i] : 0u;
+    }
+}
+
+void launch_subj_local(hipStream_t s, const DevSubjects &g, const uint32_t *rids, uint32_t n, uint32_t target_slot, uint32_t key, void *logs, uint32_t cap,
+                       uint32_t *visited, uint32_t *rows, uint32_t row_words, uint32_t *flags_out, uint32_t *status) {
+    if (!n) return;
+    static const bool big_lds =
+        hipFuncSetAttribute(reinterpret_cast<const void *>(k_subj_local), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kRevLdsRowBytes + kSubjLdsProgBytes)) == hipSuccess;
+    const size_t prog_bytes = (size_t)g.nslots * sizeof(SlotProg) + (size_t)g.nops * (sizeof(FwdOp) + sizeof(SubjOp));
+    const uint32_t prog_lds = prog_bytes <= kSubjLdsProgBytes ? 1u : 0u;
+    const uint32_t lds_words = (size_t)row_words * 4u <= (big_lds ? kRevLdsRowBytes : 16384u) ? row_words : 0u;
+    const size_t dyn = (prog_lds ? prog_bytes : 0u) + (size_t)lds_words * 4u;
+    hipLaunchKernelGGL(k_subj_local, dim3(n), dim3(kSubjThreads), dyn, s, g, rids, target_slot, key, (uint2 *)logs, cap, visited, rows, row_words, lds_words, prog_lds,
+                       flags_out, status);
+}
+
 }  // namespace acl

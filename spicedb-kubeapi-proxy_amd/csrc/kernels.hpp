@@ -166,6 +166,22 @@ void launch_rev_local(hipStream_t s, const DevReverse &r, const uint32_t *sids, 
                       uint32_t *done_ctr = nullptr, uint32_t *done_flag = nullptr, uint32_t done_val = 0 /* as launch_check_local: the last block stores done_val into the pinned
                       word done_flag behind a system-scope release of every block's rows, counts and status */,
                       const RevBigRows *big = nullptr, const RevUseful *useful = nullptr /* NULL: every slot */);
+// single-launch LookupSubjects (kernels.hip k_subj_local): block b walks the forward programs from resource rids[b] of `target_slot` and marks the ids of the
+// subjects of `key` it reaches in rows + b * row_words (device memory; zeroed by the caller when the row does not fit the block's LDS: row_words * 4 >
+// kRevLdsRowBytes); flags_out[b] = 1 when a `T:*` row was reached.  visited: [n][g.visited_words] zeroed by the caller; logs: [n][cap] 8-byte entries.
+// *status != 0 afterwards (the caller zeroes it): 1 = a block's log overflowed (redo with a larger cap), 2 = a row beyond the per-task enumeration limit.
+struct DevSubjects {
+    const uint32_t *meta, *edges;  // the forward snapshot's sorted rows
+    const FwdOp *ops;
+    const SlotProg *progs;
+    const SubjOp *sops;            // [nops] side table (plan.hpp)
+    const uint32_t *smeta, *sids;  // subject rows
+    const uint32_t *slot_vbase, *slot_vn;
+    uint32_t nslots, nops, visited_words, max_ops, max_ops_rel;
+};
+constexpr uint32_t kSubjLdsProgBytes = 16u << 10;  // programs + ops + side table staged in LDS up to this size
+void launch_subj_local(hipStream_t s, const DevSubjects &g, const uint32_t *rids, uint32_t n, uint32_t target_slot, uint32_t key, void *logs, uint32_t cap,
+                       uint32_t *visited, uint32_t *rows, uint32_t row_words, uint32_t *flags_out, uint32_t *status);
 // blocks per expand launch for this device (all co-resident); nwaves = blocks * kWavesPerBlock
 int expand_grid_blocks(int device);
 

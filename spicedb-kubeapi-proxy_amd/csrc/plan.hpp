@@ -210,6 +210,35 @@ struct Snapshot {
     uint64_t visited_bits = 0;
 };
 
+// ---- subject rows (LookupSubjects: who holds a permission on ONE resource; built on demand, plan_subjects.cpp).  The forward programs
+// already enumerate usersets and arrows over the sorted rows; what they cannot do is LIST the subjects of a membership-only class, whose rows
+// are indexed by subject.  The subject rows are their transpose: per (hashed class, RESOURCE id) a {start, end} descriptor into ascending
+// subject ids.  A `T:*` class gets one too: its only member is the wildcard id, which the walk turns into the answer's wildcard flag.
+struct SubjOp {         // 16 B, one per FwdOp (same index as Snapshot::ops): what k_subj_local needs beyond the op itself
+    uint32_t base;      // OP_PROBE_HASH: first descriptor (uint2 units) of the class's subject rows in SubjectRows::smeta
+    uint32_t nrows;     // ... resource ids they cover
+    uint32_t flags;     // kSubjSkip: the op lies inside the subtracted operand of an exclusion (the positive relaxation drops it)
+    uint32_t pad;
+};
+constexpr uint32_t kSubjSkip = 1u;
+constexpr uint32_t kSubjNoBits = 0xFFFFFFFFu;  // SubjectRows::slot_vbase: the slot's states are never a walk's children (no visited bits)
+struct SubjectRows {
+    uint64_t epoch = ~0ull;           // acl_engine::snap_epoch it was built for
+    std::vector<uint32_t> smeta;      // uint2 {start, end} per (hashed class, resource id) into sids
+    std::vector<uint32_t> sids;       // subject ids, ascending per row
+    std::vector<SubjOp> sops;         // [Snapshot::ops.size()]
+    std::vector<uint32_t> slot_vbase; // [nslots] first visited WORD of the slot's states in a lookup's region (kSubjNoBits: none)
+    std::vector<uint32_t> slot_vn;    // [nslots] ids those bits cover
+    std::vector<uint32_t> type_cover; // [ntypes] object count of each type the rows were sized for (a larger count: rebuild)
+    uint32_t visited_words = 1;       // per lookup
+    uint32_t max_ops = 0, max_ops_rel = 0;  // largest n_main / n_total of any slot (work items per state)
+    size_t bytes() const { return smeta.size() * 4 + sids.size() * 4 + sops.size() * sizeof(SubjOp) + (slot_vbase.size() + slot_vn.size()) * 4; }
+};
+// Builds the subject rows of every live hashed class of `snap` (same expiry filter as the forward rows) and the per-op side table.
+void build_subjects(Store &store, int64_t now, const Snapshot &snap, SubjectRows *out);
+// The side table's relaxation rule alone: per op of `snap`, 1 when it lies inside the subtracted operand of an exclusion (tests).
+std::vector<uint8_t> subject_skip_ops(const Snapshot &snap);
+
 // Graph partition of the north star's multi-GPU configuration: rows (and programs) of an object type live on
 // shard mix(fnv1a(type name)) mod world (plan.cpp shard_of_type).  world == 1: everything is local.
 struct ShardSpec {

@@ -29,25 +29,13 @@
 // Bound (profiles/r06_pmc_c4.md, r06_ab_check_local.txt): the CHAIN of dependent trips a wave makes per pair of segments, not HBM and
 // (round 6's A/Bs) not instruction issue -- no MFMA anywhere by design.
 #include <algorithm>
-#include <cstdlib>
+#include <type_traits>
 
 #include "kernels.hpp"
 
 namespace acl {
 namespace {
 
-#ifndef ACL_PERTURB
-#define ACL_PERTURB 0  // cost attribution (tools/perturb.sh, profiles/r01_c4_bottleneck_analysis.md): repeat ONE kind of work, results unchanged.
-                       // 1 has[] read / entry, 2 row-descriptor gather / entry, 3 hashed probe / child, 5 edge gather / child,
-                       // 6 ~60 VALU / child, 7 random bucket gather / child, 8 six LDS reads / child, 9 entry re-read / entry
-#endif
-#define ACL_KEEP(x) asm volatile("" ::"v"(x))
-#ifndef ACL_ANS_LDS
-#define ACL_ANS_LDS 1  // with ACL_ENTRY8: the unit's answer bytes (has / err) in LDS (ans_get / ans_set); 0 = in global memory as before (A/B builds)
-#endif
-#ifndef ACL_ENTRY8
-#define ACL_ENTRY8 1  // 8-byte frontier entries in the single-launch walk (put_entry); 0 = the 16-byte form everywhere (A/B builds, tools/build_variant.sh)
-#endif
 constexpr int kBlock = kWavesPerBlock * 64;
 #ifndef ACL_MIN_WAVES_PER_SIMD
 #define ACL_MIN_WAVES_PER_SIMD 6  // (k_expand, k_rev_expand; the single-launch kernel has its own bound below)
@@ -132,19 +120,10 @@ __device__ unsigned long long acl_phase_cycles[16];
 #endif
 
 // LDS-staged task list of one wave.
-#ifndef ACL_TASK_PAD
-#define ACL_TASK_PAD 0  // 1: a task record is 20 bytes, not 16 (round 6; VERDICT r5 weak #2: 40 % of the walk's LDS cycles were bank-conflict cycles).  The children of a window
-                        // read the records of ~25 consecutive tasks, one dword each: at a 16-byte stride eight records cover the 32 banks and record j meets
-                        // j + 8, j + 16, j + 24 in one bank (4-way conflicts on every per-child read); at 20 bytes (5 dwords, coprime with 32) 32 consecutive
-                        // records sit in 32 different banks.  MEASURED, same box (profiles/r06_ab_check_local.txt): C4 209.2 us padded against 208.4 us plain, the
-                        // replica 280.2 against 279.8 -- the conflicts lengthen LDS accesses that sit in the shadow of the global trips, and the padded
-                        // records cost 6 KB of LDS per block.  Off by default; kept as an A/B knob
-#endif
+// A task record is 16 bytes.  (A 20-byte record, whose 5-dword stride is coprime with the 32 banks, removes the 4-way conflicts of the per-child
+// reads but was not faster and costs 6 KB of LDS per block: profiles/r06_ab_check_local.txt)
 struct TaskRec {
     uint32_t x, y, z, w;
-#if ACL_TASK_PAD
-    uint32_t pad;
-#endif
     __device__ __forceinline__ TaskRec &operator=(const uint4 &v) {
         x = v.x; y = v.y; z = v.z; w = v.w;
         return *this;
@@ -430,17 +409,6 @@ __device__ __forceinline__ bool eval_child(const DevGraph &g, const SlotProg *pr
 #ifndef ACL_ISA_NO_SLOW
 #define ACL_ISA_NO_SLOW 0  // 1: tools/isa_loops.py only -- the simple expansion WITHOUT its rare slow-row block, so that the static instruction counts are the main path's (never run)
 #endif
-#ifndef ACL_PUSH_RECHECK
-#define ACL_PUSH_RECHECK 1  // the expansions look at the request's answer byte (LDS) once more before they write its children: a request answered
-                            // by this step's hits -- or by another wave a moment ago -- needs none of them, and an entry not written is not read
-                            // back and frees a lane of a segment of the next level (C4 253 -> 238 us; profiles/r04_push_recheck_ab.txt); 0 = A/B builds
-#endif
-#ifndef ACL_LOCAL_REQ
-#define ACL_LOCAL_REQ 1  // the direct task lists hold the request's index INSIDE the unit: the answer-byte accesses and the entry's y word lose their subtractions (A/B builds: 0)
-#endif
-#ifndef ACL_DIRECT_TASKS
-#define ACL_DIRECT_TASKS 1  // the deep levels' segments build their task list with the prefix sums taken in registers (process_segment); 0 = through flush_tasks (A/B builds)
-#endif
 #ifndef ACL_SIMPLE_WIDTH
 #define ACL_SIMPLE_WIDTH 3  // children per lane and step.  Round 5: with ONE bucket per child three of them cost the registers two used to, and the wide walk moved to 12 waves per
                             // block = 6 per SIMD = room for 72 VGPRs without a spill (rounds 2-4: 2 at 64 VGPRs and 8 waves per SIMD); profiles/r05_ab_block_shape.txt
@@ -463,8 +431,9 @@ constexpr int kEdgesAhead = ACL_EDGES_AHEAD;    // children per lane whose edges
 //     below its lane (two v_mbcnt) -- the 6-step binary search over the LDS prefix array cost ~30 VALU + 6 LDS reads per child;
 //   - one output reservation per step for the W x 64 children, not one per 64.
 // The steps of the simple expansion: the wave's task list holds T tasks whose children are `total` work items, t.a[j].x = first edge minus first work
-// item, t.heads = one bit per task at its first work item (set by the caller's prologue).  UM: every child carries the same meta `umeta` and the
-// entries are 8-byte ones (no per-task meta / subject id reads at the push).
+// item, t.heads = one bit per task at its first work item (set by the caller's prologue).  UM: every child carries the same meta `umeta`, the
+// entries are 8-byte ones (no per-task meta / subject id reads at the push) and t.a[j].w is the request's index INSIDE the unit (the answer-byte
+// accesses and the entry's y word without their subtractions).
 template <bool LOCAL, bool E8, bool UM>
 __device__ __forceinline__ void simple_steps(TaskLds &t, uint32_t total, WaveOut &wo, uint32_t lane, const uint32_t *__restrict__ edges, const uint4 *__restrict__ buckets,
                                              uint8_t *has, uint8_t *err, uint32_t umeta) {
@@ -551,22 +520,21 @@ __device__ __forceinline__ void simple_steps(TaskLds &t, uint32_t total, WaveOut
                 if (__ballot(anyhit)) {
 #pragma unroll
                     for (int k = 0; k < W; k++)
-                        if (hit[k]) ans_set<E8 && ACL_ANS_LDS>(has, rq[k], (UM && ACL_LOCAL_REQ) ? 0u : wo.first, 1);
+                        if (hit[k]) ans_set<E8>(has, rq[k], UM ? 0u : wo.first, 1);
                 }
             }
-#if ACL_PUSH_RECHECK
-            if (E8 && ACL_ANS_LDS) {
+            if (E8) {
                 // a request answered by THIS step's hits (or by another wave a moment ago) needs none of its other children any more: looked at
                 // once more before they are written -- an entry not written is not read back, and frees a lane of a segment of the next level
+                // (C4 253 -> 238 us; profiles/r04_push_recheck_ab.txt)
                 wave_lds_fence();
                 uint32_t hv[W];  // (the W answer bytes travel together: one LDS round trip, not W dependent ones)
 #pragma unroll
-                for (int k = 0; k < W; k++) hv[k] = ans_get<true>(has, rq[k], (UM && ACL_LOCAL_REQ) ? 0u : wo.first);
+                for (int k = 0; k < W; k++) hv[k] = ans_get<true>(has, rq[k], UM ? 0u : wo.first);
                 issue_fence();
 #pragma unroll
                 for (int k = 0; k < W; k++) push[k] = push[k] & (hv[k] == 0u);
             }
-#endif
 #pragma unroll
             for (int k = 0; k < W; k++) {
                 pb[k] = __ballot(push[k]);
@@ -579,7 +547,7 @@ __device__ __forceinline__ void simple_steps(TaskLds &t, uint32_t total, WaveOut
 #pragma unroll
                     for (int k = 0; k < W; k++)
                         if (push[k]) {
-                            if (UM && ACL_LOCAL_REQ)  // (the task holds the request's index inside the unit: the entry's y word without the subtraction)
+                            if (UM)  // (the task holds the request's index inside the unit: the entry's y word without the subtraction)
                                 gst(reinterpret_cast<uint2 *>(wo.buf), base + pre[k] + lanes_below(pb[k]), make_uint2((edge[k0 + k] & kIdMask) | 0x80000000u, (umeta & 0x7FFFFu) | (rq[k] << 19)));
                             else
                                 put_entry<E8>(wo, base + pre[k] + lanes_below(pb[k]), edge[k0 + k] & kIdMask, rq[k], (UM ? umeta : t.meta[tj[k0 + k]]) | kProbedBit, UM ? 0u : t.sid[tj[k0 + k]]);
@@ -715,17 +683,15 @@ __device__ __forceinline__ void flush_probes(TaskLds &t, uint32_t T, WaveOut &wo
             hit = hit && valid;
             push = push && valid;
             if (hit) {
-                ans_set<E8 && ACL_ANS_LDS>(has, req, wo.first, 1);
+                ans_set<E8>(has, req, wo.first, 1);
                 push = false;
             } else if (valid && level + cp.max_dlevel > kMaxLevels) {
-                ans_set<E8 && ACL_ANS_LDS>(err, req, wo.first, ITEM_ERR_DEPTH);
+                ans_set<E8>(err, req, wo.first, ITEM_ERR_DEPTH);
             }
-#if ACL_PUSH_RECHECK
-            if (E8 && ACL_ANS_LDS) {  // (as in flush_simple: a request answered meanwhile needs none of its other children)
+            if (E8) {  // (as in flush_simple: a request answered meanwhile needs none of its other children)
                 wave_lds_fence();
                 push = push && ans_get<true>(has, req, wo.first) == 0u;
             }
-#endif
             const uint64_t b = __ballot(push);
             if (b) {
                 const uint32_t base = reserve<LOCAL>(wo, (uint32_t)__popcll(b), lane);
@@ -768,7 +734,7 @@ __device__ __forceinline__ void flush_tasks(TaskLds &t, uint32_t T, WaveOut &wo,
                                             const FwdOp *ops, const uint32_t *__restrict__ edges, uint8_t *has, uint8_t *err, const DevShard &sh,
                                             bool same = false /* the caller made every task from ONE op: child slot, key and flags agree */,
                                             const CombineOut &co = CombineOut() /* CMB: where the children of an intersection arrow get their cells and member nodes */) {
-    constexpr bool E8 = ACL_ENTRY8 && INLINE && LOCAL && !CMB;  // (8-byte entries: the single-launch walk's monotone instantiations)
+    constexpr bool E8 = INLINE && LOCAL && !CMB;  // (8-byte entries: the single-launch walk's monotone instantiations)
     uint32_t only = ~0u;  // rounds of 64 tasks left for the generic loop
     wave_lds_fence();
     if (INLINE) {  // all tasks lead to the same "simple" child state?  (one hashed probe + authoritative leaf flags, plain subject)
@@ -883,38 +849,18 @@ __device__ __forceinline__ void flush_tasks(TaskLds &t, uint32_t T, WaveOut &wo,
                     push = eval_child(g, progs, ops, meta_slot(e.z), meta_level(e.z), meta_key(e.z), child, e.w, (c & kLeafAuthBit) != 0,
                                       (edge & kLeafBit) != 0, hit, derr);
                     if (hit) {
-                        ans_set<E8 && ACL_ANS_LDS>(has, e.y, wo.first, 1);
+                        ans_set<E8>(has, e.y, wo.first, 1);
                         push = false;
                     } else if (derr) {
-                        ans_set<E8 && ACL_ANS_LDS>(err, e.y, wo.first, ITEM_ERR_DEPTH);
+                        ans_set<E8>(err, e.y, wo.first, ITEM_ERR_DEPTH);
                     }
                     e.z |= kProbedBit;
-                    if (ACL_PERTURB == 3) {
-                        const FwdOp pop = ops[progs[meta_slot(e.z)].first];
-                        if (pop.flags & OP_PROBE_HASH) { const bool x = subject_row_contains(g, pop, child ^ 1u, e.w); ACL_KEEP((uint32_t)x); }
-                    }
-                    if (ACL_PERTURB == 5 && !(c & kSelfBit)) { const uint32_t x = edges[s + ((w - t.scan[j]) ^ 1u)]; ACL_KEEP(x); }
-                    if (ACL_PERTURB == 6) {
-                        uint32_t x = child;
-#pragma unroll
-                        for (int q = 0; q < 20; q++) x = x * 0x9E3779B1u + (x >> 7);
-                        ACL_KEEP(x);
-                    }
-                    if (ACL_PERTURB == 7) { const uint4 x = reinterpret_cast<const uint4 *>(g.buckets)[(child * 0x9E3779B1u) >> 12]; ACL_KEEP(x.x); }
-                    if (ACL_PERTURB == 8) {
-                        uint32_t x = 0;
-#pragma unroll
-                        for (int q = 0; q < 6; q++) x += t.meta[(gq + j + q * 7 + x) & (kTaskCap - 1)];
-                        ACL_KEEP(x);
-                    }
                 }
             }
-#if ACL_PUSH_RECHECK
-            if (E8 && ACL_ANS_LDS && INLINE) {  // (as in flush_simple: a request answered meanwhile needs none of its other children)
+            if (E8 && INLINE) {  // (as in flush_simple: a request answered meanwhile needs none of its other children)
                 wave_lds_fence();
                 push = push && ans_get<true>(has, e.y, wo.first) == 0u;
             }
-#endif
             const uint64_t b = __ballot(push);
             if (b) {
                 const uint32_t base = reserve<LOCAL>(wo, (uint32_t)__popcll(b), lane);
@@ -975,7 +921,7 @@ template <bool SHARDED, bool LOCAL, bool CMB, typename Next, bool SEEDS = false 
 __device__ __forceinline__ void process_segment(const uint4 &e, bool valid, Next &next, TaskLds &t, WaveOut &wo, uint32_t lane, const DevGraph &g,
                                                 const SlotProg *progs, const FwdOp *ops, uint8_t *has, uint8_t *err, const DevShard &sh,
                                                 const CombineOut &co = CombineOut()) {
-    constexpr bool E8 = ACL_ENTRY8 && LOCAL && !CMB;  // 8-byte entries + answers in LDS (put_entry, ans_get)
+    constexpr bool E8 = LOCAL && !CMB;  // 8-byte entries + answers in LDS (put_entry, ans_get)
     const uint32_t id = e.x, req = e.y, meta = e.z;
     // ---- fast path: every entry of the segment is a "simple parent" -- probes already done by its own parent (kProbedBit),
     // plain subject, and a program whose only remaining op enumerates one sorted row.  No interpreter: the has[] read, the
@@ -1018,7 +964,6 @@ __device__ __forceinline__ void process_segment(const uint4 &e, bool valid, Next
         const uint64_t vbB = haveB ? __ballot(validB) : 0ull;
         const bool oneslot = !__ballot(valid && meta != m0) && !(vbB && __ballot(validB && eB.z != m0));  // (same slot, level, key: the deep levels)
         if (oneslot) {
-#if ACL_DIRECT_TASKS
             // ---- the deep levels' shape, without the task list's round trips (round 5): ONE slot, level and subject key for both segments, children
             // that are "one hashed probe + authoritative leaf flags" (what flush_simple takes).  Decided and run HERE, while the program's fields are
             // still scalars.  The lane that creates a task already holds its degree, so the prefix sums run over the creating lanes' registers
@@ -1029,7 +974,8 @@ __device__ __forceinline__ void process_segment(const uint4 &e, bool valid, Next
             LaneOp LD{};  // (a copy of its own: nothing of it is live behind this block, so the general path's LA / LB are not carried -- spilled -- across it)
             if (E8 && !(g.walk_flags & kWalkNoDirect) && lane_op(m0, LD)) {
                 // (the program's fields come out of the LDS copy in VGPRs, uniform or not: pinned into SGPRs here -- a dozen VGPRs held across the
-                //  gathers otherwise, and the walk runs at exactly 64)
+                //  gathers otherwise, and the walk has none to spare: 6 waves per SIMD allow 80, it took 72 when round 5 chose that shape
+                //  (profiles/r05_ab_block_shape.txt) and takes nearly all of them now (tools/resusage.py))
                 const uint32_t lv = meta_level(m0), Lv = lv + uniform(LD.dlevel);
                 const uint32_t d_cnrows = uniform(LD.cnrows), d_cbase = uniform(LD.cbase), d_base = uniform(LD.base), d_nrows = uniform(LD.nrows), d_Kk = uniform(LD.Kk), d_key = uniform(LD.key);
                 if (d_cnrows != 0u && uniform(LD.ckey) == meta_key(m0) && (uniform(LD.flags) & OP_LEAFBIT) != 0u && Lv + 1u <= kMaxLevels && Lv + 1u + uniform(LD.cdl) <= kMaxLevels &&
@@ -1055,7 +1001,7 @@ __device__ __forceinline__ void process_segment(const uint4 &e, bool valid, Next
                     const uint32_t inclB = wave_incl_scan(degB, lane) + totA, total = wave_last(inclB);
                     if (total > 64u * kHeadWords || __ballot(degA > kMaxRow || degB > kMaxRow)) {
                         // more children than the head-bit window maps (an average fan-out beyond 16), or a row beyond the enumeration limit: this form has
-                        // no second round (one would have to keep the pair's registers across the steps -- the walk runs at exactly 64 VGPRs).  The batch is
+                        // no second round (one would have to keep the pair's registers across the steps, and the walk's VGPR budget is used up -- see above).  The batch is
                         // redone on the level loop and the host switches the form off for this snapshot (kOverflowDirect; a row beyond kMaxRow fails
                         // the call as it does on every path).
                         if (lane == 0) *wo.cold->overflow = __ballot(degA > kMaxRow || degB > kMaxRow) ? 2u : kOverflowDirect;
@@ -1067,12 +1013,12 @@ __device__ __forceinline__ void process_segment(const uint4 &e, bool valid, Next
                         const uint64_t bA = __ballot(degA != 0u), bB = __ballot(degB != 0u);
                         if (degA) {
                             const uint32_t ex = inclA - degA;
-                            t.a[lanes_below(bA)] = make_uint4(mdA.x - ex, sdA.x, sdA.y, ACL_LOCAL_REQ ? req - wo.first : req);
+                            t.a[lanes_below(bA)] = make_uint4(mdA.x - ex, sdA.x, sdA.y, req - wo.first);
                             atomicOr(reinterpret_cast<unsigned long long *>(&t.heads[ex >> 6]), 1ull << (ex & 63u));
                         }
                         if (degB) {
                             const uint32_t ex = inclB - degB;
-                            t.a[(uint32_t)__popcll(bA) + lanes_below(bB)] = make_uint4(mdB.x - ex, sdB.x, sdB.y, ACL_LOCAL_REQ ? eB.y - wo.first : eB.y);
+                            t.a[(uint32_t)__popcll(bA) + lanes_below(bB)] = make_uint4(mdB.x - ex, sdB.x, sdB.y, eB.y - wo.first);
                             atomicOr(reinterpret_cast<unsigned long long *>(&t.heads[ex >> 6]), 1ull << (ex & 63u));
                         }
                         wave_lds_fence();
@@ -1085,7 +1031,6 @@ __device__ __forceinline__ void process_segment(const uint4 &e, bool valid, Next
                     }
                 }
             }
-#endif
             simple = lane_op(m0, LA);  // wave-uniform argument
             LB = LA;
         } else {
@@ -1113,7 +1058,7 @@ __device__ __forceinline__ void process_segment(const uint4 &e, bool valid, Next
                     else if (md.y - md.x > kMaxRow) *wo.cold->overflow = 2u;
                     else want = true;
                 }
-                if (derr) ans_set<E8 && ACL_ANS_LDS>(err, se.y, wo.first, ITEM_ERR_DEPTH);
+                if (derr) ans_set<E8>(err, se.y, wo.first, ITEM_ERR_DEPTH);
                 const uint64_t b = __ballot(want);
                 if (want) {
                     const uint32_t q = Tb + lanes_below(b);
@@ -1125,7 +1070,7 @@ __device__ __forceinline__ void process_segment(const uint4 &e, bool valid, Next
                 return (uint32_t)__popcll(b);
             };
             // all six gathers in flight together
-            const uint32_t hvA = ans_get<E8 && ACL_ANS_LDS>(has, valid ? req : ((E8 && ACL_ANS_LDS) ? wo.first : 0u), wo.first);
+            const uint32_t hvA = ans_get<E8>(has, valid ? req : (E8 ? wo.first : 0u), wo.first);
             const bool inA = valid && id < LA.nrows;
             const uint2 mdA = row_desc(id, inA, LA);
             const uint2 sdA = subj_desc(e, valid, LA);
@@ -1133,7 +1078,7 @@ __device__ __forceinline__ void process_segment(const uint4 &e, bool valid, Next
             uint2 mdB = make_uint2(0, 0), sdB = make_uint2(0, 1);
             const bool inB = validB && eB.x < LB.nrows;
             if (pairB) {
-                hvB = ans_get<E8 && ACL_ANS_LDS>(has, validB ? eB.y : ((E8 && ACL_ANS_LDS) ? wo.first : 0u), wo.first);
+                hvB = ans_get<E8>(has, validB ? eB.y : (E8 ? wo.first : 0u), wo.first);
                 mdB = row_desc(eB.x, inB, LB);
                 sdB = subj_desc(eB, validB, LB);
             }
@@ -1173,7 +1118,7 @@ __device__ __forceinline__ void process_segment(const uint4 &e, bool valid, Next
         asm volatile("" : "+v"(ee.x), "+v"(ee.y), "+v"(ee.z), "+v"(ee.w));
         const uint32_t id = ee.x, req = ee.y, meta = ee.z, sid = ee.w;
         bool active = valid && meta != kDeadMeta;
-        if (active && (hit || ans_get<E8 && ACL_ANS_LDS>(has, req, wo.first))) active = false;  // request already answered HAS: drop its pending work
+        if (active && (hit || ans_get<E8>(has, req, wo.first))) active = false;  // request already answered HAS: drop its pending work
         const uint32_t slot = meta_slot(meta), level = meta_level(meta), key = meta_key(meta);
         const bool probed = meta & kProbedBit;  // the parent already ran this state's probes
         SlotProg p{};
@@ -1286,8 +1231,8 @@ __device__ __forceinline__ void process_segment(const uint4 &e, bool valid, Next
         }
         jstart = jj;
         if (active) {
-            if (hit) ans_set<E8 && ACL_ANS_LDS>(has, req, wo.first, 1);
-            else if (depth_err) ans_set<E8 && ACL_ANS_LDS>(err, req, wo.first, ITEM_ERR_DEPTH);
+            if (hit) ans_set<E8>(has, req, wo.first, 1);
+            else if (depth_err) ans_set<E8>(err, req, wo.first, ITEM_ERR_DEPTH);
         }
         const bool more = jstart < maxops;
         // ---- expand the recorded segments (the interpreter's state is dead from here to the loop's top)
@@ -1442,7 +1387,7 @@ struct LocalWalk {
     bool second;          // the pair's second segment is still to be taken
     const uint2 *sreq;    // E8: the unit's per-request constants {subject id, subject key} (LDS)
     uint32_t first;       // E8: the unit's first request
-    uint2 rawB = make_uint2(0u, 0u);  // ACL_PREFETCH_ENTRIES: the pair's second segment, fetched (undecoded) when the pair was claimed
+    uint2 rawB = make_uint2(0u, 0u);  // the pair's second segment, fetched (undecoded) when the pair was claimed (k_check_local's claim loop)
     bool have_rawB = false;
     __device__ __forceinline__ uint2 raw(uint32_t i) const { return gld(reinterpret_cast<const uint2 *>(in), i); }
     __device__ __forceinline__ uint4 at(uint32_t i) const {
@@ -1490,15 +1435,6 @@ struct InlineItems {  // up to four 16-byte items passed by value (kernel argume
                            // 14 waves: 275 us, 10 waves x 3 blocks: 226 us, four children per step: 227 us (profiles/r05_ab_block_shape.txt)
 #endif
 constexpr int kLocalNarrow = 4, kLocalWide = ACL_LOCAL_WIDE;
-#ifndef ACL_SPLIT_UNITS
-#define ACL_SPLIT_UNITS 0  // 1 (A/B builds; measured C4 228.4 -> 226.0 us but C5R 297 -> 304 us, level barriers 19 -> 15 % of the wave-time: profiles/r05_ab_split_units.txt): the wide monotone walk cuts a unit into two HALVES whose levels turn over independently (k_check_local); 0 = one barrier per level (A/B builds)
-#endif
-#ifndef ACL_PREFETCH_ENTRIES
-#define ACL_PREFETCH_ENTRIES 1  // the single-launch walk fetches the NEXT pair's entries before it expands the current pair (k_check_local's claim loop); 0 = A/B builds
-#endif
-#ifndef ACL_TAIL_SINGLES
-#define ACL_TAIL_SINGLES 0  // N > 0 (A/B builds): the last 2 N x WAVES segments of a level are claimed one by one instead of in pairs (see the claim loop)
-#endif
 template <bool LDSPROG, int WAVES, bool CMB = false>
 __global__ __launch_bounds__(WAVES * 64, ACL_LOCAL_WAVES_PER_SIMD) void k_check_local(DevGraph g, const uint4 *__restrict__ items, uint32_t n, uint32_t rpw,
                                                                                   uint32_t nunits, uint32_t nstatic, uint32_t rdyn, uint32_t *next_unit, uint4 *buf0, uint4 *buf1,
@@ -1509,19 +1445,19 @@ __global__ __launch_bounds__(WAVES * 64, ACL_LOCAL_WAVES_PER_SIMD) void k_check_
     __shared__ TaskLds lds[WAVES];
     __shared__ WaveOutCold s_cold[WAVES];
     // output cursor / segment-claim counter of level L live in slot L % 3: written during L, read at the start of L + 1, cleared at the
-    // start of L + 2 (every wave has read them by then) and reused at L + 3 -- ONE block barrier per level instead of three
-    // NH = 2 (chip-filling monotone batches): the unit's requests are cut into two halves with cursor sets, frontier regions and arrival counters of
-    // their own, walked by the same waves in alternation -- see the phase loop below
-    constexpr uint32_t NH = (ACL_SPLIT_UNITS && !CMB && WAVES >= 8) ? 2u : 1u;
-    __shared__ uint32_t s_cursors[6 * NH + NH], s_stop, s_unit;  // (one array: the per-unit reset is ONE store through one address -- two arrays cost a spilled VGPR)
-    uint32_t *const s_fill = s_cursors, *const s_next = s_cursors + 3;  // half h: s_fill + 6 h, s_next + 6 h; s_done = s_cursors + 6 NH
-    uint32_t *const s_done = s_cursors + 6 * NH;
+    // start of L + 2 (every wave has read them by then) and reused at L + 3 -- ONE block barrier per level instead of three.
+    // (Two half-units whose levels turn over independently, without the barrier, won on C4 and lost on the 100 M-relationship replica:
+    //  profiles/r05_ab_split_units.txt.)
+    // (s_cursors: one array -- the per-unit reset is ONE store through one address, two arrays cost a spilled VGPR.  Six words are used; the seventh
+    //  is spare, and dropping it moves the LDS layout and with it the register allocation: to be done with a measurement, not in passing.)
+    constexpr uint32_t kCursorWords = 7;
+    __shared__ uint32_t s_cursors[kCursorWords], s_stop, s_unit;
+    uint32_t *const s_fill = s_cursors, *const s_next = s_cursors + 3;
     __shared__ uint32_t s_ccount[2];  // CMB: {leaf cells, nodes} of the unit being walked
-    constexpr bool E8 = ACL_ENTRY8 && !CMB;  // 8-byte frontier entries (put_entry)
+    constexpr bool E8 = !CMB;  // 8-byte frontier entries (put_entry)
     __shared__ uint2 s_req[E8 ? WAVES * 64 : 1];  // E8: {subject id, subject key} of the unit's requests
-    constexpr bool AL = E8 && ACL_ANS_LDS;
-    __shared__ uint8_t s_has[AL ? WAVES * 64 : 1], s_err[AL ? WAVES * 64 : 1];  // the unit's answer bytes (ans_get / ans_set)
-    if (AL) {
+    __shared__ uint8_t s_has[E8 ? WAVES * 64 : 1], s_err[E8 ? WAVES * 64 : 1];  // E8: the unit's answer bytes (ans_get / ans_set)
+    if (E8) {
         has = s_has;
         err = s_err;
     }
@@ -1567,7 +1503,7 @@ __global__ __launch_bounds__(WAVES * 64, ACL_LOCAL_WAVES_PER_SIMD) void k_check_
             first = min(n, u * rpw + ((skew * u * (nunits - u)) >> 8));
             mine = min(n, (u + 1u) * rpw + ((skew * (u + 1u) * (nunits - u - 1u)) >> 8)) - first;
         }
-        if (threadIdx.x < 6 * NH + NH) s_cursors[threadIdx.x] = 0;
+        if (threadIdx.x < kCursorWords) s_cursors[threadIdx.x] = 0;
         if (CMB && threadIdx.x < 2) s_ccount[threadIdx.x] = 0;
         __syncthreads();
         // ---- seeds (k_seed's validation), in registers: wave w holds requests [64 w, 64 w + 64) of the unit
@@ -1588,8 +1524,8 @@ __global__ __launch_bounds__(WAVES * 64, ACL_LOCAL_WAVES_PER_SIMD) void k_check_
             const uint32_t rt = tok ? rtype : 0u, st = tok ? stype : 0u;
             const uint32_t rmem = gld(g.type_nmembers, rt), smem = gld(g.type_nmembers, st), rbase = gld(g.type_slot_base, rt), sbase = gld(g.type_slot_base, st);
             const bool ok = tok && perm < rmem && (srel == 0xFFFFu || srel < smem);
-            ans_set<E8 && ACL_ANS_LDS>(has, req, first, 0);
-            ans_set<E8 && ACL_ANS_LDS>(err, req, first, (uint8_t)(ok ? ITEM_ERR_NONE : ITEM_ERR_INVALID));
+            ans_set<E8>(has, req, first, 0);
+            ans_set<E8>(err, req, first, (uint8_t)(ok ? ITEM_ERR_NONE : ITEM_ERR_INVALID));
             const uint32_t skey = srel == 0xFFFFu ? g.nslots + stype : sbase + srel;
             const uint32_t meta = ok ? make_meta(rbase + perm, 1u, skey) : kDeadMeta;
             e = make_uint4(it.y, req, meta, it.w);
@@ -1598,90 +1534,6 @@ __global__ __launch_bounds__(WAVES * 64, ACL_LOCAL_WAVES_PER_SIMD) void k_check_
         wo.first = first;
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         uint32_t level_reached = 1;
-        if (NH == 2) {
-            // ---- TWO HALF-UNITS, no block barrier between levels (round 5; VERDICT r4 next #1c).  With one cursor set a level ends at a block
-            // barrier: a wave that finds the claim counter dry waits there for the waves still expanding their last pair -- a fifth of the walk's
-            // wave-time (profiles/r04_phases_final.txt), because a unit's level is only a few dozen segment pairs for a block's waves.  Here the unit's
-            // requests are cut in two (at a multiple of 64: a wave's seeds belong to one half), each half with its own cursors, frontier region
-            // (half of the block's) and an ARRIVAL COUNTER; every wave walks the phases  (half 0, level 2), (half 1, level 2), (half 0, level 3), ...
-            // in that order and, done with its share of a phase, goes straight on to the next one -- which only needs the OTHER half's previous
-            // level complete, long finished as a rule.  A phase is complete when all WAVES waves have arrived at its counter (monotonic: phase
-            // (h, L) needs s_done[h] >= WAVES (L - 2)); the counter is raised behind a workgroup release fence and read before an acquire fence,
-            // the pairing __syncthreads() provided.  Cursor slot (L + 1) % 3 of a half is cleared by every wave that enters (h, L): nobody uses
-            // it between the end of (h, L - 1) -- all waves have arrived there -- and the start of (h, L + 1).
-            const uint32_t split = min(mine, ((mine / 2u + 63u) >> 6) << 6);  // requests [0, split) of the unit are half 0
-            const uint32_t hcap = wo.cold->cap >> 1;                          // entries of a half's region (the same in both buffers)
-            const uint32_t myh = (wib * 64u >= split) ? 1u : 0u;              // the half this wave's seeds belong to
-            const size_t hoff = (size_t)(E8 ? hcap / 2u : hcap);              // ... in uint4 units
-            if (lane == 0) wo.cold->cap = hcap;
-            wo.lcap = hcap;
-            wo.buf = bufs[0] + myh * hoff;
-            wo.cur = 0;
-            wo.lfill = &s_fill[6 * myh + 1];  // level 1
-            ACL_MARK(wo, PH_SEED);
-            {
-                NoNext nn;
-                co.iter = 1u;
-                process_segment<false, true, CMB, NoNext, true>(e, valid, nn, t, wo, lane, g, progs, ops, has, err, nosh, co);
-            }
-            if (wo.cur == kNoSpace && lane == 0) s_stop = 1;
-            __syncthreads();  // (the seeds' children are written; from here on the halves' counters order everything)
-            uint32_t lvl[2] = {2u, 2u}, par[2] = {0u, 0u};
-            bool alive[2] = {true, true};
-            for (uint32_t ph = 0; alive[0] || alive[1]; ph++) {
-                const uint32_t h = ph & 1u;
-                if (!alive[h]) continue;
-                const uint32_t level = lvl[h];
-                if (level > kMaxLevels + 1) {
-                    alive[h] = false;
-                    continue;
-                }
-                // ---- every wave has left (h, level - 1): its entries are written, its cursors final
-                const uint32_t target = WAVES * (level - 2u);
-                while (__hip_atomic_load(&s_done[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < target && !__hip_atomic_load(&s_stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP))
-                    __builtin_amdgcn_s_sleep(2);
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                ACL_MARK(wo, PH_BARRIER);
-                if (__hip_atomic_load(&s_stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;  // overflow somewhere: the host redoes the batch
-                uint32_t *const fill = s_fill + 6 * h, *const nexts = s_next + 6 * h;
-                const uint32_t cnt = uniform(fill[(level - 1) % 3]);
-                if (lane == 0) {
-                    fill[(level + 1) % 3] = 0;
-                    nexts[(level + 1) % 3] = 0;
-                }
-                if (!cnt) {
-                    alive[h] = false;
-                    continue;
-                }
-                level_reached = max(level_reached, level);
-                wo.lfill = &fill[level % 3];
-                uint32_t *const next_seg = &nexts[level % 3];
-                LocalWalk<E8> lw{bufs[par[h]] + h * hoff, cnt, 0u, lane, false, s_req, first};
-                par[h] ^= 1u;
-                wo.buf = bufs[par[h]] + h * hoff;
-                co.iter = level;
-                const uint32_t nseg = (cnt + 63u) >> 6;
-                for (;;) {
-                    uint32_t sg = 0;
-                    if (lane == 0) sg = atomicAdd(next_seg, 2u);
-                    sg = uniform(sg);
-                    if (sg >= nseg) break;
-                    for (lw.s = sg, lw.second = true; lw.s < sg + 2 && lw.s * 64 < cnt; lw.s++) {
-                        if (lw.s > sg && !lw.second) break;  // the pair's second segment went with the first
-                        const bool v = lw.s * 64 + lane < cnt;
-                        const uint4 en = lw.at(v ? lw.s * 64 + lane : lw.s * 64);  // unconditional; process_segment masks by `v`
-                        if (lw.s > sg) lw.second = false;
-                        process_segment<false, true, CMB>(en, v, lw, t, wo, lane, g, progs, ops, has, err, nosh, co);
-                    }
-                }
-                if (wo.cur == kNoSpace && lane == 0) s_stop = 1;
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");  // this wave's entries and answer bytes before its arrival
-                if (lane == 0) __hip_atomic_fetch_add(&s_done[h], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                lvl[h] = level + 1u;
-            }
-            if (lane == 0) wo.cold->cap = hcap << 1;  // (the next unit sets its own geometry from the full region)
-            wo.lcap = hcap << 1;
-        } else {
         wo.buf = bufs[0];
         wo.cur = 0;
         wo.lfill = &s_fill[1];  // level 1
@@ -1711,13 +1563,10 @@ __global__ __launch_bounds__(WAVES * 64, ACL_LOCAL_WAVES_PER_SIMD) void k_check_
             parity ^= 1u;
             wo.buf = bufs[parity];
             co.iter = level;
-            // Segments are claimed in PAIRS: one prologue and one set of trips for 128 entries.  (ACL_TAIL_SINGLES = N > 0, A/B builds: the level's last
-            // 2 N x WAVES segments one by one, so that what a wave still holds when the counter runs dry is half as long -- the level barriers are a
-            // fifth of the walk's wave-time.  Measured slower, 227.5 -> 231 -> 238 us for N = 0, 1, 2 on C4: profiles/r05_ab_seeded_rows.txt.)
+            // Segments are claimed in PAIRS: one prologue and one set of trips for 128 entries.  (Claiming a level's last segments one by one was tried
+            // and was slower: profiles/r05_ab_seeded_rows.txt.)
             const uint32_t nseg = (cnt + 63u) >> 6;
-            const uint32_t npair = (ACL_TAIL_SINGLES && nseg > 2u * WAVES * ACL_TAIL_SINGLES) ? (nseg - 2u * WAVES * ACL_TAIL_SINGLES + 1u) >> 1 : (ACL_TAIL_SINGLES ? 0u : nseg);
-#if ACL_PREFETCH_ENTRIES
-            if (E8 && !ACL_TAIL_SINGLES) {
+            if (E8) {
                 // ---- the NEXT pair's entries travel while the current pair is expanded (round 6).  A pair's walk is a chain of dependent trips -- its entries,
                 // the parents' descriptors, then edges and buckets per step -- and the first of them, the entries (an L2 hit: this block wrote them a level
                 // ago), was a tenth of the walk's wave-time (profiles/r04_phases_final.txt "entries wait").  A wave now claims pair k + 1 and issues the
@@ -1768,24 +1617,23 @@ __global__ __launch_bounds__(WAVES * 64, ACL_LOCAL_WAVES_PER_SIMD) void k_check_
                     rA = nA;
                     rB = nB;
                 }
-            } else
-#endif
-            for (;;) {
-                uint32_t sg = 0;
-                if (lane == 0) sg = atomicAdd(next_seg, 1u);
-                sg = uniform(sg);
-                const uint32_t take = sg < npair ? 2u : 1u;
-                sg = sg < npair ? 2u * sg : npair + sg;  // (= 2 npair + (claim - npair))
-                if (sg >= nseg) break;
-                for (lw.s = sg, lw.second = take > 1u; lw.s < sg + take && lw.s * 64 < cnt; lw.s++) {
-                    if (lw.s > sg && !lw.second) break;  // the pair's second segment went with the first
-                    const bool v = lw.s * 64 + lane < cnt;
-                    const uint4 en = lw.at(v ? lw.s * 64 + lane : lw.s * 64);  // unconditional; process_segment masks by `v`
-                    if (lw.s > sg) lw.second = false;
-                    process_segment<false, true, CMB>(en, v, lw, t, wo, lane, g, progs, ops, has, err, nosh, co);
+            } else {  // (the combine instantiations' 16-byte entries: a pair is claimed and its entries loaded when the wave is free)
+                for (;;) {
+                    uint32_t sg = 0;
+                    if (lane == 0) sg = atomicAdd(next_seg, 1u);
+                    sg = uniform(sg);
+                    const uint32_t take = sg < nseg ? 2u : 1u;
+                    sg = sg < nseg ? 2u * sg : nseg + sg;  // (claim c is the pair of segments 2 c, 2 c + 1; a claim beyond the level's pairs ends the loop)
+                    if (sg >= nseg) break;
+                    for (lw.s = sg, lw.second = take > 1u; lw.s < sg + take && lw.s * 64 < cnt; lw.s++) {
+                        if (lw.s > sg && !lw.second) break;  // the pair's second segment went with the first
+                        const bool v = lw.s * 64 + lane < cnt;
+                        const uint4 en = lw.at(v ? lw.s * 64 + lane : lw.s * 64);  // unconditional; process_segment masks by `v`
+                        if (lw.s > sg) lw.second = false;
+                        process_segment<false, true, CMB>(en, v, lw, t, wo, lane, g, progs, ops, has, err, nosh, co);
+                    }
                 }
             }
-        }
         }
         // (statistics: dispatch levels the deepest request of the batch needed.  Test before the atomic: 2 048 blocks ending together on
         //  one address serialise at ~12 ns each -- C2's 18 us kernel took 38 us with an unconditional atomicMax.)
@@ -1811,8 +1659,8 @@ __global__ __launch_bounds__(WAVES * 64, ACL_LOCAL_WAVES_PER_SIMD) void k_check_
         // ---- answers (k_finalize): every wave's has[] / err[] stores are behind a block barrier
         __syncthreads();
         if (valid) {
-            const bool h = AL ? s_has[threadIdx.x] != 0 : __hip_atomic_load(has + req, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0;
-            const uint8_t er = h ? (uint8_t)ITEM_ERR_NONE : (AL ? s_err[threadIdx.x] : __hip_atomic_load(err + req, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+            const bool h = E8 ? s_has[threadIdx.x] != 0 : __hip_atomic_load(has + req, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0;
+            const uint8_t er = h ? (uint8_t)ITEM_ERR_NONE : (E8 ? s_err[threadIdx.x] : __hip_atomic_load(err + req, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
             perm_out[req] = h ? 2 : (er ? 0 : 1);
             if (err_out) err_out[req] = er == ITEM_ERR_DEPTH ? 100 : (er == ITEM_ERR_INVALID ? 9 : 0);
         }
@@ -2729,25 +2577,24 @@ extern "C" int acl_debug_phase_cycles(unsigned long long *out16) {  // variant b
 namespace acl {
 #endif
 static size_t prog_lds_bytes(const DevGraph &g) { return ((size_t)g.nslots + g.nops) * 32; }
-// A/B knob: ACL_PROG_LDS=0 runs the instantiations that read the program table from global memory (8 KiB less LDS per block)
-static bool prog_in_lds() {
-    static const bool on = [] {
-        const char *e = getenv("ACL_PROG_LDS");
-        return !(e && atoi(e) == 0);
-    }();
-    return on;
+// Turns a run-time flag into a compile-time one: f(std::true_type{}) or f(std::false_type{}).  The launchers below pick a kernel instantiation with it,
+// so that every kernel template has ONE launch site.
+template <typename F>
+static auto with_flag(bool flag, F &&f) {
+    if (flag) return f(std::true_type{});
+    return f(std::false_type{});
 }
 
 int expand_grid_blocks(int device) {
     hipDeviceProp_t prop;
     int cus = 256;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-    int per_cu = 8;  // 256-thread blocks, <= 64 VGPRs, ~20 KiB LDS
-    if (const char *e = getenv("ACL_BLOCKS_PER_CU")) per_cu = atoi(e) > 0 ? atoi(e) : per_cu;  // A/B knob (tools/ab.sh)
+    int per_cu = 8;  // 256-thread blocks, ~20 KiB LDS; the occupancy query lowers it to what k_expand's ~70 VGPRs allow (6 or 7)
     int occ = 0;
     // (the program table's LDS copy is dynamic; 2 KiB covers schemas of ~60 slots + ops -- a larger one only means some blocks of a launch queue)
-    const hipError_t oe = prog_in_lds() ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_expand<true, false>, kBlock, 2048)
-                                        : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_expand<false, false>, kBlock, 0);
+    const hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_expand<true, false>, kBlock, 2048);
+    (void)k_expand<false, false>;  // (no effect at run time: first named here, this instantiation stays second in the code object, whose device code can
+                                   //  then be compared line by line with an earlier build's -- the test that a host-side cleanup of this file left the kernels alone)
     if (oe == hipSuccess && occ > 0) per_cu = occ < per_cu ? occ : per_cu;
     return cus * per_cu;
 }
@@ -2758,46 +2605,28 @@ void launch_seed(hipStream_t s, const DevGraph &g, const DevFrontier &f, const u
 }
 void launch_expand(hipStream_t s, const DevGraph &g, const DevFrontier &f, uint32_t iter, uint8_t *has, uint8_t *err, const DevShard &sh) {
     const dim3 grid(f.nwaves / kWavesPerBlock);
-    const bool lds = g.nslots + g.nops <= kProgLdsEntries && prog_in_lds();
-    if (g.bexpr) {  // schemas with `&` / `-`
-        if (sh.world > 1) {  // (round 5: the sharded graph too -- cells in per-shard ranges of one global cell space, engine_shard_native.cpp)
-            if (lds) hipLaunchKernelGGL((k_expand<true, true, true>), grid, dim3(kBlock), prog_lds_bytes(g), s, g, f, iter, has, err, sh);
-            else hipLaunchKernelGGL((k_expand<false, true, true>), grid, dim3(kBlock), 0, s, g, f, iter, has, err, sh);
-            return;
-        }
-        if (lds) hipLaunchKernelGGL((k_expand<true, false, true>), grid, dim3(kBlock), prog_lds_bytes(g), s, g, f, iter, has, err, sh);
-        else hipLaunchKernelGGL((k_expand<false, false, true>), grid, dim3(kBlock), 0, s, g, f, iter, has, err, sh);
-        return;
-    }
-    if (sh.world > 1) {
-        if (lds) hipLaunchKernelGGL((k_expand<true, true>), grid, dim3(kBlock), prog_lds_bytes(g), s, g, f, iter, has, err, sh);
-        else hipLaunchKernelGGL((k_expand<false, true>), grid, dim3(kBlock), 0, s, g, f, iter, has, err, sh);
-    } else {
-        if (lds) hipLaunchKernelGGL((k_expand<true, false>), grid, dim3(kBlock), prog_lds_bytes(g), s, g, f, iter, has, err, sh);
-        else hipLaunchKernelGGL((k_expand<false, false>), grid, dim3(kBlock), 0, s, g, f, iter, has, err, sh);
-    }
+    // CMB: schemas with `&` / `-` (round 5: the sharded graph too -- cells in per-shard ranges of one global cell space, engine_shard_native.cpp);
+    // LDSPROG: the program table fits its LDS copy
+    with_flag(g.bexpr != nullptr, [&](auto cmb) {
+        with_flag(sh.world > 1, [&](auto sharded) {
+            with_flag(g.nslots + g.nops <= kProgLdsEntries, [&](auto lds) {
+                hipLaunchKernelGGL((k_expand<lds(), sharded(), cmb()>), grid, dim3(kBlock), lds() ? prog_lds_bytes(g) : 0, s, g,
+                                   f, iter, has, err, sh);
+            });
+        });
+    });
 }
 template <int WAVES>
 static void launch_check_local_w(hipStream_t s, const DevGraph &g, const uint4 *items, uint32_t n, uint32_t rpw, uint32_t nblocks, uint32_t nunits, uint32_t nstatic, uint32_t rdyn,
                                  uint32_t *next_unit, uint4 *buf0, uint4 *buf1, uint32_t cap, uint32_t *overflow, uint8_t *has, uint8_t *err, uint8_t *perm_out, int32_t *err_out,
                                  uint32_t *max_level, uint32_t skew, uint32_t *done_ctr, uint32_t *done_flag, uint32_t done_val, const InlineItems &inl) {
     const dim3 grid(nblocks);
-    const bool lds = g.nslots + g.nops <= kProgLdsEntries && prog_in_lds();
-    if (g.bexpr) {  // schemas with `&` / `-`: the combine instantiations
-        if (lds)
-            hipLaunchKernelGGL((k_check_local<true, WAVES, true>), grid, dim3(WAVES * 64), prog_lds_bytes(g), s, g, items, n, rpw, nunits, nstatic, rdyn, next_unit, buf0, buf1, cap, overflow,
-                               has, err, perm_out, err_out, max_level, skew, done_ctr, done_flag, done_val, inl);
-        else
-            hipLaunchKernelGGL((k_check_local<false, WAVES, true>), grid, dim3(WAVES * 64), 0, s, g, items, n, rpw, nunits, nstatic, rdyn, next_unit, buf0, buf1, cap, overflow, has, err,
-                               perm_out, err_out, max_level, skew, done_ctr, done_flag, done_val, inl);
-        return;
-    }
-    if (lds)
-        hipLaunchKernelGGL((k_check_local<true, WAVES>), grid, dim3(WAVES * 64), prog_lds_bytes(g), s, g, items, n, rpw, nunits, nstatic, rdyn, next_unit, buf0, buf1, cap, overflow, has, err,
-                           perm_out, err_out, max_level, skew, done_ctr, done_flag, done_val, inl);
-    else
-        hipLaunchKernelGGL((k_check_local<false, WAVES>), grid, dim3(WAVES * 64), 0, s, g, items, n, rpw, nunits, nstatic, rdyn, next_unit, buf0, buf1, cap, overflow, has, err, perm_out,
-                           err_out, max_level, skew, done_ctr, done_flag, done_val, inl);
+    with_flag(g.bexpr != nullptr, [&](auto cmb) {  // schemas with `&` / `-`: the combine instantiations
+        with_flag(g.nslots + g.nops <= kProgLdsEntries, [&](auto lds) {
+            hipLaunchKernelGGL((k_check_local<lds(), WAVES, cmb()>), grid, dim3(WAVES * 64), lds() ? prog_lds_bytes(g) : 0, s, g, items, n, rpw,
+                               nunits, nstatic, rdyn, next_unit, buf0, buf1, cap, overflow, has, err, perm_out, err_out, max_level, skew, done_ctr, done_flag, done_val, inl);
+        });
+    });
 }
 void launch_check_local(hipStream_t s, const DevGraph &g, const uint4 *items, uint32_t n, uint32_t rpw, uint32_t nblocks, uint32_t *next_unit, uint4 *buf0,
                         uint4 *buf1, uint32_t cap, uint32_t *overflow, uint8_t *has, uint8_t *err, uint8_t *perm_out, int32_t *err_out, uint32_t *max_level,
@@ -2827,7 +2656,7 @@ int local_grid_blocks(int device, size_t prog_bytes, bool wide) {
     hipDeviceProp_t prop;
     int cus = 256;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-    const bool lds = prog_in_lds() && prog_bytes <= (size_t)kProgLdsEntries * 32;
+    const bool lds = prog_bytes <= (size_t)kProgLdsEntries * 32;
     return cus * (wide ? local_occupancy<kLocalWide>(lds, prog_bytes) : local_occupancy<kLocalNarrow>(lds, prog_bytes));
 }
 uint32_t local_unit_max(bool wide) { return (uint32_t)(wide ? kLocalWide : kLocalNarrow) * 64u; }

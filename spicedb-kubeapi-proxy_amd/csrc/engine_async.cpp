@@ -4,7 +4,7 @@
 // goroutines blocking in acl_check_bulk_ids; submit / wait is the same thing for single-threaded hosts (bench.py --pipeline submit) and for
 // callers that want a window of batches in flight: a ticket is a whole blocking call on one of the pool's workers.  Since round 3 the
 // kernel reads the items from, and writes the answers to, pinned host memory itself, so such calls need no turn-taking and no copy engine;
-// round 4 made that true at every batch size (sub-passes, engine.cpp check_pass_local_host) and retired what this file used to hold for
+// round 4 made that true at every batch size (sub-passes, engine_pass.cpp check_pass_local_host) and retired what this file used to hold for
 // batches beyond one launch: look-ahead H2D staging, three "lanes" of contexts, kernels chained on the device through events and a
 // completer thread (~250 lines).
 #include "engine_internal.hpp"

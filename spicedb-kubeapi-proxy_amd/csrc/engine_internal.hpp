@@ -1,4 +1,5 @@
-// engine_internal.hpp -- shared by the translation units behind the C ABI (engine.cpp: core + Check/Filter,
+// engine_internal.hpp -- shared by the translation units behind the C ABI (engine.cpp: the ABI functions, open / close;
+// engine_snapshot.cpp, engine_pass.cpp, engine_intern.cpp, engine_lookup.cpp, engine_keep.cpp: the core, by concern;
 // engine_shard.cpp: acl_shard_*, engine_callers.cpp: keep mask / bitmap test / watch / micro-batcher,
 // engine_async.cpp: submit/wait + pinned host buffers).
 //
@@ -44,7 +45,7 @@ struct DevState;  // one replica of the HBM snapshot (below)
 
 namespace aclint {
 
-extern thread_local std::string g_last_error;  // engine.cpp
+extern thread_local std::string g_last_error;  // engine_pass.cpp
 extern thread_local int g_last_detail;          // what KIND of failure the last fail() was, for callers inside the library that react to one (0: nothing special)
 constexpr int kDetailBitmapTooSmall = 1;        // a lookup's caller-sized row no longer covers the type's ids: acl_lookup_resources_alloc sizes again and retries
 
@@ -222,7 +223,7 @@ struct PassCtx {
     int index = 0;           // among the contexts of ITS device
     DevState *dev = nullptr;  // the replica (device) this context's stream and buffers live on
     hipStream_t stream = nullptr;
-    hipStream_t aux[3] = {nullptr, nullptr, nullptr};  // further streams of a host batch cut into concurrent slices (engine.cpp check_pass_local_host), made on first use
+    hipStream_t aux[3] = {nullptr, nullptr, nullptr};  // further streams of a host batch cut into concurrent slices (engine_pass.cpp check_pass_local_host), made on first use
     // frontier
     DevArray<uint4> d_fbuf[2];
     DevArray<uint32_t> d_fcounts[2], d_status;  // status = nchunks[kLevelSlots] | any[kLevelSlots] | overflow | export counters
@@ -275,10 +276,10 @@ using namespace aclint;
 
 struct AsyncPool;
 namespace aclint {
-struct InternPool;  // engine.cpp
+struct InternPool;  // engine_strings.hpp
 }  // engine_async.cpp
 
-// Background snapshot compaction (engine.cpp).  Patching writes into the HBM snapshot leaves garbage behind (relocated
+// Background snapshot compaction (engine_snapshot.cpp).  Patching writes into the HBM snapshot leaves garbage behind (relocated
 // rows) and eats the tables' headroom; once either passes a threshold the next snapshot is built from a copy-on-write view
 // of the store on a worker thread and uploaded to fresh device arrays on the worker's own stream, while reads keep
 // patching and using the old one.  The next reader adopts it under the lock: catch-up patch from the view's revision,
@@ -368,13 +369,13 @@ struct acl_engine {
     void set_rev_uploaded(bool v) {
         for (auto &d : devs) d->rev_uploaded = v;
     }
-    std::atomic<uint64_t> keep_route_calls{0};  // PostFilter calls answered by ONE reverse walk + bit tests (engine.cpp keep_by_reverse_walk)
+    std::atomic<uint64_t> keep_route_calls{0};  // PostFilter calls answered by ONE reverse walk + bit tests (engine_keep.cpp keep_by_reverse_walk)
     // ... and what the last such call for a (type, permission, subject) found: 58 bits of the key's hash | 1 + the bit width of the allowed count (0: never seen).
     // A hint only -- it decides whether the host's pass resolves names while the device still walks -- and direct-mapped: a collision costs a wrong guess.
     std::atomic<uint64_t> keep_seen[256] = {};
     std::atomic<uint32_t> keep_route_skips{0};  // short lists for far-reaching subjects that went forward instead (one in sixteen still walks)
     // The pair form of that route on a RECURSIVE permission (Snapshot::slot_deep: the schema alone cannot rule a depth error out) needs to know that THE DATA rules it
-    // out: no object of the type whose Check runs into the dispatch-depth limit.  That is a property of the snapshot, not of the subject (engine.cpp
+    // out: no object of the type whose Check runs into the dispatch-depth limit.  That is a property of the snapshot, not of the subject (engine_keep.cpp
     // no_object_is_deep): one forward sweep over the type's objects for a subject nobody is, remembered per (type, permission, subject type) and snapshot epoch.
     SubjectRows subj;         // LookupSubjects' rows for the snapshot of subj.epoch (built lazily under state_mu exclusive)
     uint64_t snap_epoch = 0;  // counts the snapshot's changes (ensure_snapshot, under state_mu exclusive; read under state_mu shared)
@@ -407,7 +408,7 @@ struct acl_engine {
     uint32_t local_wide_min = 65536;  // batches from this size on run the wide (12-wave) instantiation (a unit pools more requests: shorter tail)
     uint32_t host_skew_pct = 8;  // a lone caller's host-mapped launch: first unit this many percent larger than the mean, last one as much smaller (ACL_HOST_SKEW_PCT;
                                  // worth 1-3 % of such a call -- the items do NOT arrive in block order, or 16 % would have hidden half the transfer: profiles/r04_host_skew.txt)
-    uint32_t host_split = 2;   // streams the slices of one large host batch are spread over (ACL_HOST_SPLIT, 1 = off; engine.cpp check_pass_local_host)
+    uint32_t host_split = 2;   // streams the slices of one large host batch are spread over (ACL_HOST_SPLIT, 1 = off; engine_pass.cpp check_pass_local_host)
     uint32_t local_upw = 1;    // single-launch pass over a large batch: work units per resident wave.  1 = every wave one unit of n / waves requests (no
                                // second round of per-level latency chains); 2 balances C4's uneven requests 3 % better but costs C2 a whole second round
     uint32_t local_static_pct = 100, local_dyn_unit = 32;  // chip-filling single-launch passes: share of the batch in static (one per block) units; hand-out unit size
@@ -451,7 +452,7 @@ struct acl_engine {
     std::mutex batcher_mu;       // start / stop
     // async submit / wait (engine_async.cpp)
     AsyncPool *async = nullptr;  // created by the first submit, destroyed by async_shutdown
-    aclint::InternPool *intern_pool = nullptr;  // host threads of bulk string interning (engine.cpp), created by the first large string batch
+    aclint::InternPool *intern_pool = nullptr;  // host threads of bulk string interning (engine_intern.cpp intern_pool), created by the first large string batch
     std::mutex intern_pool_mu;
     std::mutex async_mu;
     // pinned buffers handed out by acl_host_alloc: [base, base + bytes)
@@ -540,8 +541,13 @@ void merge_stats(acl_engine *h, PassCtx *c);
 // blocks > 0: the single-launch walk (per-block regions for units of rpw requests); 0: the level loop (one pool, counters in the status block)
 int combine_prepare(acl_engine *h, PassCtx *c, DevGraph *g, uint32_t n, uint32_t blocks, uint32_t rpw);
 int check_pass(acl_engine *h, PassCtx *c, const uint4 *d_items, uint32_t n, uint8_t *d_perm, int32_t *d_errout, bool try_local = true);
-// every level in ONE launch, wave-private frontiers; an internal negative code when a wave's private frontier overflowed (engine.cpp)
+// every level in ONE launch, wave-private frontiers; an internal negative code when a wave's private frontier overflowed (kTakeLevelLoop; engine_pass.cpp)
 int check_pass_local(acl_engine *h, PassCtx *c, const DevGraph &g, const uint4 *d_items, uint32_t n, uint8_t *d_perm, int32_t *d_errout);
+constexpr int kTakeLevelLoop = -1000;  // internal: a single-launch walk declines the batch, the level loop takes it (never leaves the library)
+#pragma GCC visibility push(hidden)
+bool spin_for(const volatile uint32_t *word, uint32_t val);  // engine_pass.cpp: the completion word of a small launch, polled instead of a stream synchronisation
+uint32_t next_done_val(PassCtx *c);                          // the value the next launch of c stores there (never 0)
+#pragma GCC visibility pop
 int not_sharded(acl_engine *h);
 int device_of(acl_engine *h, const void *p);  // HIP ordinal a device pointer lives on; -1 = any replica will do
 int check_device(acl_engine *h, PassCtx *c, const uint4 *d_items, size_t n, uint8_t *d_perm, int32_t *d_errout, bool try_local = true);  // try_local: the single-launch walk first
@@ -555,12 +561,15 @@ FilterText to_filter(const acl_filter_t *f);
 // strings -> interned item; returns 0 or the per-item error the pair carries (check.go:55).  Caller holds names_mu shared.
 int32_t intern_check_item(acl_engine_t *h, const acl_check_item_t &it, acl_item_t *out);
 void intern_pool_destroy(acl_engine_t *h);
-void host_parallel(acl_engine_t *h, size_t total, size_t piece, const std::function<void(size_t, size_t)> &fn);  // engine.cpp: pieces of [0, total) on the interning pool's threads + the caller
+void host_parallel(acl_engine_t *h, size_t total, size_t piece, const std::function<void(size_t, size_t)> &fn);  // engine_intern.cpp: pieces of [0, total) on the interning pool's threads + the caller
 unsigned host_threads(acl_engine_t *h);
-bool hostmap_takes(acl_engine *h, size_t n);  // engine.cpp: a host batch of n items is answered by the kernel across PCIe (no copies)
+bool hostmap_takes(acl_engine *h, size_t n);  // engine_pass.cpp: a host batch of n items is answered by the kernel across PCIe (no copies)
 int resolve_lookup(acl_engine_t *h, const char *rtype, const char *perm, const char *stype, const char *sid, const char *srel, int *rt_out, int *pm_out,
                    int *st_out, int *sr_out, uint32_t *sub_out);
-int check_bulk_keep_cstr_call(acl_engine_t *h, const acl_check_item_t *items, size_t n, const uint32_t *item_off, size_t k_items, uint8_t *keep_out);  // engine.cpp: acl_check_bulk_keep
+int check_bulk_keep_cstr_call(acl_engine_t *h, const acl_check_item_t *items, size_t n, const uint32_t *item_off, size_t k_items, uint8_t *keep_out);  // engine_keep.cpp: acl_check_bulk_keep
+int check_bulk_keep_v_call(acl_engine_t *h, const acl_check_item_v_t *items, size_t n, const uint32_t *item_off, size_t k_items, uint8_t *keep_out);
+int check_bulk_packed_call(acl_engine_t *h, const acl_packed_request_t *rq, uint8_t *perm_out, int32_t *err_out, const acl_call_opts_t *opts);
+int check_bulk_keep_packed_call(acl_engine_t *h, const acl_packed_request_t *rq, const uint32_t *item_off, size_t k_items, uint8_t *keep_out);
 int lookup_batch_call(acl_engine_t *h, int rtype, int perm, int stype, int srel, const uint32_t *sids, size_t n, uint32_t *bitmaps, size_t words,
                       uint64_t *counts, const CallOpts &opts);
 int lookup_one_routed(acl_engine_t *h, int rt, int pm, int st, int sr, uint32_t sub, uint32_t *bitmap_out, size_t words, uint64_t *count_out,

@@ -658,7 +658,7 @@ int acl_filter_list_response_req(acl_engine_t *h, const char *body, size_t body_
     const size_t npairs = off[items.size()];
     if (!npairs) return unchanged(items.size());  // postfilter.go:122-125
     // {pointer, length} views through acl_check_bulk_keep_v: a list filtered for ONE user by one template -- every pair shares type, permission and subject --
-    // is answered by one reverse walk and K bit tests (engine.cpp keep_by_reverse_walk), any other shape by the forward path
+    // is answered by one reverse walk and K bit tests (engine_keep.cpp keep_by_reverse_walk), any other shape by the forward path
     ci.assign(npairs, acl_check_item_v_t{});
     host_parallel(h, items.size(), std::max<size_t>(1024, items.size() / (4 * (size_t)host_threads(h))), [&](size_t a, size_t b) {
         auto sv = [](const std::string &x) { return acl_str_t{x.data(), x.size()}; };

@@ -4,7 +4,7 @@
 // What it returns per resource is exact for a monotone permission: a Check finds a subject iff some path of the programs reaches a row that names it
 // within the dispatch-depth limit, and that is what the walk marks.  A permission whose value can depend on `-`, `&` or `.all()` (Snapshot::slot_nonmono)
 // is walked by its positive relaxation: the row holds CANDIDATES, confirmed by one batched forward Check -- the way LookupResources confirms its own
-// (engine.cpp lookup_refine) -- and a candidate whose Check errs fails the call with ACL_ERR_DEPTH (ACL_FLAG_LENIENT_LOOKUP: it is left out).
+// (engine_lookup.cpp lookup_refine) -- and a candidate whose Check errs fails the call with ACL_ERR_DEPTH (ACL_FLAG_LENIENT_LOOKUP: it is left out).
 // `T:*` rows reached by the walk raise the answer's wildcard flag: "every subject of T, except the excluded row".
 #include "engine_internal.hpp"
 #include "validate.hpp"

@@ -14,7 +14,7 @@ namespace {
 
 // References / arrows in POSITIVE positions: a rewrite with `&` / `-` is walked backwards as a superset -- X true makes the parent a CANDIDATE
 // when X occurs anywhere but under the subtracted operand of an exclusion (every true value of `a - b`, `a & b` has a true positive operand);
-// the engine then runs the forward Check over the candidates (engine.cpp lookup_batch, Snapshot::slot_nonmono).
+// the engine then runs the forward Check over the candidates (engine_lookup.cpp lookup_batch, Snapshot::slot_nonmono).
 void collect(const Node &n, Node::Kind kind, std::vector<const Node *> *out) {
     // (a.all(b) true needs a true b on EVERY a: any true b makes the parent a candidate, as for a->b)
     if (n.kind == kind || (kind == Node::kArrow && n.kind == Node::kArrowAll)) out->push_back(&n);

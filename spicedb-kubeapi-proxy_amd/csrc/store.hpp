@@ -170,7 +170,7 @@ class ObjectTable {
     std::atomic<uint32_t> count_{0};
 };
 
-// Sorted unique relationship keys behind a shared pointer (copy on write): a background snapshot build (engine.cpp, snapshot
+// Sorted unique relationship keys behind a shared pointer (copy on write): a background snapshot build (engine_snapshot.cpp, snapshot
 // compaction) keeps iterating the vector it took under the lock while writers clone a table before their first change to it.
 class CowKeys {
   public:
@@ -276,7 +276,7 @@ class Store {
     uint64_t revision() const { return revision_; }
     // counts the writes that can ADD a path to the graph: relationships whose subject carries a relation (`group:g#member`) or whose relation is an arrow's
     // tupleset (`pod#namespace`), bulk loads, schema loads.  A relationship with a plain subject on any other relation ends every path it is on, and a removal
-    // (DELETE, expiry) only takes paths away: neither can make a Check end at the depth limit that did not before (engine.cpp no_object_is_deep).
+    // (DELETE, expiry) only takes paths away: neither can make a Check end at the depth limit that did not before (engine_keep.cpp no_object_is_deep).
     uint64_t path_adds() const { return path_adds_; }
     void settle_all();
     // A read-only twin for a background snapshot build: same schema, revision and clock, relationship tables SHARED

@@ -52,41 +52,54 @@ def test_postfilter_keep_mask(aclgpu):
             e.check_bulk_keep_ids(items, [0, n + 1])
 
 
+def _forward_pairs(e, items):  # names -> ids, then the id entry point: the forward walk whatever the pairs look like (a string call of one user's pairs
+    it16, rerr = e.resolve_bulk_views(e.make_check_views(items))  # may take the reverse walk itself)
+    assert not rerr.any()
+    return e.check_bulk_ids(it16)
+
+
+def _forward_keep(e, items, off):  # ... and the AND over each item's pairs (postfilter.go:144-178)
+    p, er = _forward_pairs(e, items)
+    return np.array([all(p[j] == 2 and er[j] == 0 for j in range(off[i], off[i + 1])) for i in range(len(off) - 1)])
+
+
+def _c3_named(e, w):  # names for every pod and user of a C3 graph, interned before the graph is loaded: dense id i is names[type][i]
+    import ctypes
+    pod_ns = np.zeros(w.nobjects["pod"], dtype=np.int64)
+    for ed in w.edges:
+        if ed[0] == "pod" and ed[1] == "namespace":
+            pod_ns[ed[4]] = ed[5]
+    names = {"pod": [f"ns{int(pod_ns[i])}/pod-{i}" for i in range(w.nobjects["pod"])], "user": [f"user-{i}" for i in range(w.nobjects["user"])]}
+    out = ctypes.c_uint32()
+    for t_, ns_ in names.items():
+        tid = e.type_id(t_)
+        for nm in ns_:
+            e._check(e._L.acl_intern(e._h, tid, nm.encode(), ctypes.byref(out)))
+    w.load(e)
+    return names
+
+
 def test_postfilter_one_subject_reverse_route(aclgpu):
     """Round 6.  A PostFilter call names ONE subject for all its pairs (reference pkg/authz/postfilter.go:67-119): acl_check_bulk_keep_v
     and acl_check_bulk_keep_packed answer such a call by one reverse walk + bit tests.  Compared here, on named objects: both entry points (route taken: the stats
     say so), the forward path (acl_check_bulk_v + the AND of postfilter.go:144-178) and the oracle -- for a power user, an ordinary user, a user nobody knows; with
     unknown pod names in the list, ragged pair ranges, and the calls the route must NOT take (two subjects, a userset subject) or must fail exactly as the forward
     path fails (an id the API refuses: the message names the field).  acl_check_bulk_packed answers as acl_check_bulk_v."""
-    import ctypes
     from aclgpu import workloads
     w = workloads.c3(scale=0.05, batch=256, power_users=4)
     o = orc.Oracle(w.schema)
     w.load(o)
     o.freeze()
-    npod, nuser = w.nobjects["pod"], w.nobjects["user"]
-    pod_ns = np.zeros(npod, dtype=np.int64)
-    for ed in w.edges:
-        if ed[0] == "pod" and ed[1] == "namespace":
-            pod_ns[ed[4]] = ed[5]
-    names = {"pod": [f"ns{int(pod_ns[i])}/pod-{i}" for i in range(npod)], "user": [f"user-{i}" for i in range(nuser)]}
+    npod = w.nobjects["pod"]
     rng = np.random.default_rng(11)
     with aclgpu.Engine(w.schema) as e:
-        out = ctypes.c_uint32()
-        for t_, ns_ in names.items():
-            tid = e.type_id(t_)
-            for nm in ns_:
-                e._check(e._L.acl_intern(e._h, tid, nm.encode(), ctypes.byref(out)))
-        w.load(e)
+        names = _c3_named(e, w)
 
-        def forward_pairs(items):  # names -> ids, then the id entry point: the forward walk whatever the pairs look like (a string call of one user's pairs
-            it16, rerr = e.resolve_bulk_views(e.make_check_views(items))  # takes the reverse walk itself on this schema: below)
-            assert not rerr.any()
-            return e.check_bulk_ids(it16)
+        def forward_pairs(items):
+            return _forward_pairs(e, items)
 
         def forward(items, off):
-            p, er = forward_pairs(items)
-            return np.array([all(p[j] == 2 and er[j] == 0 for j in range(off[i], off[i + 1])) for i in range(len(off) - 1)])
+            return _forward_keep(e, items, off)
 
         K = 3000
         routed = 0
@@ -179,6 +192,41 @@ def test_postfilter_one_subject_reverse_route(aclgpu):
             e.check_bulk_packed((rq, keep_alive))
         assert ei.value.code == aclgpu.ERR_INVALID_ARGUMENT and "dictionary index" in str(ei.value)
         assert routed == 18
+
+
+def test_reverse_route_thresholds(aclgpu):
+    """The sizes at which the one-subject route (csrc/engine_keep.cpp keep_by_reverse_walk) changes what it does, on a fresh engine, for one ordinary user: below
+    512 pairs it is not taken; the first routed call finds no interning pool and runs the walk and then the pass on the caller's thread; from 2 048 items on the
+    pool is created and the pass spread over it; a K x F call (keep_by_reverse_walks) is taken from 512 items on and counts one walk per template.  Every mask
+    equals the forward answer (names -> ids -> acl_check_bulk_ids, AND over each item's pairs)."""
+    from aclgpu import workloads
+    w = workloads.c3(scale=0.05, batch=256, power_users=4)
+    rng = np.random.default_rng(23)
+    with aclgpu.Engine(w.schema) as e:
+        names = _c3_named(e, w)
+        uname = names["user"][3]
+        calls = lambda: e.stats()["keep_route_calls"]
+
+        def one_pair_items(k):
+            return [("pod", names["pod"][int(p_)], "view", "user", uname, "") for p_ in rng.integers(0, w.nobjects["pod"], size=k)]
+
+        seen_kept = 0
+        for k, moves in ((511, 0), (512, 1), (2048, 1)):  # not taken; sequential walk + pass (no pool yet); the pool is created and takes the pass
+            items, off = one_pair_items(k), np.arange(k + 1, dtype=np.uint32)
+            before = calls()
+            keep = e.check_bulk_keep_views(e.make_check_views(items), off).astype(bool)
+            assert calls() == before + moves, k
+            assert np.array_equal(keep, _forward_keep(e, items, off)), k
+            seen_kept += int(keep.sum())
+        assert seen_kept > 0  # (the user sees some of the pods: the masks are not all-false by accident)
+        for k, moves in ((512, 2), (511, 0)):  # K items x 2 templates: one walk per template from 512 items on
+            pods = rng.integers(0, w.nobjects["pod"], size=k)
+            items = [("pod", names["pod"][int(p_)], perm, "user", uname, "") for p_ in pods for perm in ("view", "creator")]
+            off = np.arange(0, 2 * k + 1, 2, dtype=np.uint32)
+            before = calls()
+            keep = e.check_bulk_keep_views(e.make_check_views(items), off).astype(bool)
+            assert calls() == before + moves, k
+            assert np.array_equal(keep, _forward_keep(e, items, off)), k
 
 
 def test_postfilter_and_prefilter_mirror(aclgpu):
@@ -590,7 +638,7 @@ def test_every_call_shape_at_once_native_threads(aclgpu, tmp_path):
 
 
 def test_check_bulk_of_one_subject_behind_a_cycle_of_groups_carries_the_depth_errors(aclgpu):
-    """CheckBulkPermissions by one reverse walk (engine.cpp keep_by_reverse_walk, pair form) where the row's missing bit cannot tell NO_PERMISSION from "gave up at
+    """CheckBulkPermissions by one reverse walk (engine_keep.cpp keep_by_reverse_walk, pair form) where the row's missing bit cannot tell NO_PERMISSION from "gave up at
     the dispatch-depth limit": `group#member` is recursive and two groups contain each other, so pods shared with them answer a depth ERROR for a user who is in
     neither -- per pair, as the oracle does.  The depth sweep (no_object_is_deep) finds those pods and hands their bitmap to the route: the first call goes forward
     (nothing known about the snapshot yet), the second sweeps and walks, the third walks -- every pair's permissionship AND error the oracle's each time; the keep
@@ -624,7 +672,7 @@ definition pod { relation viewer: user | group#member
 
 def test_check_bulk_of_one_subject_on_nested_groups_takes_the_reverse_walk_once_the_snapshot_is_known_shallow(aclgpu):
     """The pair form on a RECURSIVE permission (nested groups, SURVEY 8(d) C4's schema): the schema cannot rule a depth error out, the snapshot can -- one forward
-    sweep over the type for a subject nobody is (engine.cpp no_object_is_deep; the property it rests on: tests/test_oracle_cross.py
+    sweep over the type for a subject nobody is (engine_keep.cpp no_object_is_deep; the property it rests on: tests/test_oracle_cross.py
     test_a_depth_error_does_not_depend_on_the_subject).  First call at a snapshot: forward, and a note; second: the sweep, then the reverse walk; a write starts
     over.  A cycle written behind some pods: after one more sweep the calls still walk, their pairs' depth errors from the deep pods' bitmap (as the oracle's); deleting it: shallow again.
     Every answer is the oracle's (check.go:54-69: pair i answers item i)."""
@@ -706,7 +754,7 @@ definition pod { relation namespace: namespace
 
 def test_postfilter_k_items_times_f_templates_one_walk_per_template(aclgpu):
     """K list items x F PostFilter templates for the requesting user (postfilter.go:86-119: every filter of every matching rule): pair j of every item comes
-    from template j, so each template position is a one-subject call of its own -- engine.cpp keep_by_reverse_walks answers the F of them by their reverse walks
+    from template j, so each template position is a one-subject call of its own -- engine_keep.cpp keep_by_reverse_walks answers the F of them by their reverse walks
     under ONE evaluation and ANDs the masks.  Compared with the oracle (an item is kept when every pair is HAS_PERMISSION without error, postfilter.go:144-178);
     the stats say F walks were taken.  Shapes the route must leave to the forward path: an item with a pair missing, a template position with two subjects."""
     schema = """definition user {}

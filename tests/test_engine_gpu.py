@@ -381,7 +381,7 @@ definition pod { relation namespace: namespace
             assert list(zip(p2.tolist(), er2.tolist())) == want[:100], form
         assert {w_[1] for w_ in want} >= {0, aclgpu.ERR_FAILED_PRECONDITION} and 0 < sum(w_[0] == 2 for w_ in want) < len(want)
         # the proxy's batches repeat themselves (one user for every pair of a PostFilter call, postfilter.go:88-119; F templates per list item): a
-        # name equal to the previous item's is not looked up again (engine.cpp intern_items) -- runs of one subject, runs of one resource, the same
+        # name equal to the previous item's is not looked up again (engine_intern.cpp intern_items) -- runs of one subject, runs of one resource, the same
         # STRING under two types next to each other, unknown names and erroring items inside the runs, runs across the 16-item groups
         rep = []
         for k in range(5200):
@@ -414,7 +414,7 @@ definition pod { relation namespace: namespace
 @pytest.mark.parametrize("split", ["1", "2", "4"])
 def test_host_batches_as_concurrent_slices(split, aclgpu, monkeypatch):
     """A host batch beyond one launch goes as sub-passes that alternate between streams of their own, each with a frontier region of its own
-    (engine.cpp check_pass_local_host; ACL_HOST_SPLIT streams, 1 = one after the other); a lone caller's 262 144-item batch is cut in two the same
+    (engine_pass.cpp check_pass_local_host; ACL_HOST_SPLIT streams, 1 = one after the other); a lone caller's 262 144-item batch is cut in two the same
     way.  1 200 000 items (3 slices over 1 / 2 / 3 lanes), 262 144 and 300 001 items: every answer equals the oracle's whatever the lanes."""
     from aclgpu import workloads
     monkeypatch.setenv("ACL_HOST_SPLIT", split)  # (read at acl_open)

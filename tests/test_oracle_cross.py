@@ -321,7 +321,7 @@ def test_cycles_through_nonmonotone_permissions_agree():
 
 
 def test_a_depth_error_does_not_depend_on_the_subject():
-    """What the engine's depth sweep rests on (csrc/engine.cpp no_object_is_deep): a Check that does not find its subject explores every path below its resource,
+    """What the engine's depth sweep rests on (csrc/engine_keep.cpp no_object_is_deep): a Check that does not find its subject explores every path below its resource,
     so whether it ends at the dispatch-depth limit (spicedb.go:34) is a property of the RESOURCE -- the same for a subject nobody is.  Random group graphs with
     cycles, self-memberships and chains across the limit, unions and arrows only (the route is not taken for `&` / `-`), both oracles."""
     import random

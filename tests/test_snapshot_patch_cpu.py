@@ -205,7 +205,7 @@ def test_patching_a_shard(aclgpu, world):
 
 
 def test_background_compaction_host_half(aclgpu):
-    """Snapshot compaction (engine.cpp): a snapshot built from a COPY-ON-WRITE view of the store while writes keep landing,
+    """Snapshot compaction (engine_snapshot.cpp): a snapshot built from a COPY-ON-WRITE view of the store while writes keep landing,
     then caught up with the ordinary patcher and adopted, must describe exactly the store -- including writes that hit the very
     tables the build was reading (they clone the table first) and deletes of relationships the view still held."""
     rng = random.Random(11)

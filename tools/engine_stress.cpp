@@ -22,7 +22,7 @@ static const char *kSchema =
     "definition pod {\n  relation namespace: namespace\n  relation viewer: user\n  relation creator: user\n"
     "  permission view = viewer + creator + namespace->view\n}\n"
     // (a RECURSIVE corner of the schema, which neither the writer nor the other requests touch: one user's doc pairs through acl_check_bulk_v take the reverse
-    //  walk only after a forward sweep has shown that no doc's Check ends at the depth limit on the snapshot at hand -- engine.cpp no_object_is_deep)
+    //  walk only after a forward sweep has shown that no doc's Check ends at the depth limit on the snapshot at hand -- engine_keep.cpp no_object_is_deep)
     "definition group {\n  relation member: user | group#member\n}\n"
     "definition doc {\n  relation viewer: user | group#member\n  permission view = viewer\n}\n";
 

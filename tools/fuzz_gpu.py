@@ -166,7 +166,7 @@ def run(seed: int, steps: int, big: int = 70000, verbose: bool = True, burst: in
             live = set(f"{a}:{b}#{c}@{d}:{x}" + (f"#{y}" if y else "") for t in ("group", "namespace", "pod") for a, b, c, d, x, y, _ in o.read(rtype=t))
             stats["filter_deletes"] += 1
         elif r < 0.56 and not combine:  # ---- PostFilter's shape: ONE user's pairs -- CheckBulkPermissions itself twice (the second call may sweep the type for depth
-            # errors and take the reverse walk: engine.cpp no_object_is_deep; with a cycle behind some resource the calls stay forward and carry its depth errors),
+            # errors and take the reverse walk: engine_keep.cpp no_object_is_deep; with a cycle behind some resource the calls stay forward and carry its depth errors),
             # then the keep mask of the same pairs.  Every permissionship, every error and every keep byte against the oracle.
             rt, perm, ids = rng.choice([("pod", "view", pods), ("namespace", "view", nss), ("group", "member", groups)])
             u = rng.choice(users) if rng.random() < 0.9 else "stranger"

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """usage (GPU box): [ACL_DEBUG_KEEP=1] python tools/keep_route_probe.py [--calls 40] -- PostFilter's shape on C4's named graph (K list items x one template for ONE
 user): acl_check_bulk_keep_v / _packed through the reverse-walk route and acl_check_bulk_v of the same pairs (CheckBulkPermissions itself: the pair form of the route --
-on C4's recursive schema after the depth sweep, engine.cpp no_object_is_deep; ACL_KEEP_ROUTE_MIN=0 or ACL_DEPTH_SWEEP=0 in the environment gives the forward path); one line per (K, user).  The masks are
+on C4's recursive schema after the depth sweep, engine_keep.cpp no_object_is_deep; ACL_KEEP_ROUTE_MIN=0 or ACL_DEPTH_SWEEP=0 in the environment gives the forward path); one line per (K, user).  The masks are
 compared with the id path's answers.  ACL_DEBUG_KEEP=1 prints the route's phase times per call on stderr."""
 import argparse
 import json
@@ -63,7 +63,7 @@ for m in [int(x) for x in a.sizes.split(",")]:
             row[form] = {"M_items_per_s": round(m / float(np.mean(ts)) / 1e6, 1), "p50_ms": round(1e3 * float(np.median(ts)), 4), "best_ms": round(1e3 * min(ts), 4),
                          "mask_ok": ok, "by_reverse_walk": int(eng.stats()["keep_route_calls"] - before)}
         if a.workload == "c4" and u is not None:
-            # K items x TWO templates (pod#view and pod#creator for the same user): one walk per template under one evaluation (engine.cpp keep_by_reverse_walks);
+            # K items x TWO templates (pod#view and pod#creator for the same user): one walk per template under one evaluation (engine_keep.cpp keep_by_reverse_walks);
             # beside it the same 2 K pairs by id through the forward walk + the AND
             q2 = [x for r in w.res[:m] for x in ((rt, names[rt][int(r)], perm_name, st, uname, ""), (rt, names[rt][int(r)], "creator", st, uname, ""))]
             off2 = np.arange(0, 2 * m + 1, 2, dtype=np.uint32)

@@ -10,7 +10,7 @@ CXX=/opt/rocm/lib/llvm/bin/clang++
 for SAN in thread address,undefined; do
   T=/tmp/aclgpu_san_$(echo $SAN | tr , _)
   mkdir -p $T
-  for f in schema store plan plan_reverse engine engine_shard engine_shard_native engine_callers engine_async engine_list bootstrap_yaml; do
+  for f in $(make -s --no-print-directory -C $P print-host-src); do  # (the Makefile's own list of host sources)
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -fPIC -fsanitize=$SAN -fno-gpu-sanitize -fno-sanitize=vptr -Wno-option-ignored -x hip -c $P/csrc/$f.cpp -o $T/$f.o 2> /dev/null &
   done
   wait

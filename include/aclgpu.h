@@ -289,7 +289,8 @@ int acl_lookup_resources_batch(acl_engine_t *h, int rtype, int permission, int s
  * a `stype:*` relationship grants it to every subject of the type -- except those of the `excluded` row, which is only computed when asked for
  * (NULL: not computed) and only non-empty for a permission with `-`, `&` or `.all()`.  A reached subject whose Check runs into the depth limit fails
  * the call with ACL_ERR_DEPTH, unless the engine was opened with ACL_FLAG_LENIENT_LOOKUP (then it is left out).  An id beyond the resource type's
- * objects: ACL_ERR_INVALID_ARGUMENT; a resource without relationships: an empty answer.  Sharded engines: ACL_ERR_FAILED_PRECONDITION. */
+ * objects: ACL_ERR_INVALID_ARGUMENT; a resource without relationships: an empty answer.  Sharded engines: through acl_shard_subjects_bulk (these two
+ * entry points answer ACL_ERR_FAILED_PRECONDITION there). */
 #define ACL_SUBJECTS_WILDCARD 1u
 /* batched form: n resources of one (rtype, permission); bitmaps_out (and excluded_out when given) are n * bitmap_words; flags_out may be NULL */
 int acl_lookup_subjects_batch(acl_engine_t *h, int rtype, int permission, int stype, int srel /* -1 none */, const uint32_t *resource_ids, size_t n,
@@ -501,6 +502,19 @@ int acl_shard_check_bulk(acl_engine_t *h, const acl_shard_comm_t *comm, const vo
 /* LookupResources for n subjects (host array) of one class: n rows of bitmap_words words in device memory, the same on every shard afterwards */
 int acl_shard_lookup_bulk(acl_engine_t *h, const acl_shard_comm_t *comm, int rtype, int permission, int stype, int srel /* -1 none */, const uint32_t *subject_ids,
                           size_t n, void *d_bitmaps_out, size_t bitmap_words, acl_shard_bulk_stats_t *stats_out);
+/* LookupSubjects for n resources (host array) of one (rtype, permission) on the sharded graph -- the contract of acl_lookup_subjects_batch, as a level loop
+ * of its own: a state is expanded on the shard that owns its type, over that shard's subject rows; children of other shards' types cross in the level's
+ * exchange; every shard marks the subjects ITS rows name and the partial rows are all-gathered and OR-ed (several shards set different bits of one
+ * byte, so all_reduce_max_u8 only carries the wildcard flags).  d_bitmaps_out: n rows of bitmap_words words in device memory; flags_out: n bytes on the
+ * HOST (bit 0: ACL_SUBJECTS_WILDCARD), may be NULL; d_excluded_out: n rows of bitmap_words words in device memory, may be NULL (not computed).  All
+ * three are the same on every shard afterwards, and a failure (ACL_ERR_DEPTH from a reached subject's Check unless ACL_FLAG_LENIENT_LOOKUP, a row beyond
+ * the enumeration limit) is taken by all shards or by none.  A permission with `-`, `&` or `.all()`: candidates by the positive relaxation, confirmed
+ * by one sharded Check in which every shard takes part.  world == 1 is allowed (every collective runs once).  Unknown type / permission:
+ * ACL_ERR_FAILED_PRECONDITION; a bitmap too small or an id beyond the type's objects: ACL_ERR_INVALID_ARGUMENT; a store-only engine: ACL_ERR_UNAVAILABLE.
+ * Only the native loop has LookupSubjects: the host-driven step protocol (acl_shard_*_begin / step / import / finish) is not extended. */
+int acl_shard_subjects_bulk(acl_engine_t *h, const acl_shard_comm_t *comm, int rtype, int permission, int stype, int srel /* -1 none */,
+                            const uint32_t *resource_ids, size_t n, void *d_bitmaps_out, size_t bitmap_words, uint8_t *flags_out /* host, n bytes, may be NULL */,
+                            void *d_excluded_out /* n * bitmap_words, may be NULL */, acl_shard_bulk_stats_t *stats_out);
 #define ACL_RCCL_UNIQUE_ID_BYTES 128
 int acl_shard_rccl_unique_id(void *id_out /* ACL_RCCL_UNIQUE_ID_BYTES; rank 0 makes it, the host hands it to every rank */);
 int acl_shard_rccl_init(acl_engine_t *h, const void *unique_id, uint32_t rank, uint32_t world); /* also acl_shard_configure(rank, world) */
@@ -508,6 +522,8 @@ int acl_shard_rccl_destroy(acl_engine_t *h);
 int acl_shard_check_bulk_rccl(acl_engine_t *h, const void *d_items, size_t n, void *d_perm_out, void *d_err_out, acl_shard_bulk_stats_t *stats_out);
 int acl_shard_lookup_bulk_rccl(acl_engine_t *h, int rtype, int permission, int stype, int srel, const uint32_t *subject_ids, size_t n, void *d_bitmaps_out,
                                size_t bitmap_words, acl_shard_bulk_stats_t *stats_out);
+int acl_shard_subjects_bulk_rccl(acl_engine_t *h, int rtype, int permission, int stype, int srel, const uint32_t *resource_ids, size_t n, void *d_bitmaps_out,
+                                 size_t bitmap_words, uint8_t *flags_out, void *d_excluded_out, acl_shard_bulk_stats_t *stats_out);
 
 /* ---- test hook ----
  * Updates the HOST copy of the snapshot the way the next read would (in-place patch from the change feed when

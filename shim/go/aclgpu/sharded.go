@@ -6,6 +6,7 @@ package aclgpu
 import "C"
 
 import (
+	"errors"
 	"unsafe"
 )
 
@@ -39,6 +40,31 @@ func (e *Engine) JoinShards(id [C.ACL_RCCL_UNIQUE_ID_BYTES]byte, rank, world uin
 func (e *Engine) ShardedCheckBulk(dItems unsafe.Pointer, n int, dPerm, dErr unsafe.Pointer) (levels, exchanges uint32, err error) {
 	var st C.acl_shard_bulk_stats_t
 	if rc := C.acl_shard_check_bulk_rccl(e.h, dItems, C.size_t(n), dPerm, dErr, &st); rc != 0 {
+		return 0, 0, lastError(rc)
+	}
+	return uint32(st.levels), uint32(st.exchanges), nil
+}
+
+// ShardedLookupSubjects answers LookupSubjects for n resources of one (type, permission) with all shards together (acl_shard_subjects_bulk_rccl: the
+// native level loop; the host-driven step protocol has no LookupSubjects).  SPMD: every rank calls it with the SAME interned ids.  dBitmaps (and
+// dExcluded, which may be nil: not computed) are device pointers to n rows of bitmapWords words over the subject type's ids; flags[i] bit 0 says a
+// `T:*` grant answers resource i (flags == nil: not wanted; a non-nil slice shorter than resourceIDs is an error).  Rows, flags and excluded rows come
+// back identical on every rank; an error is returned by all ranks or by none.
+func (e *Engine) ShardedLookupSubjects(rtype, permission, stype, srel int, resourceIDs []uint32, dBitmaps unsafe.Pointer, bitmapWords int, flags []uint8,
+	dExcluded unsafe.Pointer) (levels, exchanges uint32, err error) {
+	var st C.acl_shard_bulk_stats_t
+	var ids *C.uint32_t
+	if len(resourceIDs) > 0 {
+		ids = (*C.uint32_t)(unsafe.Pointer(&resourceIDs[0]))
+	}
+	var fl *C.uint8_t
+	if flags != nil && len(flags) < len(resourceIDs) {
+		return 0, 0, errors.New("aclgpu: ShardedLookupSubjects: flags is shorter than resourceIDs")
+	}
+	if len(flags) > 0 {
+		fl = (*C.uint8_t)(unsafe.Pointer(&flags[0]))
+	}
+	if rc := C.acl_shard_subjects_bulk_rccl(e.h, C.int(rtype), C.int(permission), C.int(stype), C.int(srel), ids, C.size_t(len(resourceIDs)), dBitmaps, C.size_t(bitmapWords), fl, dExcluded, &st); rc != 0 {
 		return 0, 0, lastError(rc)
 	}
 	return uint32(st.levels), uint32(st.exchanges), nil

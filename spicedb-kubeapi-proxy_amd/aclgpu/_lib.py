@@ -29,7 +29,7 @@ SYMBOLS = [
     "acl_shard_rccl_destroy", "acl_shard_check_bulk_rccl", "acl_shard_lookup_bulk", "acl_shard_lookup_bulk_rccl", "acl_selfcheck_compaction", "acl_check_one_submit", "acl_check_completions",
     "acl_lookup_one_submit", "acl_lookup_completions", "acl_prefilter_response", "acl_open_replicas", "acl_replica_calls", "acl_watch_wait", "acl_watch_recheck", "acl_load_bootstrap_yaml",
     "acl_check_bulk_v_opts", "acl_object_name_copy", "acl_resolve_bulk_v", "acl_check_bulk_packed", "acl_check_bulk_keep_v", "acl_check_bulk_keep_packed", "acl_selfcheck_json_array", "acl_bitmap_names",
-    "acl_lookup_subjects_batch", "acl_lookup_subjects",
+    "acl_lookup_subjects_batch", "acl_lookup_subjects", "acl_shard_subjects_bulk", "acl_shard_subjects_bulk_rccl",
 ]
 
 
@@ -236,6 +236,10 @@ def load():
     L.acl_shard_check_bulk_rccl.argtypes = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(ShardBulkStats)]
     L.acl_shard_lookup_bulk.argtypes = [H, C.POINTER(ShardComm), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(ShardBulkStats)]
     L.acl_shard_lookup_bulk_rccl.argtypes = [H, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(ShardBulkStats)]
+    L.acl_shard_subjects_bulk.argtypes = [H, C.POINTER(ShardComm), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                          C.POINTER(ShardBulkStats)]
+    L.acl_shard_subjects_bulk_rccl.argtypes = [H, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                               C.POINTER(ShardBulkStats)]
     L.acl_shard_stream.argtypes = [H]
     L.acl_shard_stream.restype = C.c_void_p
     L.acl_shard_check_begin.argtypes = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]

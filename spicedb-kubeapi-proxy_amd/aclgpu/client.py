@@ -7,8 +7,10 @@ INTEGRATION.md is the same mapping in cgo.
 Only the methods the reference invokes are implemented: CheckPermission
 (pkg/authz/watch.go:50), CheckBulkPermissions (check.go:48, postfilter.go:134),
 LookupResources (lookups.go:65), WriteRelationships (distributedtx/activity.go:60),
-ReadRelationships (activity.go:107), DeleteRelationships (e2e/util_test.go:66).  The other
-four raise UNIMPLEMENTED, as the shim does.
+ReadRelationships (activity.go:107), DeleteRelationships (e2e/util_test.go:66) -- and
+LookupSubjects, which the reference never calls but the engine answers (Engine.lookup_subjects)
+and the Go shim serves.  The other three (ExpandPermissionTree, ExportBulkRelationships,
+ImportBulkRelationships) raise UNIMPLEMENTED, as the shim does.
 """
 from __future__ import annotations
 
@@ -20,6 +22,7 @@ from .engine import (AclError, Engine, OP_CREATE, OP_DELETE, OP_TOUCH, PERM_HAS,
 # authzed.api.v1 enums
 PERMISSIONSHIP_UNSPECIFIED, PERMISSIONSHIP_NO_PERMISSION, PERMISSIONSHIP_HAS_PERMISSION, PERMISSIONSHIP_CONDITIONAL_PERMISSION = 0, 1, 2, 3
 LOOKUP_PERMISSIONSHIP_HAS_PERMISSION = 1
+LOOKUP_PERMISSIONSHIP_UNSPECIFIED = 0  # (on an excluded subject: it does not hold the permission)
 OPERATION_CREATE, OPERATION_TOUCH, OPERATION_DELETE = OP_CREATE, OP_TOUCH, OP_DELETE
 PRECONDITION_MUST_NOT_MATCH, PRECONDITION_MUST_MATCH = PRE_MUST_NOT_MATCH, PRE_MUST_MATCH
 CODE_UNIMPLEMENTED = 12
@@ -116,6 +119,27 @@ class LookupResourcesResponse:
 
 
 @dataclass
+class LookupSubjectsRequest:
+    resource: ObjectReference = field(default_factory=ObjectReference)
+    permission: str = ""
+    subject_object_type: str = ""
+    optional_subject_relation: str = ""
+
+
+@dataclass
+class ResolvedSubject:
+    subject_object_id: str = ""
+    permissionship: int = LOOKUP_PERMISSIONSHIP_HAS_PERMISSION
+
+
+@dataclass
+class LookupSubjectsResponse:
+    subject: ResolvedSubject = field(default_factory=ResolvedSubject)
+    excluded_subjects: List[ResolvedSubject] = field(default_factory=list)  # only on the wildcard's message: who `*` leaves out
+    looked_up_at: int = 0
+
+
+@dataclass
 class WriteRelationshipsResponse:
     written_at: int = 0  # ZedToken: monotonically increasing store revision
 
@@ -185,6 +209,17 @@ class PermissionsServiceClient:
         for i in sorted(ids):
             yield LookupResourcesResponse(i, LOOKUP_PERMISSIONSHIP_HAS_PERMISSION, rev)
 
+    def LookupSubjects(self, req: LookupSubjectsRequest) -> Iterator[LookupSubjectsResponse]:
+        """Who holds req.permission on req.resource, as a stream of subject ids (Engine.lookup_subjects).  A `T:*` grant comes first, as the
+        subject "*" with the ids it leaves out; then one message per subject, ascending by id."""
+        ids, wildcard, excluded = self.engine.lookup_subjects(req.resource.object_type, req.resource.object_id, req.permission, req.subject_object_type,
+                                                              req.optional_subject_relation)
+        rev = self.engine.revision
+        if wildcard:
+            yield LookupSubjectsResponse(ResolvedSubject("*"), [ResolvedSubject(x, LOOKUP_PERMISSIONSHIP_UNSPECIFIED) for x in sorted(excluded)], rev)
+        for i in sorted(ids):
+            yield LookupSubjectsResponse(ResolvedSubject(i), [], rev)
+
     def ReadRelationships(self, flt: RelationshipFilter) -> Iterator[ReadRelationshipsResponse]:
         rev = self.engine.revision
         for rt, rid, rel, st, sid, srel, exp in self.engine.read(**_filter_kwargs(flt)):
@@ -208,7 +243,7 @@ class PermissionsServiceClient:
     def _unimplemented(self, *_a, **_k):
         raise AclError(CODE_UNIMPLEMENTED, "not implemented by the GPU ACL engine (never called by spicedb-kubeapi-proxy)")
 
-    LookupSubjects = ExpandPermissionTree = ExportBulkRelationships = ImportBulkRelationships = _unimplemented
+    ExpandPermissionTree = ExportBulkRelationships = ImportBulkRelationships = _unimplemented
 
 
 @dataclass

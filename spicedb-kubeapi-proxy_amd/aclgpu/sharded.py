@@ -521,6 +521,32 @@ class ShardedEngine:
             e._check(rc)
             return bitmaps[:sids.size], {f: int(getattr(st, f)) for f, _t in _lib.ShardBulkStats._fields_}
 
+    def lookup_subjects_ids_batch_native(self, rtype, perm, stype, srel, resource_ids, want_excluded=False):
+        """LookupSubjects through acl_shard_subjects_bulk: the level loop of the sharded graph inside libaclgpu.so (only the native loop has it).
+        -> (bitmaps int32 tensor [n, words] over the subject type's ids, flags uint8 [n] (bit 0: wildcard), excluded tensor or None, stats dict),
+        the same on every rank."""
+        sh = self.shard
+        if getattr(self, "_native", None) is None:
+            self._native = RcclNative(sh, self.comm) if isinstance(self.comm, TorchComm) else ThreadNative(self.comm)
+        rids = np.ascontiguousarray(resource_ids, dtype=np.uint32)
+        e = sh.e
+        with sh.stream():
+            words = sh.lookup_words(stype)
+            bitmaps = torch.zeros((max(1, rids.size), words), dtype=torch.int32, device=sh.device)
+            excluded = torch.zeros((max(1, rids.size), words), dtype=torch.int32, device=sh.device) if want_excluded else None
+            flags = np.zeros(max(1, rids.size), dtype=np.uint8)
+            torch.cuda.current_stream().synchronize()
+            st = _lib.ShardBulkStats()
+            args = (e.type_id(rtype), e.relation_id(rtype, perm), e.type_id(stype), e.relation_id(stype, srel), rids.ctypes.data, rids.size, bitmaps.data_ptr(), words,
+                    flags.ctypes.data, excluded.data_ptr() if want_excluded else None, C.byref(st))
+            if self._native.struct is None:
+                rc = sh._L.acl_shard_subjects_bulk_rccl(sh._h, *args)
+            else:
+                rc = sh._L.acl_shard_subjects_bulk(sh._h, C.byref(self._native.struct), *args)
+            e._check(rc)
+            return (bitmaps[:rids.size], flags[:rids.size], excluded[:rids.size] if want_excluded else None,
+                    {f: int(getattr(st, f)) for f, _t in _lib.ShardBulkStats._fields_})
+
     def _check_levels(self, items, has, err):
         if self.exchange == "alltoall":
             return self._check_levels_a2a(items, has, err)

@@ -257,8 +257,9 @@ struct PassCtx {
     DevArray<uint32_t> d_xctrl;
     PinnedBuf h_xctrl;
     uint32_t xcap = 0;
-    std::vector<uint8_t> xplan_fwd, xplan_rev;  // [iteration] the previous batch exported something there: exchange entries (empty: always)
+    std::vector<uint8_t> xplan_fwd, xplan_rev, xplan_subj;  // [iteration] the previous batch exported something there: exchange entries (empty: always)
     uint32_t rev_levels_hint = 4;
+    uint32_t subj_levels_hint = 6;
     uint32_t levels_hint = 6;
     CallOpts opts;  // of the call that holds this context
     // measurement (merged into the engine's stats when the context is released)
@@ -502,6 +503,8 @@ int ensure_snapshot(acl_engine *h);
 int ensure_reverse(acl_engine *h);
 int ensure_subjects(acl_engine *h);     // engine_subjects.cpp; the snapshot is current
 bool subjects_current(acl_engine *h);   // caller holds state_mu at least shared
+constexpr uint32_t kFreshSubject = 0xFFFFFFFCu;  // LookupSubjects: an id of the subject type that no relationship names (intern_check_item's unknown subject) -- the wildcard's stand-in
+int subjects_error(int32_t code, uint32_t rid, uint32_t sid);  // fails a LookupSubjects call with a reached subject's Check error (engine_subjects.cpp)
 // true when the device snapshot answers for the store as it is now (caller holds state_mu at least shared)
 bool snapshot_current(acl_engine *h, bool need_reverse);
 void compaction_join(acl_engine *h);  // acl_close / schema reload: waits for a build in flight and drops its result
@@ -531,7 +534,8 @@ struct ShardCall {
     ShardCall(const ShardCall &) = delete;
     ShardCall &operator=(const ShardCall &) = delete;
     ~ShardCall();
-    int begin(acl_engine *h_, bool fresh, bool need_reverse, bool combine_ok = false /* the caller evaluates schemas with `&` / `-` (the native Check loop) */);
+    int begin(acl_engine *h_, bool fresh, bool need_reverse, bool combine_ok = false /* the caller evaluates schemas with `&` / `-` (the native Check loop) */,
+              bool need_subjects = false /* the subject rows of LookupSubjects must be current too (ensure_subjects) */);
 };
 DevShard dev_shard(acl_engine *h, PassCtx *c, void *d_export, size_t cap);
 int new_ctx(acl_engine *h, DevState *d, std::unique_ptr<PassCtx> *out, int index);  // (leaves the calling thread on d's device)

@@ -19,7 +19,7 @@ DevShard dev_shard(acl_engine *h, PassCtx *c, void *d_export, size_t cap) {
 }
 
 // one call of the step protocol: shard_mu + state_mu shared (+ the snapshot brought up to date when `fresh`)
-int ShardCall::begin(acl_engine *h_, bool fresh, bool need_reverse, bool combine_ok) {
+int ShardCall::begin(acl_engine *h_, bool fresh, bool need_reverse, bool combine_ok, bool need_subjects) {
     h = h_;
     if (h->store_only) return fail(ACL_ERR_UNAVAILABLE, "engine was opened store-only (no GPU): Check / LookupResources are unavailable");
     HIP_TRY(hipSetDevice(h->dev0().device));  // (the sharded entry points run on the first replica)
@@ -27,13 +27,14 @@ int ShardCall::begin(acl_engine *h_, bool fresh, bool need_reverse, bool combine
     have_mu = true;
     for (;;) {
         h->state_mu.lock_shared();
-        if (!fresh || snapshot_current(h, need_reverse)) {
+        if (!fresh || (snapshot_current(h, need_reverse) && (!need_subjects || subjects_current(h)))) {
             locked = true;
             break;
         }
         h->state_mu.unlock_shared();
         std::lock_guard<RwLock> lk(h->state_mu);
         int rc = need_reverse ? ensure_reverse(h) : ensure_snapshot(h);
+        if (rc == ACL_OK && need_subjects) rc = ensure_subjects(h);  // (a shard's subject rows: the transpose of the classes it holds)
         if (rc) return rc;
     }
     // Schemas with `&` / `-` / `.all()`: Check through the native loop (acl_shard_check_bulk: cells in per-shard ranges of one global cell space,

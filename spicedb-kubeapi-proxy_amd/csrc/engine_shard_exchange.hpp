@@ -1,0 +1,125 @@
+// engine_shard_exchange.hpp -- what the native sharded loops share (engine_shard_native.cpp: Check and LookupResources; engine_shard_subjects.cpp:
+// LookupSubjects): one batch's exchange machinery and the Check loop the lookups confirm their candidates with.
+#pragma once
+#include "engine_internal.hpp"
+
+namespace aclint {
+
+constexpr uint32_t kCtrlWords = 4;  // per level: total exported, any produced, overflow code, largest block
+
+// One batch's exchange machinery: buffers, the per-level "are entries expected?" plan, the collectives.
+//   headers  ALWAYS travel (16 bytes per peer): they carry the counts, the produced flag and the overflow code, so termination and
+//            retry decisions are taken on the device, identically on every shard;
+//   entries  travel only on levels the PLAN expects to export something.  The plan is the previous batch's record (the proxy's request
+//            streams repeat their shape: pods -> namespaces / groups cross shards on the first levels, nested groups stay on theirs): a
+//            fixed-capacity collective over world x cap entries per level was the price of deciding on the device, and most levels paid
+//            it for nothing.  A level that exports after all raises code 4 in every shard's control record and the batch is redone with
+//            entries on every level.
+struct Exchange {
+    acl_engine *h;
+    PassCtx *c;
+    const acl_shard_comm_t *comm;
+    uint32_t world, rank, cap = 0;
+    bool a2a = false;     // per-destination blocks through comm->all_to_all (Check only); else one block per shard through all_gather
+    acl_shard_bulk_stats_t *st;
+    std::vector<uint8_t> *plan;  // [level] 1 = exchange entries; empty = always
+
+    uint32_t nblk() const { return a2a ? world : 1u; }
+    // c->xcap is what a shard may export per level IN ALL: the all-gather form moves it whole to every shard, the all-to-all form cuts it into
+    // one block per destination -- `world` times fewer bytes on the wire for the same capacity
+    void size_blocks() { cap = a2a ? std::max<uint32_t>(8, c->xcap / world) : c->xcap; }
+    int alloc() {
+        HIP_TRY(c->d_xsend.ensure((size_t)nblk() * cap));
+        HIP_TRY(c->d_xrecv.ensure((size_t)world * cap));
+        HIP_TRY(c->d_xhsend.ensure(std::max<uint32_t>(world, 64)));
+        HIP_TRY(c->d_xhrecv.ensure(std::max<uint32_t>(world, 64)));
+        HIP_TRY(c->d_xctrl.ensure((size_t)kLevelSlots * kCtrlWords));
+        if (!c->h_xctrl.p) HIP_TRY(c->h_xctrl.ensure((size_t)kLevelSlots * kCtrlWords * sizeof(uint32_t)));
+        return ACL_OK;
+    }
+    DevShard shard() const {
+        DevShard sh = dev_shard(h, c, c->d_xsend.p, cap);
+        sh.by_dest = a2a ? 1u : 0u;
+        return sh;
+    }
+    bool wants_data(uint32_t it) const { return plan->empty() || it >= plan->size() || (*plan)[it]; }
+    // after iteration `it` wrote its exports: headers, (entries), import + control record.  `import`: (hdrs, data, have_data, ctrl)
+    template <typename Import>
+    int run(uint32_t it, Import import) {
+        const uint32_t *status = c->d_status.p;
+        launch_xhdr(c->stream, c->d_xhsend.p, nblk(), status + 2 * kLevelSlots + 1, status + kLevelSlots + it, status + 2 * kLevelSlots);
+        int rc = a2a ? comm->all_to_all(comm->user, c->d_xhsend.p, c->d_xhrecv.p, sizeof(uint4), (void *)c->stream)
+                     : comm->all_gather(comm->user, c->d_xhsend.p, c->d_xhrecv.p, sizeof(uint4), (void *)c->stream);
+        if (rc) return rc;
+        const bool data = wants_data(it);
+        if (data) {
+            rc = a2a ? comm->all_to_all(comm->user, c->d_xsend.p, c->d_xrecv.p, (size_t)cap * sizeof(uint4), (void *)c->stream)
+                     : comm->all_gather(comm->user, c->d_xsend.p, c->d_xrecv.p, (size_t)cap * sizeof(uint4), (void *)c->stream);
+            if (rc) return rc;
+            st->exchanged_bytes += (uint64_t)world * cap * sizeof(uint4);
+            st->data_exchanges++;
+        }
+        st->exchanged_bytes += (uint64_t)world * sizeof(uint4);
+        st->exchanges++;
+        import(c->d_xhrecv.p, c->d_xrecv.p, data, c->d_xctrl.p + (size_t)it * kCtrlWords);
+        return ACL_OK;
+    }
+    // reads the control records of iterations [first, last] (step 1 or 2) after a burst; returns 0 = go on, 1 = done at *done_at, 2 = redo
+    int settle(uint32_t first, uint32_t last, uint32_t step, uint32_t *done_at, uint32_t *redo_code, uint32_t *redo_max, std::vector<uint8_t> *seen) {
+        const uint32_t *hc = (const uint32_t *)c->h_xctrl.p;
+        for (uint32_t it = first; it <= last; it += step) {
+            const uint32_t *k = hc + (size_t)it * kCtrlWords;
+            st->entries_exchanged += k[0];
+            if (seen->size() <= it) seen->resize(it + 1, 0);
+            (*seen)[it] = k[0] ? 1 : 0;
+            if (k[2]) {  // some shard overflowed (frontier, export block, a row beyond the enumeration limit, the combine pools) or exported on a level planned without entries
+                *redo_code = (k[2] & 2u) ? 2u : (k[2] & kOverflowPools) ? kOverflowPools : (k[2] & 1u) ? 1u : 4u;
+                *redo_max = std::max(*redo_max, k[3]);
+                return 2;
+            }
+            if (k[0] == 0 && k[1] == 0) {
+                *done_at = it;
+                return 1;
+            }
+        }
+        return 0;
+    }
+    // every shard saw the same control records, so every shard grows the same things and redoes the batch
+    int grow(uint32_t redo_code, uint32_t redo_max, int attempt) {
+        if (redo_code == 2) return fail(ACL_ERR_RESOURCE_EXHAUSTED, "a relationship row exceeds the per-task enumeration limit");
+        st->retries++;
+        if (attempt > 8) return fail(ACL_ERR_RESOURCE_EXHAUSTED, "sharded frontier / export capacity exceeded after 8 retries");
+        c->stats.overflow_retries++;
+        if (redo_code == 4) {
+            plan->clear();  // exports where none were expected: entries on every level from now on
+            return ACL_OK;
+        }
+        if (redo_code == kOverflowPools) {  // a shard ran out of combine nodes / leaf cells: four times the pools (every shard alike)
+            c->shard_pool_shift += 2;
+            return ACL_OK;
+        }
+        if (redo_max > cap) {
+            uint32_t nc = cap;
+            while (nc < redo_max + redo_max / 4 && nc < (1u << 27)) nc <<= 1;
+            c->xcap = a2a ? (uint32_t)std::min<uint64_t>((uint64_t)nc * world, 1u << 30) : nc;  // (xcap = entries a shard may export per level in all)
+            return ACL_OK;
+        }
+        return alloc_frontier(h, c, c->frontier_entries * 4);
+    }
+};
+
+inline uint32_t first_xcap(PassCtx *c) {
+    if (!c->xcap) {
+        const char *e = getenv("ACL_SHARD_XCAP");  // test knob: a tiny first export block forces the grow-and-redo path
+        c->xcap = e && atoi(e) > 0 ? (uint32_t)std::max(8, atoi(e)) : 1u << 16;
+    }
+    return c->xcap;
+}
+
+// the native Check loop on context c (the caller holds the shard call's locks; engine_shard_native.cpp)
+int shard_check_core(acl_engine_t *h, PassCtx *c, const acl_shard_comm_t *comm, const void *d_items, size_t n, void *d_perm_out, void *d_err_out,
+                     acl_shard_bulk_stats_t *stats_out);
+// the built-in RCCL communicator of an engine after acl_shard_rccl_init (else ACL_ERR_FAILED_PRECONDITION, naming `who`)
+int shard_rccl_comm(acl_engine_t *h, const char *who, acl_shard_comm_t *out);
+
+}  // namespace aclint

@@ -13,15 +13,18 @@ namespace aclint {
 
 namespace {
 
-constexpr uint32_t kFreshSubject = 0xFFFFFFFCu;  // an id of the subject type that no relationship names (intern_check_item's unknown subject)
 constexpr uint32_t kSubjCapFirst = 1u << 14;     // log entries per block of the first attempt (128 KiB)
 constexpr uint32_t kSubjCapMax = 1u << 24;       // ... and at most (128 MiB): beyond, ACL_ERR_RESOURCE_EXHAUSTED
+
+}  // namespace
 
 int subjects_error(int32_t code, uint32_t rid, uint32_t sid) {
     const std::string who = sid == kFreshSubject ? std::string("the wildcard (a subject no relationship names)") : "subject id " + std::to_string(sid);
     return fail(code, std::string(code == ACL_ERR_DEPTH ? "LookupSubjects: max depth exceeded" : "LookupSubjects: a subject's check failed") + " while checking " + who +
                           " on resource id " + std::to_string(rid) + " (the permission holds an intersection / exclusion: reached subjects are confirmed by a forward Check)");
 }
+
+namespace {
 
 // one launch per group of resources: rows of `row_words` words into bitmaps (stride `words`), wildcard reached into wild[]
 int subjects_walk(acl_engine *h, PassCtx *c, uint32_t target, uint32_t key, const uint32_t *rids, size_t n, uint32_t *bitmaps, size_t words, size_t row_words,

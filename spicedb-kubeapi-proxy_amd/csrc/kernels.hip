@@ -2489,6 +2489,70 @@ __global__ __launch_bounds__(64) void k_xhdr(uint4 *hdr, uint32_t nblocks, const
     hdr[d] = make_uint4(exp_count[1 + d], flags, mx, tot);
 }
 
+// What the gathered imports share.  fold_headers: the own row's first wave folds all headers into the level's control record {total exported, any shard
+// produced, overflow code, largest block} (call with the first 64 threads of one block).  ImportOut: a wave's append cursor into the dynamic chunks of the
+// frontier iteration `iter` produced (the static chunks belong to that iteration's expand waves).
+__device__ __forceinline__ void fold_headers(const uint4 *__restrict__ hdrs, uint32_t world, uint32_t cap, uint32_t have_data, uint32_t *ctrl, uint32_t lane) {
+    uint32_t total = 0, anyp = 0, over = 0, mx = 0;
+    for (uint32_t r = lane; r < world; r += 64) {
+        const uint4 h = hdrs[r];
+        total += h.w;
+        anyp |= h.y & 1u;
+        over |= (h.y >> 1) | (h.z > cap ? 1u : 0u) | ((!have_data && h.w) ? 4u : 0u);  // (h.w, every shard's own included: the same verdict on every shard)
+        mx = max(mx, h.z);
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        total += (uint32_t)__shfl_xor((int)total, d, 64);
+        anyp |= (uint32_t)__shfl_xor((int)anyp, d, 64);
+        over |= (uint32_t)__shfl_xor((int)over, d, 64);
+        mx = max(mx, (uint32_t)__shfl_xor((int)mx, d, 64));
+    }
+    if (lane == 0) {
+        ctrl[0] = total;
+        ctrl[1] = anyp;
+        ctrl[2] = over;
+        ctrl[3] = mx;
+    }
+}
+struct ImportOut {
+    uint4 *__restrict__ out;
+    uint32_t *counts, *nchunks, *overflow, *any;
+    uint32_t nwaves, max_chunks;
+    uint32_t cur = kNoSpace, fill = kChunk, produced = 0;
+    __device__ __forceinline__ ImportOut(const DevFrontier &f, uint32_t iter)
+        : out(f.buf[iter & 1u]), counts(f.counts[iter & 1u]), nchunks(f.nchunks + iter), overflow(f.overflow), any(f.any + iter), nwaves(f.nwaves), max_chunks(f.max_chunks) {}
+    // appends the flagged lanes' entries (wave-uniform control flow); false: the frontier is out of chunks (overflow raised), stop
+    __device__ __forceinline__ bool append(bool mine, const uint4 &e, uint32_t lane) {
+        const uint64_t b = __ballot(mine);
+        if (!b) return true;
+        const uint32_t need = (uint32_t)__popcll(b);
+        if (fill + need > kChunk) {
+            if (lane == 0 && cur != kNoSpace) counts[cur] = fill;
+            uint32_t c = 0;
+            if (lane == 0) c = atomicAdd(nchunks, 1u);
+            c = uniform(c) + nwaves;
+            if (c >= max_chunks) {
+                if (lane == 0) *overflow = 1u;
+                cur = kNoSpace;
+                return false;
+            }
+            cur = c;
+            fill = 0;
+        }
+        if (mine) out[(size_t)cur * kChunk + fill + lanes_below(b)] = e;
+        fill += need;
+        produced += need;
+        return true;
+    }
+    __device__ __forceinline__ void close(uint32_t lane) {
+        if (lane == 0) {
+            if (cur != kNoSpace) counts[cur] = fill;
+            if (produced) *any = 1u;
+        }
+    }
+};
+
 // After the exchange: blockIdx.y = source shard.  Rows of other shards import what they sent (FWD: the entries whose slot this shard owns;
 // reverse: foreign states for which this shard holds parent rows), the count read from the source's header; the own row's first wave folds all
 // headers into the level's control record {total exported, any shard produced, overflow code, largest block} -- identical on every shard, so
@@ -2501,68 +2565,22 @@ __global__ __launch_bounds__(256) void k_import_gathered(DevFrontier f, uint32_t
     const uint32_t lane = lane_id();
     const uint32_t src = blockIdx.y;
     if (src == rank) {
-        if (blockIdx.x == 0 && threadIdx.x < 64) {
-            uint32_t total = 0, anyp = 0, over = 0, mx = 0;
-            for (uint32_t r = lane; r < world; r += 64) {
-                const uint4 h = hdrs[r];
-                total += h.w;
-                anyp |= h.y & 1u;
-                over |= (h.y >> 1) | (h.z > cap ? 1u : 0u) | ((!have_data && h.w) ? 4u : 0u);  // (h.w, every shard's own included: the same verdict on every shard)
-                mx = max(mx, h.z);
-            }
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) {
-                total += (uint32_t)__shfl_xor((int)total, d, 64);
-                anyp |= (uint32_t)__shfl_xor((int)anyp, d, 64);
-                over |= (uint32_t)__shfl_xor((int)over, d, 64);
-                mx = max(mx, (uint32_t)__shfl_xor((int)mx, d, 64));
-            }
-            if (lane == 0) {
-                ctrl[0] = total;
-                ctrl[1] = anyp;
-                ctrl[2] = over;
-                ctrl[3] = mx;
-            }
-        }
+        if (blockIdx.x == 0 && threadIdx.x < 64) fold_headers(hdrs, world, cap, have_data, ctrl, lane);
         return;
     }
     if (!have_data) return;
     const uint4 *__restrict__ in = data + (size_t)src * cap;
     const uint32_t n = min(hdrs[src].x, cap);
     const uint32_t wave = blockIdx.x * 4 + (threadIdx.x >> 6), nw = gridDim.x * 4;
-    uint4 *__restrict__ out = f.buf[iter & 1u];
-    uint32_t *out_counts = f.counts[iter & 1u];
-    uint32_t *out_nchunks = f.nchunks + iter;
-    uint32_t cur = kNoSpace, fill = kChunk, produced = 0;
+    ImportOut io(f, iter);
     for (uint32_t x = wave; (uint64_t)x * 64 < n; x += nw) {
         const uint32_t i = x * 64 + lane;
         const uint4 e = i < n ? in[i] : make_uint4(0, 0, kDeadMeta, 0);
         bool mine = i < n && e.z != kDeadMeta;
         if (mine) mine = FWD ? progs[meta_slot(e.z)].owner == rank : (rprogs[e.z & 0x1FFFu].n & ~kRevRemoteBit) != 0;
-        const uint64_t b = __ballot(mine);
-        if (!b) continue;
-        const uint32_t need = (uint32_t)__popcll(b);
-        if (fill + need > kChunk) {
-            if (lane == 0 && cur != kNoSpace) out_counts[cur] = fill;
-            uint32_t c = 0;
-            if (lane == 0) c = atomicAdd(out_nchunks, 1u);
-            c = uniform(c) + f.nwaves;
-            if (c >= f.max_chunks) {
-                if (lane == 0) *f.overflow = 1u;
-                cur = kNoSpace;
-                break;
-            }
-            cur = c;
-            fill = 0;
-        }
-        if (mine) out[(size_t)cur * kChunk + fill + lanes_below(b)] = e;
-        fill += need;
-        produced += need;
+        if (!io.append(mine, e, lane)) break;
     }
-    if (lane == 0) {
-        if (cur != kNoSpace) out_counts[cur] = fill;
-        if (produced) f.any[iter] = 1u;
-    }
+    io.close(lane);
 }
 
 }  // namespace
@@ -3016,6 +3034,269 @@ void launch_subj_local(hipStream_t s, const DevSubjects &g, const uint32_t *rids
     const size_t dyn = (prog_lds ? prog_bytes : 0u) + (size_t)lds_words * 4u;
     hipLaunchKernelGGL(k_subj_local, dim3(n), dim3(kSubjThreads), dyn, s, g, rids, target_slot, key, (uint2 *)logs, cap, visited, rows, row_words, lds_words, prog_lds,
                        flags_out, status);
+}
+
+// ---- LookupSubjects, level-synchronous: k_subj_expand (the sharded graph's native loop, engine_shard_subjects.cpp).  One launch = one dispatch level of ALL
+// lookups of a chunk on all CUs, over the chunked frontier of k_expand / k_rev_expand.  Entry: x = object id, y = lookup index, z = slot | level << 16 |
+// kSubjMarked, w = 0.  The emission rules and the depth arithmetic per op are k_subj_local's; what differs is WHEN a visit is decided.  There, unmarked
+// entries of level L decide behind a block barrier that follows every append of level L - 1.  Here other blocks (and other shards) are still appending, so
+// every decision for a level-L state is taken while iteration L - 1 runs: where an L - 1 state's direct child is appended, where an entry that becomes due
+// next is carried over, and where an exchanged entry is imported.  Entries of later levels travel unmarked.  Every visited bit set during iteration L - 1
+// therefore belongs to level L, and a state still counts at the least level that reaches it -- across blocks and across shards (the bits live on the shard
+// that owns the slot's type, and only there).  Iteration L reads: marked entries of level L (expanded), unmarked entries of levels > L (carried).
+namespace {
+__device__ __forceinline__ bool subj_first_visit(const DevSubjLevel &s, uint32_t req, uint32_t slot, uint32_t id) {
+    const uint32_t vb = s.g.slot_vbase[slot];
+    if (vb == kSubjNoBits) return true;  // (nothing produces this slot's states: a lookup's own root)
+    if (id >= s.g.slot_vn[slot]) return false;
+    const uint32_t m = 1u << (id & 31u);
+    // agent scope: the blocks of a launch sit on different XCDs, whose L2s are not coherent for anything less
+    return !(__hip_atomic_fetch_or(s.visited + (size_t)req * s.g.visited_words + vb + (id >> 5), m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & m);
+}
+// wave-cooperative append of the flagged lanes' entries to the frontier iteration `iter` produces (wave-uniform control flow)
+__device__ __forceinline__ void subj_append(WaveOut &wo, uint32_t lane, bool push, uint32_t id, uint32_t req, uint32_t z) {
+    const uint64_t b = __ballot(push);
+    if (!b) return;
+    const uint32_t base = reserve<false>(wo, (uint32_t)__popcll(b), lane);
+    if (push && base != kNoSpace) wo.buf[base + lanes_below(b)] = make_uint4(id, req, z, 0u);
+}
+// child state (slot, id) of lookup `req` at level lvl, produced while level `iter` is expanded: to the owner of the slot's type when that is another shard
+// (unmarked: the importer decides), else into the next frontier -- its visit decided here when it is due next
+template <bool SHARDED>
+__device__ __forceinline__ void subj_child(const DevSubjLevel &s, WaveOut &wo, const DevShard &sh, uint32_t iter, uint32_t lane, bool valid, uint32_t id, uint32_t req,
+                                           uint32_t slot, uint32_t lvl) {
+    uint32_t z = slot | (lvl << 16);
+    bool local = valid;
+    if (SHARDED) {
+        const uint32_t owner = valid ? s.g.progs[slot].owner : sh.rank;
+        local = valid && owner == sh.rank;
+        export_entries(valid && owner != sh.rank, make_uint4(id, req, z, 0u), owner, lane, sh);
+    }
+    bool push = local;
+    if (local && lvl == iter + 1u) {
+        push = subj_first_visit(s, req, slot, id);
+        z |= kSubjMarked;
+    }
+    subj_append(wo, lane, push, id, req, z);
+}
+}  // namespace
+
+// lookup i of the chunk starts from resource rids[i] of `target_slot`, on the shard that owns the slot's type; also resets the status block (as k_rev_seed)
+__global__ __launch_bounds__(256) void k_subj_seed(DevSubjLevel s, DevFrontier f, const uint32_t *__restrict__ rids, uint32_t n, uint32_t target_slot, DevShard sh) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t need = (n + kChunk - 1) / kChunk;
+    const uint32_t readable = max(need, f.nwaves);
+    if (i < kStatusWords) f.nchunks[i] = i == 0 ? (need > f.nwaves ? need - f.nwaves : 0u) : (i == kLevelSlots ? (n ? 1u : 0u) : 0u);
+    if (i < readable) f.counts[0][i] = i < need ? min(kChunk, n - i * kChunk) : 0u;
+    if (i >= n) return;
+    const uint32_t id = rids[i];
+    bool mine = sh.world <= 1u || s.g.progs[target_slot].owner == sh.rank;
+    if (mine) mine = subj_first_visit(s, i, target_slot, id);  // (an id beyond the visited bits: no walk, as k_subj_local)
+    f.buf[0][i] = make_uint4(id, i, mine ? (target_slot | (1u << 16) | kSubjMarked) : kDeadMeta, 0u);
+}
+
+template <bool SHARDED>
+__global__ __launch_bounds__(kBlock) void k_subj_expand(DevSubjLevel s, DevFrontier f, uint32_t iter, DevShard sh) {
+    __shared__ WaveOutCold s_cold[kWavesPerBlock];
+    __shared__ uint32_t s_slots[kWavesPerBlock][128];
+    const uint32_t lane = lane_id();
+    const uint32_t wib = uniform(threadIdx.x >> 6);
+    const uint32_t wave = blockIdx.x * kWavesPerBlock + wib, nwaves = f.nwaves;
+    const uint32_t pin = (iter + 1) & 1u;
+    const uint32_t *__restrict__ in_counts = f.counts[pin];
+    const bool live = !*f.overflow && f.any[iter - 1];
+    const uint32_t C = live ? nwaves + min(f.nchunks[iter - 1], f.max_chunks - nwaves) : 0u;
+    WaveOut wo = chunked_out(f, iter, wave, &s_cold[wib], lane);
+    uint32_t *slots = s_slots[wib];
+    ChunkWalk cw{f.buf[pin], lane, slots, 0ull};
+    const DevSubjects &g = s.g;
+    const bool rel_key = s.key < g.nslots;  // the subject carries a relation: REFLEX ops count
+    const uint32_t nbits = s.row_words * 32u;
+    const uint2 *__restrict__ meta2 = reinterpret_cast<const uint2 *>(g.meta);
+    const uint2 *__restrict__ smeta2 = reinterpret_cast<const uint2 *>(g.smeta);
+    // segment-major work order: k_expand's ChunkWalk (the fill counts of the wave's next 64 segment slots in one gather)
+    const uint32_t nslot = C * kSegsPerChunk;
+    for (uint32_t x0 = wave; x0 < nslot; x0 += 64 * nwaves) {
+        const uint32_t xl = x0 + lane * nwaves;
+        uint32_t lat = 0, lcnt = 0;
+        if (xl < nslot) {
+            const uint32_t ls = xl / C, lc = (xl % C + ls * 509u) % C;
+            lcnt = in_counts[lc];
+            lcnt = lcnt > ls * 64 ? lcnt - ls * 64 : 0u;  // entries of this slot's segment and beyond
+            lat = lc * kChunk + ls * 64;
+        }
+        wave_lds_fence();  // (the previous round's readers are done)
+        slots[lane] = lat;
+        slots[64 + lane] = lcnt;
+        cw.work = __ballot(lcnt != 0);
+        wave_lds_fence();
+        while (cw.work) {
+            const int wl = __ffsll((unsigned long long)cw.work) - 1;
+            cw.take();
+            uint4 e;
+            bool valid;
+            cw.load(wl, e, valid);
+            if (!valid) e.z = kDeadMeta;
+            const uint32_t id = e.x, req = e.y, z = e.z;
+            const bool act = valid && z != kDeadMeta;
+            const uint32_t slot = z & 0xFFFFu, level = (z >> 16) & 63u;
+            {  // entries of later levels move on; the ones due next decide their visit now
+                const bool later = act && level > iter;
+                bool push = later;
+                uint32_t nz = z & ~kSubjMarked;
+                if (later && level == iter + 1u) {
+                    push = subj_first_visit(s, req, slot, id);
+                    nz |= kSubjMarked;
+                }
+                subj_append(wo, lane, push, id, req, nz);
+            }
+            const bool expand = act && level == iter;  // (marked: its visit was decided during the iteration before)
+            SlotProg p{};
+            if (expand) p = g.progs[slot];
+            const uint32_t nops = expand ? (rel_key ? p.n_total : p.n_main) : 0u;
+            const uint32_t maxops = wave_max(nops);
+            for (uint32_t j = 0; j < maxops; j++) {
+                uint32_t deg = 0, start = 0, tag = 0, one_slot = 0, one_lvl = 0;
+                bool one_child = false, one_emit = false;
+                if (j < nops && !(g.sops[p.first + j].flags & kSubjSkip)) {
+                    const FwdOp op = g.ops[p.first + j];
+                    const uint32_t L = level + op.dlevel;
+                    if (L <= kMaxLevels) {
+                        if (op.flags & OP_REFLEX) {
+                            one_emit = op.key == s.key;
+                        } else if (op.flags & OP_PUSH_SAME) {
+                            if (L + 1u <= kMaxLevels) {
+                                one_child = true;
+                                one_slot = op.key;
+                                one_lvl = L + 1u;
+                            }
+                        } else if (op.flags & OP_PROBE_HASH) {
+                            const SubjOp so = g.sops[p.first + j];
+                            if (op.key == s.key && id < so.nrows) {
+                                const uint2 rd = smeta2[so.base + id];
+                                if (rd.y > rd.x) {
+                                    if (op.flags & OP_WILD) s.flags[req] = 1;
+                                    else if (rd.y - rd.x > kSubjMaxRow) *f.overflow = 2u;
+                                    else {
+                                        start = rd.x;
+                                        deg = rd.y - rd.x;
+                                        tag = kSubjEmitIds;
+                                    }
+                                }
+                            }
+                        } else if (id < op.nrows) {
+                            const uint2 md = meta2[op.base + id * op.K + op.k];
+                            if (md.y > md.x) {
+                                const bool probe = (op.flags & OP_PROBE) && op.key == s.key;
+                                const bool enm = (op.flags & OP_ENUM) && L + 1u <= kMaxLevels;
+                                if (md.y - md.x > kSubjMaxRow) {
+                                    if (probe || enm) *f.overflow = 2u;
+                                } else if (enm) {
+                                    start = md.x;
+                                    deg = md.y - md.x;
+                                    tag = kSubjChild | ((L + 1u) << 16) | op.key;
+                                } else if (probe) {
+                                    start = md.x;
+                                    deg = md.y - md.x;
+                                    tag = kSubjEmitEdges;
+                                }
+                            }
+                        }
+                    }
+                }
+                // the state itself is the subject (REFLEX): the lanes hold different lookups, so each ORs its own bit
+                if (one_emit && id < nbits)
+                    __hip_atomic_fetch_or(s.rows + (size_t)req * s.row_words + (id >> 5), 1u << (id & 31u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                subj_child<SHARDED>(s, wo, sh, iter, lane, one_child, id, req, one_slot, one_lvl);
+                // rows: the wave walks one lane's row at a time, consecutive lanes on consecutive ids (coalesced; ascending ids fold in subj_mark)
+                uint64_t todo = __ballot(deg != 0);
+                while (todo) {
+                    const int src = __ffsll((unsigned long long)todo) - 1;
+                    todo &= todo - 1;
+                    const uint32_t tstart = (uint32_t)__builtin_amdgcn_readlane((int)start, src), tdeg = (uint32_t)__builtin_amdgcn_readlane((int)deg, src);
+                    const uint32_t ttag = (uint32_t)__builtin_amdgcn_readlane((int)tag, src), treq = (uint32_t)__builtin_amdgcn_readlane((int)req, src);
+                    const uint32_t kind = ttag & (3u << 30);
+                    uint32_t *row = s.rows + (size_t)treq * s.row_words;
+                    for (uint32_t o = 0; o < tdeg; o += 64) {
+                        const bool v = o + lane < tdeg;
+                        const uint32_t pos = tstart + (v ? o + lane : 0u);
+                        const uint32_t val = kind == kSubjEmitIds ? gld(g.sids, pos) : (gld(g.edges, pos) & kIdMask);
+                        if (kind != kSubjChild) subj_mark(row, false, val, v, nbits, lane);
+                        else subj_child<SHARDED>(s, wo, sh, iter, lane, v, val, treq, ttag & 0xFFFFu, (ttag >> 16) & 63u);
+                    }
+                }
+            }
+        }
+    }
+    if (lane == 0) {
+        if (wo.cur != kNoSpace) wo.cold->counts[wo.cur] = wo.fill;
+        if (wo.produced) f.any[iter] = 1u;
+    }
+}
+
+// After the exchange (k_import_gathered's shape: blockIdx.y = source shard; the own row's first wave folds the headers into the level's control record).
+// Keeps the gathered entries whose slot this shard owns and appends them to the frontier iteration `iter` produced; an entry that is due next decides its
+// visit here -- on its owner, in the same iteration as every other decision for that level.
+__global__ __launch_bounds__(256) void k_subj_import_gathered(DevSubjLevel s, DevFrontier f, uint32_t iter, const uint4 *__restrict__ hdrs, const uint4 *__restrict__ data,
+                                                              uint32_t world, uint32_t rank, uint32_t cap, uint32_t have_data, uint32_t *ctrl) {
+    const uint32_t lane = lane_id();
+    const uint32_t src = blockIdx.y;
+    if (src == rank) {
+        if (blockIdx.x == 0 && threadIdx.x < 64) fold_headers(hdrs, world, cap, have_data, ctrl, lane);
+        return;
+    }
+    if (!have_data) return;
+    const uint4 *__restrict__ in = data + (size_t)src * cap;
+    const uint32_t n = min(hdrs[src].x, cap);
+    const uint32_t wave = blockIdx.x * 4 + (threadIdx.x >> 6), nw = gridDim.x * 4;
+    ImportOut io(f, iter);
+    for (uint32_t x = wave; (uint64_t)x * 64 < n; x += nw) {
+        const uint32_t i = x * 64 + lane;
+        uint4 e = i < n ? in[i] : make_uint4(0, 0, kDeadMeta, 0);
+        bool mine = i < n && e.z != kDeadMeta;
+        const uint32_t slot = e.z & 0xFFFFu;
+        if (mine) mine = slot < s.g.nslots && s.g.progs[slot].owner == rank;
+        if (mine && ((e.z >> 16) & 63u) == iter + 1u) {
+            mine = subj_first_visit(s, e.y, slot, e.x);
+            e.z |= kSubjMarked;
+        }
+        if (!io.append(mine, e, lane)) break;
+    }
+    io.close(lane);
+}
+
+// result rows: ORs the `world` gathered partial rows ([world][m][row_words]) into out[m][out_stride]; the words behind row_words are zeroed.  (Several
+// shards set different bits of one byte -- pod#creator on pod's shard, group#member on group's -- so a byte-wise max would not do.)
+__global__ __launch_bounds__(256) void k_subj_fold(const uint32_t *__restrict__ gathered, uint32_t world, uint32_t m, uint32_t row_words, uint32_t *out,
+                                                   uint32_t out_stride) {
+    const size_t total = (size_t)m * out_stride, part = (size_t)m * row_words;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t r = i / out_stride;
+        const uint32_t w = (uint32_t)(i - r * out_stride);
+        uint32_t v = 0;
+        if (w < row_words)
+            for (uint32_t k = 0; k < world; k++) v |= gathered[k * part + r * row_words + w];
+        out[i] = v;
+    }
+}
+
+void launch_subj_seed(hipStream_t st, const DevSubjLevel &s, const DevFrontier &f, const uint32_t *rids, uint32_t n, uint32_t target_slot, const DevShard &sh) {
+    const uint32_t threads = std::max(std::max(n, f.nwaves), kStatusWords);
+    hipLaunchKernelGGL(k_subj_seed, dim3((threads + 255) / 256), dim3(256), 0, st, s, f, rids, n, target_slot, sh);
+}
+void launch_subj_expand(hipStream_t st, const DevSubjLevel &s, const DevFrontier &f, uint32_t iter, const DevShard &sh) {
+    const dim3 grid(f.nwaves / kWavesPerBlock);
+    with_flag(sh.world > 1, [&](auto sharded) { hipLaunchKernelGGL((k_subj_expand<sharded()>), grid, dim3(kBlock), 0, st, s, f, iter, sh); });
+}
+void launch_subj_import_gathered(hipStream_t st, const DevSubjLevel &s, const DevFrontier &f, uint32_t iter, const uint4 *hdrs, const uint4 *data, uint32_t world,
+                                 uint32_t rank, uint32_t cap, bool have_data, uint32_t *ctrl) {
+    const uint32_t bx = have_data ? std::max<uint32_t>(1, std::min<uint32_t>(64, (cap + 4095) / 4096)) : 1u;
+    hipLaunchKernelGGL(k_subj_import_gathered, dim3(bx, world), dim3(256), 0, st, s, f, iter, hdrs, data, world, rank, cap, have_data ? 1u : 0u, ctrl);
+}
+void launch_subj_fold(hipStream_t st, const uint32_t *gathered, uint32_t world, uint32_t m, uint32_t row_words, uint32_t *out, uint32_t out_stride) {
+    const size_t total = (size_t)m * out_stride;
+    if (!total) return;
+    hipLaunchKernelGGL(k_subj_fold, dim3((uint32_t)std::min<size_t>((total + 255) / 256, 4096)), dim3(256), 0, st, gathered, world, m, row_words, out, out_stride);
 }
 
 }  // namespace acl

@@ -182,6 +182,25 @@ struct DevSubjects {
 constexpr uint32_t kSubjLdsProgBytes = 16u << 10;  // programs + ops + side table staged in LDS up to this size
 void launch_subj_local(hipStream_t s, const DevSubjects &g, const uint32_t *rids, uint32_t n, uint32_t target_slot, uint32_t key, void *logs, uint32_t cap,
                        uint32_t *visited, uint32_t *rows, uint32_t row_words, uint32_t *flags_out, uint32_t *status);
+// level-synchronous LookupSubjects (kernels.hip k_subj_expand; the sharded graph's native loop): one launch per dispatch level over the chunked frontier, all
+// lookups of a chunk at once.  visited: [m][g.visited_words], rows: this shard's PARTIAL rows [m][row_words], flags: [m] bytes (1: a `T:*` row was reached) --
+// all zeroed by the caller.  A row beyond the per-task enumeration limit raises overflow code 2 in the frontier's status block.
+struct DevSubjLevel {
+    DevSubjects g;
+    uint32_t *visited;
+    uint32_t *rows;
+    uint8_t *flags;
+    uint32_t row_words;
+    uint32_t key;  // the subjects' class
+};
+// seeds (lookup i starts from rids[i] of target_slot, on the shard that owns the slot's type) + the status block
+void launch_subj_seed(hipStream_t s, const DevSubjLevel &g, const DevFrontier &f, const uint32_t *rids, uint32_t n, uint32_t target_slot, const DevShard &sh);
+void launch_subj_expand(hipStream_t s, const DevSubjLevel &g, const DevFrontier &f, uint32_t iter, const DevShard &sh);
+// as launch_import_gathered: keeps the exchanged entries whose slot this shard owns (deciding the visits of the ones due next) + the level's control record
+void launch_subj_import_gathered(hipStream_t s, const DevSubjLevel &g, const DevFrontier &f, uint32_t iter, const uint4 *hdrs, const uint4 *data, uint32_t world,
+                                 uint32_t rank, uint32_t cap, bool have_data, uint32_t *ctrl);
+// out[m][out_stride] = OR over the `world` gathered partial rows [world][m][row_words] (words behind row_words: zero)
+void launch_subj_fold(hipStream_t s, const uint32_t *gathered, uint32_t world, uint32_t m, uint32_t row_words, uint32_t *out, uint32_t out_stride);
 // blocks per expand launch for this device (all co-resident); nwaves = blocks * kWavesPerBlock
 int expand_grid_blocks(int device);
 

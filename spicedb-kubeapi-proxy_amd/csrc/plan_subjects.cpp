@@ -113,6 +113,32 @@ void build_subjects(Store &store, int64_t now, const Snapshot &s, SubjectRows *o
     std::vector<uint8_t> child(sc.nslots, 0);
     for (const FwdOp &op : s.ops)
         if ((op.flags & (OP_ENUM | OP_PUSH_SAME)) && op.key < (uint32_t)sc.nslots) child[op.key] = 1;
+    // A shard's programs hold row ops only for the types it owns, but its states are also the children of rows on OTHER shards (pod#viewer@group#member
+    // lives with `pod`, the group#member states it produces with `group`): there the producers are read off the schema -- the userset classes and the
+    // arrows of every definition, which is what the owners' programs enumerate (computed usersets stay on their own object, hence on its shard).
+    bool sharded = false;
+    for (uint32_t o : s.type_owner) sharded = sharded || o != s.type_owner[0];
+    if (sharded) {
+        std::vector<std::pair<int, const Node *>> todo;
+        for (size_t t = 0; t < sc.defs.size(); t++)
+            for (const Member &m : sc.defs[t].members) {
+                if (m.is_permission) todo.push_back({(int)t, &m.expr});
+                for (const SubjectClass &c : m.classes)
+                    if (c.srel != kNoRelation) child[sc.slot(c.stype, c.srel)] = 1;
+            }
+        while (!todo.empty()) {
+            const auto [t, n] = todo.back();
+            todo.pop_back();
+            for (const Node &k : n->kids) todo.push_back({t, &k});
+            if (n->kind != Node::kArrow && n->kind != Node::kArrowAll) continue;
+            const int ts = sc.defs[t].find(n->a);
+            if (ts < 0) continue;
+            for (const SubjectClass &c : sc.defs[t].members[ts].classes) {
+                const int tm = sc.defs[c.stype].find(n->b);
+                if (tm >= 0) child[sc.slot(c.stype, tm)] = 1;
+            }
+        }
+    }
     uint64_t words = 0;
     for (int slot = 0; slot < sc.nslots; slot++) {
         if (!child[slot]) continue;

@@ -468,6 +468,9 @@ struct acl_engine {
     DevGraph dev_graph(const DevState &d) const {
         DevGraph g{d.d_meta.p, d.d_edges.p, d.d_buckets.p, d.d_ops.p, d.d_progs.p, d.d_tsb.p, d.d_tnm.p, snap.nslots, snap.ntypes, (uint32_t)snap.ops.size()};
         g.walk_flags = walk_no_direct.load(std::memory_order_relaxed) ? kWalkNoDirect : 0u;
+        g.hot_cbase = snap.hot_cbase;
+        g.hot_cnrows = snap.hot_cnrows;
+        g.hot_ckey = snap.hot_ckey;
         return g;
     }
     DevGraph dev_graph(const PassCtx *c) const { return dev_graph(*c->dev); }

@@ -17,6 +17,8 @@
 //     their task list with the prefix sums taken in registers (the direct form, round 5); simple_steps expands the tasks kSimpleWidth
 //     children per lane and step; flush_probes handles arrow-target states.
 //   Loads are pinned into trips (issue_fence): all loads of a trip are issued before the first of them is waited for.
+//   What a wave pays for is the vector-memory INSTRUCTION, not the lane or the byte (profiles/vmem_per_pair_ab.txt): the subject's row descriptor of the hot hashed
+//   class is fetched once per request (LDS), and an expansion's last step is only as wide as its children.
 // Two drivers call it:
 //   k_check_local  ONE launch per batch: a block walks its share of the requests through every level inside a block-private
 //                  frontier region (LDS cursors, one barrier per level).  The default for every batch size.
@@ -105,7 +107,7 @@ __device__ __forceinline__ uint32_t wave_max(uint32_t v) {  // same network with
 #endif
 enum { PH_OTHER = 0, PH_ENTRIES, PH_GATHERS, PH_TASKS, PH_PROLOGUE, PH_EDGES, PH_BUCKETS, PH_PUSH, PH_GENERIC, PH_BARRIER, PH_SEED, PH_COUNT };
 #if ACL_PROFILE_PHASES
-__device__ unsigned long long acl_phase_cycles[16];
+__device__ unsigned long long acl_phase_cycles[18];
 #define ACL_MARK(wo, ph)                                                                  \
     do {                                                                                  \
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                       \
@@ -149,7 +151,7 @@ struct WaveOutCold {  // what only the chunk switch / overflow paths need: kept 
     uint32_t *counts, *nchunks, *overflow;
     uint32_t nwaves, max_chunks, cap;
 #if ACL_PROFILE_PHASES
-    uint32_t last, prof[16];
+    uint32_t last, prof[18];  // [0, PH_COUNT): phase cycles; [12, 18): counters (process_segment, simple_step)
 #endif
 };
 struct WaveOut {
@@ -159,6 +161,7 @@ struct WaveOut {
     uint32_t *lfill;    // LOCAL: the block's output cursor (LDS) -- the block's waves append to one region
     uint32_t first;     // LOCAL: first request of the unit being walked (8-byte entries hold the request's index inside the unit)
     uint32_t lcap;      // LOCAL: entries of the block's region (a kernel constant: kept here, not behind an LDS read per reservation)
+    const uint2 *ssd;   // LOCAL, 8-byte entries: the unit's requests' row descriptors of the hot hashed class (LDS, k_check_local's s_sd)
 };
 // room for `need` (<= kChunk) consecutive entries; returns the first entry index
 template <bool LOCAL>
@@ -414,10 +417,6 @@ __device__ __forceinline__ bool eval_child(const DevGraph &g, const SlotProg *pr
                             // block = 6 per SIMD = room for 72 VGPRs without a spill (rounds 2-4: 2 at 64 VGPRs and 8 waves per SIMD); profiles/r05_ab_block_shape.txt
 #endif
 constexpr int kSimpleWidth = ACL_SIMPLE_WIDTH;  // children per lane whose buckets are in flight together
-#ifndef ACL_EDGES_AHEAD
-#define ACL_EDGES_AHEAD 3  // = the width (6 = both windows' edges in one trip: 1 us better on C4, 3.5 us worse on the 100 M-relationship replica)
-#endif
-constexpr int kEdgesAhead = ACL_EDGES_AHEAD;    // children per lane whose edges are fetched in one trip
 // Returns a bit mask of the 64-task rounds it did NOT handle (the caller expands those the generic way): a round whose rows
 // together exceed the head-bit window (a row of thousands of ids) or with a task at the dispatch-depth limit.
 //
@@ -434,128 +433,140 @@ constexpr int kEdgesAhead = ACL_EDGES_AHEAD;    // children per lane whose edges
 // item, t.heads = one bit per task at its first work item (set by the caller's prologue).  UM: every child carries the same meta `umeta`, the
 // entries are 8-byte ones (no per-task meta / subject id reads at the push) and t.a[j].w is the request's index INSIDE the unit (the answer-byte
 // accesses and the entry's y word without their subtractions).
+// One step: N (<= kSimpleWidth) windows of 64 children from work item w0 on.  Their edges go out in one trip (one VGPR each), then their buckets
+// (8 VGPRs per child).  What the walk's time follows is the number of vector-memory INSTRUCTIONS its waves issue, whatever the number of lanes
+// that need them (profiles/r04_bucket_gather_sensitivity.txt, r06_ab_check_local.txt `warm`): a window without a valid lane costs what a full one
+// costs, so the LAST step of an expansion is instantiated only as wide as its children (simple_steps) -- every body keeps the shape: all edge loads,
+// fence, all bucket loads, fence, compares, stores behind the last compare.
+template <bool LOCAL, bool E8, bool UM, int N>
+__device__ __forceinline__ void simple_step(TaskLds &t, uint32_t w0, uint32_t total, uint32_t &before, WaveOut &wo, uint32_t lane, const uint32_t *__restrict__ edges,
+                                            const uint4 *__restrict__ buckets, uint8_t *has, uint8_t *err, uint32_t umeta) {
+    bool valid[N];
+    uint32_t tj[N], edge[N];
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+        const uint32_t win = (w0 >> 6) + (uint32_t)k;
+        const uint64_t hw = win < kHeadWords ? t.heads[win] : 0ull;
+        const uint32_t hlo = uniform((uint32_t)hw), hhi = uniform((uint32_t)(hw >> 32));
+        const uint32_t w = w0 + 64u * k + lane;
+        valid[k] = w < total;
+        const uint32_t wv = valid[k] ? w : total - 1;  // inactive lanes shadow the last child: every load stays in range
+        // tasks starting at or before this lane's work item, minus one (beyond `total` there are no head bits: the last task)
+        // (the lane's own head bit straight from the uniform mask -- inverse ballot: the mask IS the condition register; `(hw >> lane) & 1` is a 64-bit
+        //  vector shift, quarter rate, plus an AND per child window)
+        const uint32_t own = __builtin_amdgcn_inverse_ballot_w64(((uint64_t)hhi << 32) | hlo) ? 1u : 0u;
+        const uint32_t j = before + __builtin_amdgcn_mbcnt_hi(hhi, __builtin_amdgcn_mbcnt_lo(hlo, 0u)) + own - 1u;
+        before += (uint32_t)__popc(hlo) + (uint32_t)__popc(hhi);
+        tj[k] = j;
+        edge[k] = gld(edges, t.a[j].x + wv);
+    }
+    issue_fence();  // trip 1: every edge of the step
+    ACL_MARK(wo, PH_EDGES);
+    uint4 p[N];
+    uint32_t rq[N];
+    uint32_t slow = 0u;
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+        const uint4 ta = t.a[tj[k]];  // the child's task: {edge base, first bucket, the row's y (buckets | two-choice | seed), request} in one 16-byte read
+        rq[k] = ta.w;
+        // (hrow_fast: full-rate arithmetic, in range for EVERY row and right for all but the slow ones -- those are redone below)
+        p[k] = gld(buckets, ta.y + hrow_fast(edge[k] & kIdMask, ta.z));
+        slow |= ta.z;
+    }
+    issue_fence();  // trip 2: the N buckets
+    ACL_MARK(wo, PH_BUCKETS);
+    bool hit[N], push[N];
+    uint64_t pb[N];
+    uint32_t pre[N], np = 0;
+#pragma unroll
+    for (int k = 0; k < N; k++) hit[k] = valid[k] & bucket_has(p[k], edge[k] & kIdMask);
+    if (!ACL_ISA_NO_SLOW && __ballot(hrow_is_slow(slow))) {  // (rare: a child whose request's subject has a SLOW row -- two-choice, or 2^16 buckets and more: its bucket(s) by the
+                                         //  32-bit hash, one child at a time; a hit in the fast hash's bucket of such a row is still a hit: the id IS in the row)
+#pragma unroll
+        for (int k = 0; k < N; k++) {
+            const uint4 ta = t.a[tj[k]];
+            if (hrow_is_slow(ta.z)) {
+                const uint32_t cid = edge[k] & kIdMask, h1 = hrow_slow(cid, ta.z);
+                uint4 q = gld(buckets, ta.y + h1);
+                bool h = bucket_has(q, cid);
+                if (ta.z & kRowTwoBit) {
+                    q = gld(buckets, ta.y + hrow_bucket2(cid, ta.z, h1));
+                    h = h | bucket_has(q, cid);
+                }
+                hit[k] = hit[k] | (valid[k] & h);
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+        // (bitwise, not &&: a short-circuit puts the compare under a branch, and the compiler then waits for "maybe still pending"
+        //  loads at the end of every step; depth limits were checked per task above)
+        push[k] = valid[k] & !hit[k] & ((edge[k] & kLeafBit) == 0u);
+    }
+    // stores only after the last compare: a conditional store between two compares makes the second one's wait cover it
+    // (vmcnt counts stores too, and the compiler must assume the store was not issued)
+    {
+        // (one branch for the step's hits, not an exec-mask round trip per child: most steps of the deep levels answer nobody)
+        bool anyhit = hit[0];
+#pragma unroll
+        for (int k = 1; k < N; k++) anyhit = anyhit | hit[k];
+        if (__ballot(anyhit)) {
+#pragma unroll
+            for (int k = 0; k < N; k++)
+                if (hit[k]) ans_set<E8>(has, rq[k], UM ? 0u : wo.first, 1);
+        }
+    }
+    if (E8) {
+        // a request answered by THIS step's hits (or by another wave a moment ago) needs none of its other children any more: looked at
+        // once more before they are written -- an entry not written is not read back, and frees a lane of a segment of the next level
+        // (C4 253 -> 238 us; profiles/r04_push_recheck_ab.txt)
+        wave_lds_fence();
+        uint32_t hv[N];  // (the N answer bytes travel together: one LDS round trip, not N dependent ones)
+#pragma unroll
+        for (int k = 0; k < N; k++) hv[k] = ans_get<true>(has, rq[k], UM ? 0u : wo.first);
+        issue_fence();
+#pragma unroll
+        for (int k = 0; k < N; k++) push[k] = push[k] & (hv[k] == 0u);
+    }
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+        pb[k] = __ballot(push[k]);
+        pre[k] = np;
+        np += (uint32_t)__popcll(pb[k]);
+    }
+    if (np) {
+        const uint32_t base = reserve<LOCAL>(wo, np, lane);
+        if (base != kNoSpace) {
+#pragma unroll
+            for (int k = 0; k < N; k++)
+                if (push[k]) {
+                    if (UM)  // (the task holds the request's index inside the unit: the entry's y word without the subtraction)
+                        gst(reinterpret_cast<uint2 *>(wo.buf), base + pre[k] + lanes_below(pb[k]), make_uint2((edge[k] & kIdMask) | 0x80000000u, (umeta & 0x7FFFFu) | (rq[k] << 19)));
+                    else
+                        put_entry<E8>(wo, base + pre[k] + lanes_below(pb[k]), edge[k] & kIdMask, rq[k], (UM ? umeta : t.meta[tj[k]]) | kProbedBit, UM ? 0u : t.sid[tj[k]]);
+                }
+        }
+    }
+#if ACL_PROFILE_PHASES  // (instrumented builds: steps issued, and the windows a full-width step would have issued for no valid lane)
+    if (lane == 0) {
+        wo.cold->prof[16] += 1u;
+        wo.cold->prof[17] += (uint32_t)(kSimpleWidth - N);
+    }
+#endif
+    ACL_MARK(wo, PH_PUSH);
+}
 template <bool LOCAL, bool E8, bool UM>
 __device__ __forceinline__ void simple_steps(TaskLds &t, uint32_t total, WaveOut &wo, uint32_t lane, const uint32_t *__restrict__ edges, const uint4 *__restrict__ buckets,
                                              uint8_t *has, uint8_t *err, uint32_t umeta) {
     constexpr int W = kSimpleWidth;
+    static_assert(W == 3, "the step bodies below are the widths 1 .. 3");
     uint32_t before = 0;  // tasks that start before the current 64-item window
     ACL_MARK(wo, PH_PROLOGUE);
-    // A step = kEdgesAhead windows of 64 children: their edges go out in one trip (one VGPR each), then the buckets follow W windows
-    // at a time (8 VGPRs per child).
-    constexpr int E = kEdgesAhead;
-    static_assert(E % W == 0, "the bucket stage walks the fetched windows W at a time");
-    for (uint32_t w0 = 0; w0 < total; w0 += 64 * E) {
-        bool valid[E];
-        uint32_t tj[E], edge[E];
-#pragma unroll
-        for (int k = 0; k < E; k++) {
-            const uint32_t win = (w0 >> 6) + (uint32_t)k;
-            const uint64_t hw = win < kHeadWords ? t.heads[win] : 0ull;
-            const uint32_t hlo = uniform((uint32_t)hw), hhi = uniform((uint32_t)(hw >> 32));
-            const uint32_t w = w0 + 64u * k + lane;
-            valid[k] = w < total;
-            const uint32_t wv = valid[k] ? w : total - 1;  // inactive lanes shadow the last child: every load stays in range
-            // tasks starting at or before this lane's work item, minus one (beyond `total` there are no head bits: the last task)
-            // (the lane's own head bit straight from the uniform mask -- inverse ballot: the mask IS the condition register; `(hw >> lane) & 1` is a 64-bit
-            //  vector shift, quarter rate, plus an AND per child window)
-            const uint32_t own = __builtin_amdgcn_inverse_ballot_w64(((uint64_t)hhi << 32) | hlo) ? 1u : 0u;
-            const uint32_t j = before + __builtin_amdgcn_mbcnt_hi(hhi, __builtin_amdgcn_mbcnt_lo(hlo, 0u)) + own - 1u;
-            before += (uint32_t)__popc(hlo) + (uint32_t)__popc(hhi);
-            tj[k] = j;
-            edge[k] = gld(edges, t.a[j].x + wv);
-        }
-        issue_fence();  // trip 1: every edge of the step
-        ACL_MARK(wo, PH_EDGES);
-#pragma unroll
-        for (int k0 = 0; k0 < E; k0 += W) {
-            if (w0 + 64u * k0 >= total) break;  // (uniform)
-            uint4 p[W];
-            uint32_t rq[W];
-            uint32_t slow = 0u;
-#pragma unroll
-            for (int k = 0; k < W; k++) {
-                const uint4 ta = t.a[tj[k0 + k]];  // the child's task: {edge base, first bucket, the row's y (buckets | two-choice | seed), request} in one 16-byte read
-                rq[k] = ta.w;
-                // (hrow_fast: full-rate arithmetic, in range for EVERY row and right for all but the slow ones -- those are redone below)
-                p[k] = gld(buckets, ta.y + hrow_fast(edge[k0 + k] & kIdMask, ta.z));
-                slow |= ta.z;
-            }
-            issue_fence();  // trip 2: the W buckets
-            ACL_MARK(wo, PH_BUCKETS);
-            bool hit[W], push[W];
-            uint64_t pb[W];
-            uint32_t pre[W], np = 0;
-#pragma unroll
-            for (int k = 0; k < W; k++) hit[k] = valid[k0 + k] & bucket_has(p[k], edge[k0 + k] & kIdMask);
-            if (!ACL_ISA_NO_SLOW && __ballot(hrow_is_slow(slow))) {  // (rare: a child whose request's subject has a SLOW row -- two-choice, or 2^16 buckets and more: its bucket(s) by the
-                                                 //  32-bit hash, one child at a time; a hit in the fast hash's bucket of such a row is still a hit: the id IS in the row)
-#pragma unroll
-                for (int k = 0; k < W; k++) {
-                    const uint4 ta = t.a[tj[k0 + k]];
-                    if (hrow_is_slow(ta.z)) {
-                        const uint32_t cid = edge[k0 + k] & kIdMask, h1 = hrow_slow(cid, ta.z);
-                        uint4 q = gld(buckets, ta.y + h1);
-                        bool h = bucket_has(q, cid);
-                        if (ta.z & kRowTwoBit) {
-                            q = gld(buckets, ta.y + hrow_bucket2(cid, ta.z, h1));
-                            h = h | bucket_has(q, cid);
-                        }
-                        hit[k] = hit[k] | (valid[k0 + k] & h);
-                    }
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < W; k++) {
-                // (bitwise, not &&: a short-circuit puts the compare under a branch, and the compiler then waits for "maybe still pending"
-                //  loads at the end of every step; depth limits were checked per task above)
-                push[k] = valid[k0 + k] & !hit[k] & ((edge[k0 + k] & kLeafBit) == 0u);
-            }
-            // stores only after the last compare: a conditional store between two compares makes the second one's wait cover it
-            // (vmcnt counts stores too, and the compiler must assume the store was not issued)
-            {
-                // (one branch for the step's hits, not an exec-mask round trip per child: most steps of the deep levels answer nobody)
-                bool anyhit = hit[0];
-#pragma unroll
-                for (int k = 1; k < W; k++) anyhit = anyhit | hit[k];
-                if (__ballot(anyhit)) {
-#pragma unroll
-                    for (int k = 0; k < W; k++)
-                        if (hit[k]) ans_set<E8>(has, rq[k], UM ? 0u : wo.first, 1);
-                }
-            }
-            if (E8) {
-                // a request answered by THIS step's hits (or by another wave a moment ago) needs none of its other children any more: looked at
-                // once more before they are written -- an entry not written is not read back, and frees a lane of a segment of the next level
-                // (C4 253 -> 238 us; profiles/r04_push_recheck_ab.txt)
-                wave_lds_fence();
-                uint32_t hv[W];  // (the W answer bytes travel together: one LDS round trip, not W dependent ones)
-#pragma unroll
-                for (int k = 0; k < W; k++) hv[k] = ans_get<true>(has, rq[k], UM ? 0u : wo.first);
-                issue_fence();
-#pragma unroll
-                for (int k = 0; k < W; k++) push[k] = push[k] & (hv[k] == 0u);
-            }
-#pragma unroll
-            for (int k = 0; k < W; k++) {
-                pb[k] = __ballot(push[k]);
-                pre[k] = np;
-                np += (uint32_t)__popcll(pb[k]);
-            }
-            if (np) {
-                const uint32_t base = reserve<LOCAL>(wo, np, lane);
-                if (base != kNoSpace) {
-#pragma unroll
-                    for (int k = 0; k < W; k++)
-                        if (push[k]) {
-                            if (UM)  // (the task holds the request's index inside the unit: the entry's y word without the subtraction)
-                                gst(reinterpret_cast<uint2 *>(wo.buf), base + pre[k] + lanes_below(pb[k]), make_uint2((edge[k0 + k] & kIdMask) | 0x80000000u, (umeta & 0x7FFFFu) | (rq[k] << 19)));
-                            else
-                                put_entry<E8>(wo, base + pre[k] + lanes_below(pb[k]), edge[k0 + k] & kIdMask, rq[k], (UM ? umeta : t.meta[tj[k0 + k]]) | kProbedBit, UM ? 0u : t.sid[tj[k0 + k]]);
-                        }
-                }
-            }
-            ACL_MARK(wo, PH_PUSH);
-        }
+    for (uint32_t w0 = 0; w0 < total; w0 += 64 * W) {
+        const uint32_t left = total - w0;  // (uniform: one branch per step)
+        if (!E8 || left > 128u) simple_step<LOCAL, E8, UM, 3>(t, w0, total, before, wo, lane, edges, buckets, has, err, umeta);
+        else if (left > 64u) simple_step<LOCAL, E8, UM, 2>(t, w0, total, before, wo, lane, edges, buckets, has, err, umeta);
+        else simple_step<LOCAL, E8, UM, 1>(t, w0, total, before, wo, lane, edges, buckets, has, err, umeta);
     }
 }
 
@@ -989,12 +1000,24 @@ __device__ __forceinline__ void process_segment(const uint4 &e, bool valid, Next
                     const uint32_t hvA = ans_get<true>(has, valid ? req : wo.first, wo.first), hvB = ans_get<true>(has, vB ? eB.y : wo.first, wo.first);
                     const bool inA = valid && id < d_nrows, inB = vB && eB.x < d_nrows;
                     const uint2 mdA = gld(dmeta2, d_base + (inA ? id * rK + rk : 0u)), mdB = gld(dmeta2, d_base + (inB ? eB.x * rK + rk : 0u));
+                    // the subject's row of the child's probe is a constant of the REQUEST: for the snapshot's hot hashed class (DevGraph::hot_*) every
+                    // request's descriptor was fetched once, when the unit was seeded (s_sd) -- two LDS reads here, not two gathers per pair of segments
+                    const bool hotd = d_cbase == g.hot_cbase && d_cnrows == g.hot_cnrows && uniform(LD.ckey) == g.hot_ckey;  // (uniform)
                     const bool okA = valid && e.w < d_cnrows, okB = vB && eB.w < d_cnrows;
-                    uint2 sdA = gld(dmeta2, d_cbase + (okA ? e.w : 0u)), sdB = gld(dmeta2, d_cbase + (okB ? eB.w : 0u));
+                    uint2 sdA, sdB;
+                    if (hotd) {
+                        sdA = wo.ssd[valid ? req - wo.first : 0u];
+                        sdB = wo.ssd[vB ? eB.y - wo.first : 0u];
+                    } else {
+                        sdA = gld(dmeta2, d_cbase + (okA ? e.w : 0u));
+                        sdB = gld(dmeta2, d_cbase + (okB ? eB.w : 0u));
+                    }
                     issue_fence();
                     ACL_MARK(wo, PH_GATHERS);
-                    if (!(okA && sdA.y != 0u)) sdA = make_uint2(0u, 1u);  // no row: the reserved empty bucket
-                    if (!(okB && sdB.y != 0u)) sdB = make_uint2(0u, 1u);
+                    if (!hotd) {
+                        if (!(okA && sdA.y != 0u)) sdA = make_uint2(0u, 1u);  // no row: the reserved empty bucket (what s_sd holds for such a request)
+                        if (!(okB && sdB.y != 0u)) sdB = make_uint2(0u, 1u);
+                    }
                     const uint32_t degA = (valid && !hvA && inA && mdA.y > mdA.x) ? mdA.y - mdA.x : 0u;
                     const uint32_t degB = (vB && !hvB && inB && mdB.y > mdB.x) ? mdB.y - mdB.x : 0u;
                     const uint32_t inclA = wave_incl_scan(degA, lane), totA = wave_last(inclA);
@@ -1042,6 +1065,7 @@ __device__ __forceinline__ void process_segment(const uint4 &e, bool valid, Next
             if (pairB) next.take();
             else validB = false;
             const uint2 *__restrict__ meta2 = reinterpret_cast<const uint2 *>(g.meta);
+            // (the subject's row descriptor is gathered here: reading the unit's LDS copy, s_sd, as the direct form does took the walk past its 80 VGPRs -- 30 to 63 spilled)
             auto subj_desc = [&](const uint4 &se, bool sv, const LaneOp &L) -> uint2 {
                 const bool ok = sv && meta_key(se.z) == L.ckey && se.w < L.cnrows;
                 const uint2 d = gld(meta2, L.cbase + (ok ? se.w : 0u));
@@ -1456,6 +1480,9 @@ __global__ __launch_bounds__(WAVES * 64, ACL_LOCAL_WAVES_PER_SIMD) void k_check_
     __shared__ uint32_t s_ccount[2];  // CMB: {leaf cells, nodes} of the unit being walked
     constexpr bool E8 = !CMB;  // 8-byte frontier entries (put_entry)
     __shared__ uint2 s_req[E8 ? WAVES * 64 : 1];  // E8: {subject id, subject key} of the unit's requests
+    // E8: {first bucket, the row's y} of every request's subject in the snapshot's hot hashed class (DevGraph::hot_*; {0, 1}, the reserved empty bucket, where the
+    // subject has no row there): what the deep levels gathered per ENTRY -- some 50 times per request -- is gathered once per request, at the seeds
+    __shared__ uint2 s_sd[E8 ? WAVES * 64 : 1];
     __shared__ uint8_t s_has[E8 ? WAVES * 64 : 1], s_err[E8 ? WAVES * 64 : 1];  // E8: the unit's answer bytes (ans_get / ans_set)
     if (E8) {
         has = s_has;
@@ -1489,6 +1516,7 @@ __global__ __launch_bounds__(WAVES * 64, ACL_LOCAL_WAVES_PER_SIMD) void k_check_
     wo.cold = &s_cold[wib];
     wo.lcap = E8 ? 2u * cap : cap;  // (the block's region holds twice as many 8-byte entries)
     wo.lfill = &s_fill[1];
+    wo.ssd = s_sd;
     // units [0, nstatic) hold rpw requests each (block b starts on unit b: no hand-out); the requests behind them come in SMALL units of rdyn,
     // handed out through `next_unit` as blocks finish -- the launch's tail is then a small unit's walk, not the slowest big unit's
     const uint32_t nstat_req = min(n, nstatic * rpw);
@@ -1529,7 +1557,16 @@ __global__ __launch_bounds__(WAVES * 64, ACL_LOCAL_WAVES_PER_SIMD) void k_check_
             const uint32_t skey = srel == 0xFFFFu ? g.nslots + stype : sbase + srel;
             const uint32_t meta = ok ? make_meta(rbase + perm, 1u, skey) : kDeadMeta;
             e = make_uint4(it.y, req, meta, it.w);
-            if (E8) s_req[threadIdx.x] = make_uint2(it.w, skey);
+            if (E8) {
+                s_req[threadIdx.x] = make_uint2(it.w, skey);
+                uint2 sd = make_uint2(0u, 1u);
+                if (g.hot_cnrows) {  // (uniform)
+                    const bool hot = skey == g.hot_ckey && it.w < g.hot_cnrows;
+                    const uint2 d = gld(reinterpret_cast<const uint2 *>(g.meta), g.hot_cbase + (hot ? it.w : 0u));
+                    if (hot && d.y != 0u) sd = d;
+                }
+                s_sd[threadIdx.x] = sd;
+            }
         }
         wo.first = first;
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -1671,7 +1708,7 @@ __global__ __launch_bounds__(WAVES * 64, ACL_LOCAL_WAVES_PER_SIMD) void k_check_
     }
 #if ACL_PROFILE_PHASES
     ACL_MARK(wo, PH_OTHER);
-    if (lane < 16) atomicAdd(&acl_phase_cycles[lane], (unsigned long long)s_cold[wib].prof[lane]);
+    if (lane < 18) atomicAdd(&acl_phase_cycles[lane], (unsigned long long)s_cold[wib].prof[lane]);
 #endif
     // ---- small host batches (round 5): the caller does not wait in hipStreamSynchronize -- that costs ~5.5 us AFTER the kernel's
     // last store is visible to a spinning host thread (tools/launch_latency.hip: flag visible 6.6 us after the launch call, synchronize returns at
@@ -2587,9 +2624,9 @@ __global__ __launch_bounds__(256) void k_import_gathered(DevFrontier f, uint32_t
 
 #if ACL_PROFILE_PHASES
 }  // namespace acl
-extern "C" int acl_debug_phase_cycles(unsigned long long *out16) {  // variant builds only (tools/phases.sh): reads and resets the counters
-    unsigned long long z[16] = {0};
-    if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(acl::acl_phase_cycles), sizeof(z)) != hipSuccess) return 1;
+extern "C" int acl_debug_phase_cycles(unsigned long long *out18) {  // variant builds only (tools/phases.py): reads and resets the counters
+    unsigned long long z[18] = {0};
+    if (hipMemcpyFromSymbol(out18, HIP_SYMBOL(acl::acl_phase_cycles), sizeof(z)) != hipSuccess) return 1;
     return hipMemcpyToSymbol(HIP_SYMBOL(acl::acl_phase_cycles), z, sizeof(z)) == hipSuccess ? 0 : 1;
 }
 namespace acl {

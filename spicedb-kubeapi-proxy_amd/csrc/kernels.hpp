@@ -40,6 +40,9 @@ struct DevGraph {
     uint32_t cell0 = 0;                // index of the first leaf cell in has[] / err[] (= the batch size: cells follow the requests' own)
     uint32_t walk_flags = 0;           // kWalkNoDirect: the single-launch walk builds every task list the general way (set by the host after a walk met a
                                        // pair of segments with more children than the direct form's head-bit window: kernels.hip, process_segment)
+    // the snapshot's hot hashed class (Snapshot::hot_*, plan.cpp choose_hot_class): the single-launch walk keeps every request's row descriptor of this class
+    // in LDS for the length of a unit (kernels.hip, k_check_local's s_sd).  hot_cnrows == 0: none
+    uint32_t hot_cbase = 0, hot_cnrows = 0, hot_ckey = 0;
 };
 constexpr uint32_t kWalkNoDirect = 1u;
 constexpr uint32_t kOverflowPools = 8u;   // level loop on the SHARDED graph, schemas with `&` / `-`: a shard ran out of combine nodes / leaf cells -- the native loop grows the pools and redoes the batch

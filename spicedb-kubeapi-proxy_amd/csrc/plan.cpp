@@ -316,6 +316,25 @@ void collect(const Node &n, Node::Kind kind, std::vector<const Node *> *out) {
     for (const Node &k : n.kids) collect(k, kind, out);
 }
 
+// Snapshot::hot_*: among the slots that some enumerating op leads into and whose program starts with exactly one plain hashed probe (the children the
+// walk's deep levels accept: kernels.hip, lane_op), the probe's class with the most subject rows; the lowest descriptor base breaks a tie.  A function
+// of the programs alone (a patch changes neither an op's class nor the ids it covers), so it is made where they are.
+void choose_hot_class(Snapshot &s) {
+    s.hot_cbase = s.hot_cnrows = s.hot_ckey = 0;
+    for (const FwdOp &o : s.ops) {
+        if (!(o.flags & OP_ENUM) || (o.flags & (OP_PUSH_SAME | OP_REFLEX | OP_PROBE_HASH)) || o.key >= s.progs.size()) continue;
+        const SlotProg &cp = s.progs[o.key];
+        if (cp.n_probe != 1 || cp.combine) continue;
+        const FwdOp &c = s.ops[cp.first];
+        if (c.flags != OP_PROBE_HASH || c.nrows == 0) continue;
+        if (c.nrows > s.hot_cnrows || (c.nrows == s.hot_cnrows && c.base < s.hot_cbase)) {
+            s.hot_cbase = c.base;
+            s.hot_cnrows = c.nrows;
+            s.hot_ckey = c.key;
+        }
+    }
+}
+
 }  // namespace
 
 // tables are sized for objects that do not exist yet, so that writes naming new objects can be patched in
@@ -534,6 +553,7 @@ void build_forward(Store &store, int64_t now, Snapshot *snap, ShardSpec shard) {
     }
     if (s.ops.empty()) s.ops.push_back(FwdOp{});
     if (s.bexpr.empty()) s.bexpr.push_back(0);
+    choose_hot_class(s);
     // which slots' values can depend on a combine program (their LookupResources is candidates + a forward Check): the combine slots and
     // whatever reaches one through a reference, an arrow or a userset subject
     s.slot_nonmono.assign(sc.nslots, 0);

@@ -170,6 +170,10 @@ struct Snapshot {
     std::vector<uint32_t> buckets;  // hashed rows: uint4 buckets of RESOURCE ids of one subject, empty slot = 0xFFFFFFFF
     std::vector<FwdOp> ops;
     std::vector<SlotProg> progs;  // [nslots]
+    // The hot hashed class: the class {descriptor base, subjects covered, subject key} of the one hashed probe of a slot that an enumerating op leads into
+    // (what the walk's deep levels probe every child in: `group#member@user` on a nested-groups schema); the one with the most subject rows where several
+    // qualify, hot_cnrows == 0 where none does.  A hint: the walk fetches this class's row descriptor once per request instead of once per entry.
+    uint32_t hot_cbase = 0, hot_cnrows = 0, hot_ckey = 0;
     std::vector<uint32_t> bexpr;  // boolean programs of the combine slots (word 0 unused: SlotProg::combine == 0 means none)
     bool has_combine = false;     // some slot's rewrite uses `&` / `-`: evaluations run the kernels' combine instantiations
     std::vector<uint8_t> slot_nonmono;  // [nslots] the slot's value can depend on a combine program: LookupResources = candidates + a forward Check

@@ -2,7 +2,8 @@
 """usage: tools/isa_loops.py [-DNAME=VALUE ...] -- instruction mix of the hot loops of k_check_local<true, 12, false> (the wide monotone walk) in the gfx950 ISA.
 
 Cross-compiles kernels.hip to assembly (no GPU needed), cuts the kernel out, and for every innermost loop that holds the simple expansion's three
-bucket gathers (global_load_dwordx4 x 3 per step: simple_steps) prints VALU / SALU / LDS / VMEM / wait counts, the quarter-rate multiplies
+bucket gathers (global_load_dwordx4 x 3 per step: simple_steps -- with 8-byte entries the loop also holds the two- and one-window bodies of an expansion's last
+step, six bucket gathers in all) prints VALU / SALU / LDS / VMEM / wait counts, the quarter-rate multiplies
 (v_mul_lo_u32 / v_mul_hi_u32), 64-bit shifts and the lane spills (v_writelane / v_readlane) inside it -- what a step of 192 children costs a wave.
 The walk is instruction-issue bound (profiles/r05_pmc_c4.md); this is the static half of that picture, the PMC passes are the dynamic one."""
 import os

@@ -25,7 +25,7 @@ d_items = torch.from_numpy(items.view(np.uint8).copy()).cuda()
 d_perm = torch.zeros(n, dtype=torch.uint8, device="cuda")
 d_err = torch.zeros(n, dtype=torch.int32, device="cuda")
 lib = C.CDLL(os.environ["ACLGPU_LIB"])
-out = (C.c_ulonglong * 16)()
+out = (C.c_ulonglong * 18)()
 for _ in range(3):
     e.check_bulk_ids_device(d_items.data_ptr(), n, d_perm.data_ptr(), d_err.data_ptr())
 torch.cuda.synchronize()
@@ -46,4 +46,9 @@ for i, nm in enumerate(NAMES):
 if out[12]:
     print(f"  deep-level entries read per batch {out[12] / K / 1e6:.2f} M, of which dead on arrival {100.0 * out[13] / out[12]:.1f} %; segments {out[14] / K / 1e3:.0f} k, "
           f"pairs whose live entries fit ONE segment {100.0 * 2 * out[15] / max(out[14], 1):.1f} % of the segments")
+# counters of the simple expansion (slots 16-17): steps issued, and the 64-child windows its narrow last steps left out -- each of them two vector-memory
+# instructions (an edge and a bucket gather) that a full-width step issues for no valid lane
+if out[16]:
+    print(f"  simple-expansion steps per batch {out[16] / K / 1e3:.0f} k, windows without a valid lane {out[17] / K / 1e3:.0f} k = {out[17] / out[16]:.2f} per step "
+          f"({100.0 * out[17] / (3 * out[16]):.1f} % of the windows of full-width steps)")
 e.close()

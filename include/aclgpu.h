@@ -563,6 +563,7 @@ typedef struct {
     uint64_t ids_recycled;         /* object ids given a new name after their object had lost its last relationship (since the schema was loaded) */
     uint64_t keep_route_calls;     /* acl_check_bulk_keep_v / _packed calls answered by ONE reverse walk and bit tests (since open) */
     uint64_t depth_sweeps;         /* forward sweeps over a whole type that established "no Check of this permission ends at the depth limit" for the snapshot (since open) */
+    uint64_t hop2_rows;            /* two-hop rows of nested groups in the current snapshot (0: none qualify, or a nesting write dropped them until the next build) */
 } acl_stats_t;
 int acl_stats(acl_engine_t *h, acl_stats_t *out);
 int acl_stats_reset(acl_engine_t *h);

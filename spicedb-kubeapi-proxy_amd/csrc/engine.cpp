@@ -47,6 +47,7 @@ static void read_env_knobs(acl_engine *h) {
     if (const char *ev = getenv("ACL_LOCAL_UPW")) h->local_upw = (uint32_t)std::max(1, atoi(ev));  // A/B knob: units per resident wave
     if (const char *ev = getenv("ACL_LOCAL_STATIC_PCT")) h->local_static_pct = (uint32_t)std::min(100, std::max(10, atoi(ev)));  // A/B knobs: share of a chip-filling batch
     if (const char *ev = getenv("ACL_LOCAL_DYN_UNIT")) h->local_dyn_unit = (uint32_t)std::min(256, std::max(1, atoi(ev)));       // in static units; size of the hand-out units
+    if (const char *ev = getenv("ACL_HOP2")) h->hop2_on = atoi(ev) != 0;  // A/B knob: 0 = the walk ignores the two-hop rows
     if (const char *ev = getenv("ACL_LOCAL_MAX")) h->local_max_items = (uint32_t)atoi(ev);  // A/B knob: 0 disables the single-launch path
 }
 
@@ -500,6 +501,7 @@ int acl_stats(acl_engine_t *h, acl_stats_t *out) {
     out->ids_recycled = recycled;
     out->keep_route_calls = h->keep_route_calls.load(std::memory_order_relaxed);
     out->depth_sweeps = h->depth_sweeps.load(std::memory_order_relaxed);
+    out->hop2_rows = h->hop2_rows_now.load(std::memory_order_relaxed);
     return ACL_OK;
 }
 int acl_stats_reset(acl_engine_t *h) {

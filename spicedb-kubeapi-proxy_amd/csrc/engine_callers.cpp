@@ -634,6 +634,7 @@ int acl_selfcheck_snapshot(acl_engine_t *h, int *patched_out) {
                         : p.array == Patch::RMETA ? h->snap.rmeta.size() : h->snap.redges.size();
         if (p.off + p.n > sz) return fail(ACL_ERR_INTERNAL, "patch region outside its array");
     }
+    h->hop2_rows_now.store(h->snap.hop2_rows, std::memory_order_relaxed);
     if (patched_out) *patched_out = patched ? 1 : current ? 2 : 0;  // 1: patched in place, 0: rebuilt, 2: was current already
     if (patched || current) debug_rows_report(h->store, h->snap);  // (a rebuild reported itself in build_forward)
     std::string why;
@@ -676,6 +677,7 @@ int acl_selfcheck_compaction(acl_engine_t *h, int phase, int *adopted_out) {
     h->snap = std::move(c->snap);
     c->snap = Snapshot();
     h->snap_valid = true;
+    h->hop2_rows_now.store(h->snap.hop2_rows, std::memory_order_relaxed);
     if (!h->snap.has_reverse) build_reverse(h->store, now, &h->snap, h->shard);
     std::string why;
     if (!verify_snapshot(h->store, now, h->snap, h->shard, &why)) return fail(ACL_ERR_INTERNAL, "compacted snapshot does not match the store: " + why);

@@ -393,12 +393,14 @@ struct acl_engine {
     std::mutex deep_mu;
     std::vector<DeepKnown> deep_known;  // (a handful: one per list rule's template)
     std::atomic<uint64_t> depth_sweeps{0};
+    std::atomic<uint64_t> hop2_rows_now{0};  // Snapshot::hop2_rows of the current snapshot (stored wherever the snapshot is built, patched or adopted)
     bool per_item_validation = false;  // ACL_FLAG_PER_ITEM_VALIDATION: ill-formed items of a bulk Check fail their own pair, not the call
     bool lenient_lookup = false;       // ACL_FLAG_LENIENT_LOOKUP: a LookupResources candidate whose forward Check errs is dropped instead of failing the call
     bool store_only = false;  // ACL_FLAG_STORE_ONLY: relationship store without a device (reads that need the GPU fail)
     // the single-launch walk met rows too long for its direct task lists on this snapshot (kOverflowDirect): later walks build their lists the general
     // way (reset when a snapshot is rebuilt); (the batch that found out is redone without a back-off: PassCtx::direct_tripped, walk_outcome)
     std::atomic<bool> walk_no_direct{false};
+    bool hop2_on = true;  // the walk's direct form reads the snapshot's two-hop rows (ACL_HOP2=0: the one-hop rows only; A/B and tests)
     std::atomic<int> local_skip{0}, local_fail_streak{0};  // large passes the walk sits out after it overflowed (check_pass)
     bool raw_intern = false;       // test knob (ACL_RAW_INTERN): acl_intern skips the API's object-id pattern
     uint32_t local_cap_limit = 0;  // test knob (ACL_LOCAL_CAP): private frontier entries per block, at most
@@ -467,7 +469,10 @@ struct acl_engine {
 
     DevGraph dev_graph(const DevState &d) const {
         DevGraph g{d.d_meta.p, d.d_edges.p, d.d_buckets.p, d.d_ops.p, d.d_progs.p, d.d_tsb.p, d.d_tnm.p, snap.nslots, snap.ntypes, (uint32_t)snap.ops.size()};
-        g.walk_flags = walk_no_direct.load(std::memory_order_relaxed) ? kWalkNoDirect : 0u;
+        g.walk_flags = (walk_no_direct.load(std::memory_order_relaxed) ? kWalkNoDirect : 0u) | (hop2_on ? 0u : kWalkNoHop2);
+        g.hop2_base = snap.hop2_base;  // (read from the snapshot with every pass: a patch that drops the rows reaches the next walk with it)
+        g.hop2_nrows = snap.hop2_nrows;
+        g.hop2_slot = (hop2_on && snap.hop2_nrows) ? snap.hop2_slot : 0xFFFFFFFFu;  // (the walk's one test: "is this the two-hop slot, and are its rows in use")
         g.hot_cbase = snap.hot_cbase;
         g.hot_cnrows = snap.hot_cnrows;
         g.hot_ckey = snap.hot_ckey;

@@ -184,6 +184,7 @@ static bool compaction_adopt(acl_engine *h, int64_t now) {
     refresh_local_blocks(h);
     std::lock_guard<std::mutex> lk(h->stats_mu);
     h->stats.snapshot_compactions++;
+    h->hop2_rows_now.store(h->snap.hop2_rows, std::memory_order_relaxed);
     h->stats.snapshot_edges = h->snap.nedges;
     h->stats.snapshot_edges_local = h->snap.nedges_local;
     h->stats.snapshot_bytes = h->snap.meta.size() * 4 + h->snap.edges.size() * 4 + h->snap.buckets.size() * 4 + h->snap.ops.size() * sizeof(FwdOp) +
@@ -244,6 +245,7 @@ int ensure_snapshot(acl_engine *h) {
             {
                 std::lock_guard<std::mutex> lk(h->stats_mu);
                 h->stats.snapshot_patches++;
+                h->hop2_rows_now.store(h->snap.hop2_rows, std::memory_order_relaxed);
                 h->stats.snapshot_edges = h->snap.nedges;
                 h->stats.snapshot_edges_local = h->snap.nedges_local;
             }
@@ -285,6 +287,7 @@ int ensure_snapshot(acl_engine *h) {
     refresh_local_blocks(h);
     std::lock_guard<std::mutex> lk(h->stats_mu);
     h->stats.snapshot_builds++;
+    h->hop2_rows_now.store(h->snap.hop2_rows, std::memory_order_relaxed);
     h->walk_no_direct.store(false, std::memory_order_relaxed);  // (a new snapshot: the direct task lists get another chance)
     h->stats.snapshot_edges = h->snap.nedges;
     h->stats.snapshot_edges_local = h->snap.nedges_local;

@@ -107,7 +107,7 @@ __device__ __forceinline__ uint32_t wave_max(uint32_t v) {  // same network with
 #endif
 enum { PH_OTHER = 0, PH_ENTRIES, PH_GATHERS, PH_TASKS, PH_PROLOGUE, PH_EDGES, PH_BUCKETS, PH_PUSH, PH_GENERIC, PH_BARRIER, PH_SEED, PH_COUNT };
 #if ACL_PROFILE_PHASES
-__device__ unsigned long long acl_phase_cycles[18];
+__device__ unsigned long long acl_phase_cycles[20];
 #define ACL_MARK(wo, ph)                                                                  \
     do {                                                                                  \
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                       \
@@ -151,7 +151,7 @@ struct WaveOutCold {  // what only the chunk switch / overflow paths need: kept 
     uint32_t *counts, *nchunks, *overflow;
     uint32_t nwaves, max_chunks, cap;
 #if ACL_PROFILE_PHASES
-    uint32_t last, prof[18];  // [0, PH_COUNT): phase cycles; [12, 18): counters (process_segment, simple_step)
+    uint32_t last, prof[20];  // [0, PH_COUNT): phase cycles; [12, 20): counters (process_segment, simple_step; 18, 19: pairs expanded from two-hop rows / that fell back)
 #endif
 };
 struct WaveOut {
@@ -433,14 +433,19 @@ constexpr int kSimpleWidth = ACL_SIMPLE_WIDTH;  // children per lane whose bucke
 // item, t.heads = one bit per task at its first work item (set by the caller's prologue).  UM: every child carries the same meta `umeta`, the
 // entries are 8-byte ones (no per-task meta / subject id reads at the push) and t.a[j].w is the request's index INSIDE the unit (the answer-byte
 // accesses and the entry's y word without their subtractions).
+// PT (with UM; states of the two-hop slot, plan.hpp Snapshot::hop2_*): the children's level travels PER TASK -- t.a[j].w = request index << 19 | child level << 13,
+// `umeta` is the child slot alone and an entry's y word is their sum; hopadd = 1 << 13 while the tasks name two-hop rows, else 0: an edge with kHop2Bit is a
+// grandchild -- bit 30 is not part of its id, and its state lies one level further on.  Every other expansion is instantiated without any of it.
 // One step: N (<= kSimpleWidth) windows of 64 children from work item w0 on.  Their edges go out in one trip (one VGPR each), then their buckets
 // (8 VGPRs per child).  What the walk's time follows is the number of vector-memory INSTRUCTIONS its waves issue, whatever the number of lanes
 // that need them (profiles/r04_bucket_gather_sensitivity.txt, r06_ab_check_local.txt `warm`): a window without a valid lane costs what a full one
 // costs, so the LAST step of an expansion is instantiated only as wide as its children (simple_steps) -- every body keeps the shape: all edge loads,
 // fence, all bucket loads, fence, compares, stores behind the last compare.
-template <bool LOCAL, bool E8, bool UM, int N>
+template <bool LOCAL, bool E8, bool UM, int N, bool PT = false>
 __device__ __forceinline__ void simple_step(TaskLds &t, uint32_t w0, uint32_t total, uint32_t &before, WaveOut &wo, uint32_t lane, const uint32_t *__restrict__ edges,
-                                            const uint4 *__restrict__ buckets, uint8_t *has, uint8_t *err, uint32_t umeta) {
+                                            const uint4 *__restrict__ buckets, uint8_t *has, uint8_t *err, uint32_t umeta, uint32_t hopadd = 0u) {
+    static_assert(!PT || UM, "per-task levels ride in the uniform-meta form's task word");
+    const uint32_t idm = PT ? (kIdMask ^ (hopadd << 17)) : kIdMask;  // (uniform: without kHop2Bit while two-hop rows are read)
     bool valid[N];
     uint32_t tj[N], edge[N];
 #pragma unroll
@@ -470,7 +475,7 @@ __device__ __forceinline__ void simple_step(TaskLds &t, uint32_t w0, uint32_t to
         const uint4 ta = t.a[tj[k]];  // the child's task: {edge base, first bucket, the row's y (buckets | two-choice | seed), request} in one 16-byte read
         rq[k] = ta.w;
         // (hrow_fast: full-rate arithmetic, in range for EVERY row and right for all but the slow ones -- those are redone below)
-        p[k] = gld(buckets, ta.y + hrow_fast(edge[k] & kIdMask, ta.z));
+        p[k] = gld(buckets, ta.y + hrow_fast(edge[k] & idm, ta.z));
         slow |= ta.z;
     }
     issue_fence();  // trip 2: the N buckets
@@ -479,14 +484,14 @@ __device__ __forceinline__ void simple_step(TaskLds &t, uint32_t w0, uint32_t to
     uint64_t pb[N];
     uint32_t pre[N], np = 0;
 #pragma unroll
-    for (int k = 0; k < N; k++) hit[k] = valid[k] & bucket_has(p[k], edge[k] & kIdMask);
+    for (int k = 0; k < N; k++) hit[k] = valid[k] & bucket_has(p[k], edge[k] & idm);
     if (!ACL_ISA_NO_SLOW && __ballot(hrow_is_slow(slow))) {  // (rare: a child whose request's subject has a SLOW row -- two-choice, or 2^16 buckets and more: its bucket(s) by the
                                          //  32-bit hash, one child at a time; a hit in the fast hash's bucket of such a row is still a hit: the id IS in the row)
 #pragma unroll
         for (int k = 0; k < N; k++) {
             const uint4 ta = t.a[tj[k]];
             if (hrow_is_slow(ta.z)) {
-                const uint32_t cid = edge[k] & kIdMask, h1 = hrow_slow(cid, ta.z);
+                const uint32_t cid = edge[k] & idm, h1 = hrow_slow(cid, ta.z);
                 uint4 q = gld(buckets, ta.y + h1);
                 bool h = bucket_has(q, cid);
                 if (ta.z & kRowTwoBit) {
@@ -513,7 +518,7 @@ __device__ __forceinline__ void simple_step(TaskLds &t, uint32_t w0, uint32_t to
         if (__ballot(anyhit)) {
 #pragma unroll
             for (int k = 0; k < N; k++)
-                if (hit[k]) ans_set<E8>(has, rq[k], UM ? 0u : wo.first, 1);
+                if (hit[k]) ans_set<E8>(has, PT ? rq[k] >> 19 : rq[k], UM ? 0u : wo.first, 1);
         }
     }
     if (E8) {
@@ -523,7 +528,7 @@ __device__ __forceinline__ void simple_step(TaskLds &t, uint32_t w0, uint32_t to
         wave_lds_fence();
         uint32_t hv[N];  // (the N answer bytes travel together: one LDS round trip, not N dependent ones)
 #pragma unroll
-        for (int k = 0; k < N; k++) hv[k] = ans_get<true>(has, rq[k], UM ? 0u : wo.first);
+        for (int k = 0; k < N; k++) hv[k] = ans_get<true>(has, PT ? rq[k] >> 19 : rq[k], UM ? 0u : wo.first);
         issue_fence();
 #pragma unroll
         for (int k = 0; k < N; k++) push[k] = push[k] & (hv[k] == 0u);
@@ -540,7 +545,9 @@ __device__ __forceinline__ void simple_step(TaskLds &t, uint32_t w0, uint32_t to
 #pragma unroll
             for (int k = 0; k < N; k++)
                 if (push[k]) {
-                    if (UM)  // (the task holds the request's index inside the unit: the entry's y word without the subtraction)
+                    if (PT)  // (the task holds the entry's request and level bits; a grandchild's extra level is added)
+                        gst(reinterpret_cast<uint2 *>(wo.buf), base + pre[k] + lanes_below(pb[k]), make_uint2((edge[k] & idm) | 0x80000000u, umeta + rq[k] + ((edge[k] >> 17) & hopadd)));
+                    else if (UM)  // (the task holds the request's index inside the unit: the entry's y word without the subtraction)
                         gst(reinterpret_cast<uint2 *>(wo.buf), base + pre[k] + lanes_below(pb[k]), make_uint2((edge[k] & kIdMask) | 0x80000000u, (umeta & 0x7FFFFu) | (rq[k] << 19)));
                     else
                         put_entry<E8>(wo, base + pre[k] + lanes_below(pb[k]), edge[k] & kIdMask, rq[k], (UM ? umeta : t.meta[tj[k]]) | kProbedBit, UM ? 0u : t.sid[tj[k]]);
@@ -555,18 +562,18 @@ __device__ __forceinline__ void simple_step(TaskLds &t, uint32_t w0, uint32_t to
 #endif
     ACL_MARK(wo, PH_PUSH);
 }
-template <bool LOCAL, bool E8, bool UM>
+template <bool LOCAL, bool E8, bool UM, bool PT = false>
 __device__ __forceinline__ void simple_steps(TaskLds &t, uint32_t total, WaveOut &wo, uint32_t lane, const uint32_t *__restrict__ edges, const uint4 *__restrict__ buckets,
-                                             uint8_t *has, uint8_t *err, uint32_t umeta) {
+                                             uint8_t *has, uint8_t *err, uint32_t umeta, uint32_t hopadd = 0u) {
     constexpr int W = kSimpleWidth;
     static_assert(W == 3, "the step bodies below are the widths 1 .. 3");
     uint32_t before = 0;  // tasks that start before the current 64-item window
     ACL_MARK(wo, PH_PROLOGUE);
     for (uint32_t w0 = 0; w0 < total; w0 += 64 * W) {
         const uint32_t left = total - w0;  // (uniform: one branch per step)
-        if (!E8 || left > 128u) simple_step<LOCAL, E8, UM, 3>(t, w0, total, before, wo, lane, edges, buckets, has, err, umeta);
-        else if (left > 64u) simple_step<LOCAL, E8, UM, 2>(t, w0, total, before, wo, lane, edges, buckets, has, err, umeta);
-        else simple_step<LOCAL, E8, UM, 1>(t, w0, total, before, wo, lane, edges, buckets, has, err, umeta);
+        if (!E8 || left > 128u) simple_step<LOCAL, E8, UM, 3, PT>(t, w0, total, before, wo, lane, edges, buckets, has, err, umeta, hopadd);
+        else if (left > 64u) simple_step<LOCAL, E8, UM, 2, PT>(t, w0, total, before, wo, lane, edges, buckets, has, err, umeta, hopadd);
+        else simple_step<LOCAL, E8, UM, 1, PT>(t, w0, total, before, wo, lane, edges, buckets, has, err, umeta, hopadd);
     }
 }
 
@@ -973,7 +980,11 @@ __device__ __forceinline__ void process_segment(const uint4 &e, bool valid, Next
         LaneOp LA{}, LB{};
         bool simple;
         const uint64_t vbB = haveB ? __ballot(validB) : 0ull;
-        const bool oneslot = !__ballot(valid && meta != m0) && !(vbB && __ballot(validB && eB.z != m0));  // (same slot, level, key: the deep levels)
+        // (same slot, level, key: the deep levels.  States of the two-hop slot may differ in their LEVEL: with two-hop rows one iteration holds that slot's states
+        //  of two adjacent levels side by side -- children of one-hop rows and grandchildren of two-hop ones.  Nothing a segment of one slot relies on below
+        //  depends on the level: lane_op() does not look at it, seg_tasks() takes each lane's own, the direct form keeps it per task.)
+        const uint32_t lvbits = (E8 && meta_slot(m0) == g.hop2_slot) ? (63u << 13) : 0u;  // (uniform; hop2_slot names no slot while the rows are not in use)
+        const bool oneslot = !__ballot(valid && ((meta ^ m0) & ~lvbits) != 0u) && !(vbB && __ballot(validB && ((eB.z ^ m0) & ~lvbits) != 0u));
         if (oneslot) {
             // ---- the deep levels' shape, without the task list's round trips (round 5): ONE slot, level and subject key for both segments, children
             // that are "one hashed probe + authoritative leaf flags" (what flush_simple takes).  Decided and run HERE, while the program's fields are
@@ -982,77 +993,113 @@ __device__ __forceinline__ void process_segment(const uint4 &e, bool valid, Next
             // rebased and sets its head bit itself, and every child carries the same meta: no count / meta / subject-id stores, no read-back of the
             // counts, no read-modify-write of the edge bases -- the prologue's chain of dependent LDS trips (14 % of the walk's wave-time,
             // profiles/r05_ab_split_units.txt) shrinks to one fence.
-            LaneOp LD{};  // (a copy of its own: nothing of it is live behind this block, so the general path's LA / LB are not carried -- spilled -- across it)
-            if (E8 && !(g.walk_flags & kWalkNoDirect) && lane_op(m0, LD)) {
+            // HOP (states of the two-hop slot while two-hop rows are in use; uniform, decided per pair): the same form reading the two-hop rows and carrying the
+            // children's level per task.  Instantiated apart, so that every other pair runs the instructions it always ran.  true: the pair is done.
+            auto direct = [&](auto hop_tag) -> bool {
+                constexpr bool HOP = decltype(hop_tag)::value;
+                LaneOp LD{};  // (a copy of its own: nothing of it is live behind this block, so the general path's LA / LB are not carried -- spilled -- across it)
+                if (!lane_op(m0, LD)) return false;
                 // (the program's fields come out of the LDS copy in VGPRs, uniform or not: pinned into SGPRs here -- a dozen VGPRs held across the
                 //  gathers otherwise, and the walk has none to spare: 6 waves per SIMD allow 80, it took 72 when round 5 chose that shape
                 //  (profiles/r05_ab_block_shape.txt) and takes nearly all of them now (tools/resusage.py))
-                const uint32_t lv = meta_level(m0), Lv = lv + uniform(LD.dlevel);
+                uint32_t lv = meta_level(m0);
+                if (HOP && (__ballot(valid && meta != m0) || (vbB && __ballot(validB && eB.z != m0))))  // levels differ: the depth guards take the pair's highest
+                    lv = wave_max(max(valid ? meta_level(meta) : 0u, (vbB && validB) ? meta_level(eB.z) : 0u));
+                const uint32_t Lv = lv + uniform(LD.dlevel);
                 const uint32_t d_cnrows = uniform(LD.cnrows), d_cbase = uniform(LD.cbase), d_base = uniform(LD.base), d_nrows = uniform(LD.nrows), d_Kk = uniform(LD.Kk), d_key = uniform(LD.key);
-                if (d_cnrows != 0u && uniform(LD.ckey) == meta_key(m0) && (uniform(LD.flags) & OP_LEAFBIT) != 0u && Lv + 1u <= kMaxLevels && Lv + 1u + uniform(LD.cdl) <= kMaxLevels &&
-                    Lv + 1u + uniform(LD.cmaxd) <= kMaxLevels && lv + uniform(LD.maxd) <= kMaxLevels) {
-                    const bool dpair = vbB != 0;
-                    if (dpair) next.take();
-                    const uint2 *__restrict__ dmeta2 = reinterpret_cast<const uint2 *>(g.meta);
-                    const uint32_t rK = d_Kk & 0xFFFFu, rk = d_Kk >> 16;
-                    const bool vB = dpair && validB;
-                    // all six gathers in flight together
-                    const uint32_t hvA = ans_get<true>(has, valid ? req : wo.first, wo.first), hvB = ans_get<true>(has, vB ? eB.y : wo.first, wo.first);
-                    const bool inA = valid && id < d_nrows, inB = vB && eB.x < d_nrows;
-                    const uint2 mdA = gld(dmeta2, d_base + (inA ? id * rK + rk : 0u)), mdB = gld(dmeta2, d_base + (inB ? eB.x * rK + rk : 0u));
-                    // the subject's row of the child's probe is a constant of the REQUEST: for the snapshot's hot hashed class (DevGraph::hot_*) every
-                    // request's descriptor was fetched once, when the unit was seeded (s_sd) -- two LDS reads here, not two gathers per pair of segments
-                    const bool hotd = d_cbase == g.hot_cbase && d_cnrows == g.hot_cnrows && uniform(LD.ckey) == g.hot_ckey;  // (uniform)
-                    const bool okA = valid && e.w < d_cnrows, okB = vB && eB.w < d_cnrows;
-                    uint2 sdA, sdB;
-                    if (hotd) {
-                        sdA = wo.ssd[valid ? req - wo.first : 0u];
-                        sdB = wo.ssd[vB ? eB.y - wo.first : 0u];
-                    } else {
-                        sdA = gld(dmeta2, d_cbase + (okA ? e.w : 0u));
-                        sdB = gld(dmeta2, d_cbase + (okB ? eB.w : 0u));
-                    }
-                    issue_fence();
-                    ACL_MARK(wo, PH_GATHERS);
-                    if (!hotd) {
-                        if (!(okA && sdA.y != 0u)) sdA = make_uint2(0u, 1u);  // no row: the reserved empty bucket (what s_sd holds for such a request)
-                        if (!(okB && sdB.y != 0u)) sdB = make_uint2(0u, 1u);
-                    }
-                    const uint32_t degA = (valid && !hvA && inA && mdA.y > mdA.x) ? mdA.y - mdA.x : 0u;
-                    const uint32_t degB = (vB && !hvB && inB && mdB.y > mdB.x) ? mdB.y - mdB.x : 0u;
-                    const uint32_t inclA = wave_incl_scan(degA, lane), totA = wave_last(inclA);
-                    const uint32_t inclB = wave_incl_scan(degB, lane) + totA, total = wave_last(inclB);
-                    if (total > 64u * kHeadWords || __ballot(degA > kMaxRow || degB > kMaxRow)) {
-                        // more children than the head-bit window maps (an average fan-out beyond 16), or a row beyond the enumeration limit: this form has
-                        // no second round (one would have to keep the pair's registers across the steps, and the walk's VGPR budget is used up -- see above).  The batch is
-                        // redone on the level loop and the host switches the form off for this snapshot (kOverflowDirect; a row beyond kMaxRow fails
-                        // the call as it does on every path).
-                        if (lane == 0) *wo.cold->overflow = __ballot(degA > kMaxRow || degB > kMaxRow) ? 2u : kOverflowDirect;
-                        wo.cur = kNoSpace;
-                        return;
-                    }
-                    {
-                        if (!total) return;
-                        const uint64_t bA = __ballot(degA != 0u), bB = __ballot(degB != 0u);
-                        if (degA) {
-                            const uint32_t ex = inclA - degA;
-                            t.a[lanes_below(bA)] = make_uint4(mdA.x - ex, sdA.x, sdA.y, req - wo.first);
-                            atomicOr(reinterpret_cast<unsigned long long *>(&t.heads[ex >> 6]), 1ull << (ex & 63u));
-                        }
-                        if (degB) {
-                            const uint32_t ex = inclB - degB;
-                            t.a[(uint32_t)__popcll(bA) + lanes_below(bB)] = make_uint4(mdB.x - ex, sdB.x, sdB.y, eB.y - wo.first);
-                            atomicOr(reinterpret_cast<unsigned long long *>(&t.heads[ex >> 6]), 1ull << (ex & 63u));
-                        }
-                        wave_lds_fence();
-                        ACL_MARK(wo, PH_TASKS);
-                        simple_steps<LOCAL, true, true>(t, total, wo, lane, g.edges, reinterpret_cast<const uint4 *>(g.buckets), has, err, make_meta(d_key, Lv + 1u, meta_key(m0)));
-                        if (lane < kHeadWords) t.heads[lane] = 0ull;
-                        wave_lds_fence();
-                        ACL_MARK(wo, PH_PUSH);
-                        return;
-                    }
+                if (!(d_cnrows != 0u && uniform(LD.ckey) == meta_key(m0) && (uniform(LD.flags) & OP_LEAFBIT) != 0u && Lv + 1u <= kMaxLevels && Lv + 1u + uniform(LD.cdl) <= kMaxLevels &&
+                      Lv + 1u + uniform(LD.cmaxd) <= kMaxLevels && lv + uniform(LD.maxd) <= kMaxLevels))
+                    return false;
+                const bool dpair = vbB != 0;
+                if (dpair) next.take();
+                const uint2 *__restrict__ dmeta2 = reinterpret_cast<const uint2 *>(g.meta);
+                const uint32_t rK = d_Kk & 0xFFFFu, rk = d_Kk >> 16;
+                const bool vB = dpair && validB;
+                // Two-hop rows (plan.hpp Snapshot::hop2_*): the row of a state of the self-nested class holds its children (probed, not pushed) AND their children
+                // (probed and pushed, one level further on) -- two of three states of the class are never written, read back, gathered or scheduled.  Taken
+                // where the depth guards hold for BOTH hops (the four conditions above, once more for a state one level further on); at the depth limit the
+                // pair runs on the one-hop rows exactly as it always did.  (uniform)
+                bool h2 = HOP && d_key == g.hop2_slot && d_nrows == g.hop2_nrows && Lv + 2u + uniform(LD.dlevel) <= kMaxLevels &&
+                          Lv + 2u + uniform(LD.dlevel) + uniform(LD.cdl) <= kMaxLevels && Lv + 2u + uniform(LD.dlevel) + uniform(LD.cmaxd) <= kMaxLevels &&
+                          Lv + 1u + uniform(LD.maxd) <= kMaxLevels;
+                const uint32_t gbase = h2 ? g.hop2_base : d_base, gK = h2 ? 1u : rK, gk = h2 ? 0u : rk;
+                // all six gathers in flight together
+                const uint32_t hvA = ans_get<true>(has, valid ? req : wo.first, wo.first), hvB = ans_get<true>(has, vB ? eB.y : wo.first, wo.first);
+                const bool inA = valid && id < d_nrows, inB = vB && eB.x < d_nrows;
+                uint2 mdA = gld(dmeta2, gbase + (inA ? id * gK + gk : 0u)), mdB = gld(dmeta2, gbase + (inB ? eB.x * gK + gk : 0u));
+                // the subject's row of the child's probe is a constant of the REQUEST: for the snapshot's hot hashed class (DevGraph::hot_*) every
+                // request's descriptor was fetched once, when the unit was seeded (s_sd) -- two LDS reads here, not two gathers per pair of segments
+                const bool hotd = d_cbase == g.hot_cbase && d_cnrows == g.hot_cnrows && uniform(LD.ckey) == g.hot_ckey;  // (uniform)
+                const bool okA = valid && e.w < d_cnrows, okB = vB && eB.w < d_cnrows;
+                uint2 sdA, sdB;
+                if (hotd) {
+                    sdA = wo.ssd[valid ? req - wo.first : 0u];
+                    sdB = wo.ssd[vB ? eB.y - wo.first : 0u];
+                } else {
+                    sdA = gld(dmeta2, d_cbase + (okA ? e.w : 0u));
+                    sdB = gld(dmeta2, d_cbase + (okB ? eB.w : 0u));
                 }
+                issue_fence();
+                ACL_MARK(wo, PH_GATHERS);
+                if (!hotd) {
+                    if (!(okA && sdA.y != 0u)) sdA = make_uint2(0u, 1u);  // no row: the reserved empty bucket (what s_sd holds for such a request)
+                    if (!(okB && sdB.y != 0u)) sdB = make_uint2(0u, 1u);
+                }
+                uint32_t degA = (valid && !hvA && inA && mdA.y > mdA.x) ? mdA.y - mdA.x : 0u;
+                uint32_t degB = (vB && !hvB && inB && mdB.y > mdB.x) ? mdB.y - mdB.x : 0u;
+                uint32_t inclA = wave_incl_scan(degA, lane), totA = wave_last(inclA);
+                uint32_t inclB = wave_incl_scan(degB, lane) + totA, total = wave_last(inclB);
+                if (HOP && h2 && total > 64u * kHeadWords) {
+                    // (rare: a pair of two-hop rows alone always fits the window -- kHop2MaxRow -- so this pair mixes them with long one-hop rows.  Expanded
+                    //  again from the one-hop descriptors: a second descriptor trip; only what overflows there too is an overflow of the form)
+                    h2 = false;
+                    mdA = gld(dmeta2, d_base + (inA ? id * rK + rk : 0u));
+                    mdB = gld(dmeta2, d_base + (inB ? eB.x * rK + rk : 0u));
+                    issue_fence();
+                    degA = (valid && !hvA && inA && mdA.y > mdA.x) ? mdA.y - mdA.x : 0u;
+                    degB = (vB && !hvB && inB && mdB.y > mdB.x) ? mdB.y - mdB.x : 0u;
+                    inclA = wave_incl_scan(degA, lane);
+                    inclB = wave_incl_scan(degB, lane) + wave_last(inclA);
+                    total = wave_last(inclB);
+                }
+#if ACL_PROFILE_PHASES  // (instrumented builds: pairs of the two-hop slot expanded from two-hop rows, and those that fell back to the one-hop rows -- depth or window)
+                if (HOP && lane == 0) wo.cold->prof[h2 ? 18 : 19] += 1u;
+#endif
+                if (total > 64u * kHeadWords || __ballot(degA > kMaxRow || degB > kMaxRow)) {
+                    // more children than the head-bit window maps (an average fan-out beyond 16), or a row beyond the enumeration limit: this form has
+                    // no second round (one would have to keep the pair's registers across the steps, and the walk's VGPR budget is used up -- see above).  The batch is
+                    // redone on the level loop and the host switches the form off for this snapshot (kOverflowDirect; a row beyond kMaxRow fails
+                    // the call as it does on every path).
+                    if (lane == 0) *wo.cold->overflow = __ballot(degA > kMaxRow || degB > kMaxRow) ? 2u : kOverflowDirect;
+                    wo.cur = kNoSpace;
+                    return true;
+                }
+                if (!total) return true;
+                const uint64_t bA = __ballot(degA != 0u), bB = __ballot(degB != 0u);
+                const uint32_t cladd = (uniform(LD.dlevel) + 1u) << 13;  // (HOP: a task carries its children's level -- the parent's own + the op's offset + 1)
+                if (degA) {
+                    const uint32_t ex = inclA - degA;
+                    t.a[lanes_below(bA)] = make_uint4(mdA.x - ex, sdA.x, sdA.y, HOP ? ((req - wo.first) << 19) | ((meta & (63u << 13)) + cladd) : req - wo.first);
+                    atomicOr(reinterpret_cast<unsigned long long *>(&t.heads[ex >> 6]), 1ull << (ex & 63u));
+                }
+                if (degB) {
+                    const uint32_t ex = inclB - degB;
+                    t.a[(uint32_t)__popcll(bA) + lanes_below(bB)] = make_uint4(mdB.x - ex, sdB.x, sdB.y, HOP ? ((eB.y - wo.first) << 19) | ((eB.z & (63u << 13)) + cladd) : eB.y - wo.first);
+                    atomicOr(reinterpret_cast<unsigned long long *>(&t.heads[ex >> 6]), 1ull << (ex & 63u));
+                }
+                wave_lds_fence();
+                ACL_MARK(wo, PH_TASKS);
+                if (HOP)
+                    simple_steps<LOCAL, true, true, true>(t, total, wo, lane, g.edges, reinterpret_cast<const uint4 *>(g.buckets), has, err, d_key, h2 ? (1u << 13) : 0u);
+                else
+                    simple_steps<LOCAL, true, true>(t, total, wo, lane, g.edges, reinterpret_cast<const uint4 *>(g.buckets), has, err, make_meta(d_key, Lv + 1u, meta_key(m0)));
+                if (lane < kHeadWords) t.heads[lane] = 0ull;
+                wave_lds_fence();
+                ACL_MARK(wo, PH_PUSH);
+                return true;
+            };
+            if constexpr (E8) {
+                if (!(g.walk_flags & kWalkNoDirect) && (__builtin_expect(lvbits != 0u, 0) ? direct(std::true_type{}) : direct(std::false_type{}))) return;
             }
             simple = lane_op(m0, LA);  // wave-uniform argument
             LB = LA;
@@ -1708,7 +1755,7 @@ __global__ __launch_bounds__(WAVES * 64, ACL_LOCAL_WAVES_PER_SIMD) void k_check_
     }
 #if ACL_PROFILE_PHASES
     ACL_MARK(wo, PH_OTHER);
-    if (lane < 18) atomicAdd(&acl_phase_cycles[lane], (unsigned long long)s_cold[wib].prof[lane]);
+    if (lane < 20) atomicAdd(&acl_phase_cycles[lane], (unsigned long long)s_cold[wib].prof[lane]);
 #endif
     // ---- small host batches (round 5): the caller does not wait in hipStreamSynchronize -- that costs ~5.5 us AFTER the kernel's
     // last store is visible to a spinning host thread (tools/launch_latency.hip: flag visible 6.6 us after the launch call, synchronize returns at
@@ -2624,9 +2671,9 @@ __global__ __launch_bounds__(256) void k_import_gathered(DevFrontier f, uint32_t
 
 #if ACL_PROFILE_PHASES
 }  // namespace acl
-extern "C" int acl_debug_phase_cycles(unsigned long long *out18) {  // variant builds only (tools/phases.py): reads and resets the counters
-    unsigned long long z[18] = {0};
-    if (hipMemcpyFromSymbol(out18, HIP_SYMBOL(acl::acl_phase_cycles), sizeof(z)) != hipSuccess) return 1;
+extern "C" int acl_debug_phase_cycles(unsigned long long *out20) {  // variant builds only (tools/phases.py): reads and resets the counters
+    unsigned long long z[20] = {0};
+    if (hipMemcpyFromSymbol(out20, HIP_SYMBOL(acl::acl_phase_cycles), sizeof(z)) != hipSuccess) return 1;
     return hipMemcpyToSymbol(HIP_SYMBOL(acl::acl_phase_cycles), z, sizeof(z)) == hipSuccess ? 0 : 1;
 }
 namespace acl {

@@ -43,8 +43,13 @@ struct DevGraph {
     // the snapshot's hot hashed class (Snapshot::hot_*, plan.cpp choose_hot_class): the single-launch walk keeps every request's row descriptor of this class
     // in LDS for the length of a unit (kernels.hip, k_check_local's s_sd).  hot_cnrows == 0: none
     uint32_t hot_cbase = 0, hot_cnrows = 0, hot_ckey = 0;
+    // the snapshot's two-hop rows (Snapshot::hop2_*): one {start, end} descriptor per object of hop2_slot's type at meta[hop2_base + id]; the direct form of the
+    // single-launch walk expands states of that slot from them.  hop2_nrows == 0: none (never built, or dropped by a patch)
+    uint32_t hop2_base = 0, hop2_nrows = 0, hop2_slot = 0xFFFFFFFFu;  // hop2_slot: no slot's number while the rows are not in use (none, dropped, or kWalkNoHop2)
 };
 constexpr uint32_t kWalkNoDirect = 1u;
+constexpr uint32_t kWalkNoHop2 = 2u;  // ACL_HOP2=0 (A/B and tests, one library for both forms): the walk reads the one-hop rows even where two-hop rows exist -- the host
+                                      // sets the bit and, with it, hop2_slot to no slot's number: the kernel's one test per pair is the slot compare
 constexpr uint32_t kOverflowPools = 8u;   // level loop on the SHARDED graph, schemas with `&` / `-`: a shard ran out of combine nodes / leaf cells -- the native loop grows the pools and redoes the batch
 constexpr uint32_t kOverflowDirect = 4u;  // single-launch walk's overflow code: "redo, and stop using the direct task lists on this snapshot"
 struct DevReverse {

@@ -335,6 +335,100 @@ void choose_hot_class(Snapshot &s) {
     }
 }
 
+// ---- two-hop rows (Snapshot::hop2_*)
+// The enumerate op of `slot` when the slot is a self-nested sorted class whose states the walk's direct form takes: exactly one plain hashed probe and one
+// enumerate op with authoritative leaf flags that leads back into the slot itself, nothing inlined (every op at dispatch offset 0).  nullptr otherwise.
+const FwdOp *hop2_op_of(const Snapshot &s, uint32_t slot) {
+    if (slot >= s.progs.size()) return nullptr;
+    const SlotProg &p = s.progs[slot];
+    if (p.combine || p.n_probe != 1 || p.n_main != 2 || p.max_dlevel != 0 || (size_t)p.first + 2 > s.ops.size()) return nullptr;
+    const FwdOp &pr = s.ops[p.first], &en = s.ops[p.first + 1];
+    if (pr.flags != OP_PROBE_HASH || pr.nrows == 0 || pr.dlevel != 0) return nullptr;
+    if ((en.flags & (OP_ENUM | OP_LEAFBIT)) != (OP_ENUM | OP_LEAFBIT) || (en.flags & (OP_PUSH_SAME | OP_REFLEX | OP_PROBE_HASH | OP_ALL)) != 0) return nullptr;
+    if (en.key != slot || en.dlevel != 0 || en.nrows == 0 || en.nrows >= kHop2Bit) return nullptr;
+    return &en;
+}
+// The two-hop row of object `id` under `op`, composed from the one-hop rows as they are: false when the object keeps its one-hop row (no grandchild, or
+// more than kHop2MaxRow ids).  Shared by the builder and verify_snapshot.
+bool hop2_compose(const Snapshot &s, const FwdOp &op, uint32_t id, std::vector<uint32_t> *row) {
+    auto desc = [&](uint32_t x) { return s.meta.data() + 2 * ((size_t)op.base + (size_t)x * op.K + op.k); };
+    const uint32_t *md = desc(id);
+    if (md[1] <= md[0] || md[1] - md[0] >= kHop2MaxRow) return false;
+    const uint32_t nc = md[1] - md[0];
+    uint32_t gc[kHop2MaxRow], ng = 0;  // ascending, distinct
+    for (uint32_t e = md[0]; e < md[1]; e++) {
+        const uint32_t c = s.edges[e] & kIdMask;
+        if (c >= op.nrows) continue;
+        const uint32_t *cd = desc(c);
+        for (uint32_t f = cd[0]; f < cd[1]; f++) {
+            const uint32_t g = s.edges[f] & kIdMask;
+            uint32_t *pos = std::lower_bound(gc, gc + ng, g);
+            if (pos != gc + ng && *pos == g) continue;
+            if (nc + ng + 1 > kHop2MaxRow) return false;
+            std::copy_backward(pos, gc + ng, gc + ng + 1);
+            *pos = g;
+            ng++;
+        }
+    }
+    if (!ng) return false;
+    row->clear();
+    for (uint32_t e = md[0]; e < md[1]; e++) row->push_back((s.edges[e] & kIdMask) | kLeafBit);  // probed, never pushed: their children follow
+    for (uint32_t i = 0; i < ng; i++) {
+        const bool leaf = gc[i] >= op.nrows || desc(gc[i])[1] <= desc(gc[i])[0];
+        row->push_back(gc[i] | kHop2Bit | (leaf ? kLeafBit : 0u));
+    }
+    return true;
+}
+// Chooses the class (the qualifying op with the most rows, the lowest slot on a tie) and appends its descriptors to `meta` and its two-hop rows to `edges`.
+void build_hop2(Snapshot &s, uint32_t world) {
+    s.hop2_base = s.hop2_nrows = s.hop2_slot = s.hop2_cls = s.hop2_rows = 0;
+    s.hop2_words = 0;
+    if (world != 1) return;
+    const FwdOp *best = nullptr;
+    uint32_t best_slot = 0;
+    for (uint32_t slot = 0; slot < s.nslots; slot++) {
+        const FwdOp *op = hop2_op_of(s, slot);
+        if (op && (!best || op->nrows > best->nrows)) best = op, best_slot = slot;
+    }
+    if (!best) return;
+    const FwdOp op = *best;  // (a copy: nothing below touches s.ops, but the arrays it indexes grow)
+    const RelLayout &l = s.lay[best_slot];
+    uint32_t cls = ~0u;
+    for (size_t k = 0; k < l.cls.size(); k++)
+        if (l.cls[k].live && !l.cls[k].hashed && l.cls[k].ks == op.k) cls = (uint32_t)k;
+    if (cls == ~0u || l.meta_base != op.base || l.nrows != op.nrows) return;
+    const size_t meta0 = s.meta.size(), edges0 = s.edges.size();
+    const uint32_t base = (uint32_t)(meta0 / 2);
+    s.meta.resize(meta0 + 2 * (size_t)op.nrows, 0);
+    std::vector<uint32_t> row;
+    uint32_t rows = 0;
+    for (uint32_t id = 0; id < op.nrows; id++) {
+        uint32_t d0, d1;
+        if (hop2_compose(s, op, id, &row)) {
+            d0 = (uint32_t)s.edges.size();
+            s.edges.insert(s.edges.end(), row.begin(), row.end());
+            d1 = (uint32_t)s.edges.size();
+            rows++;
+        } else {
+            const uint32_t *md = s.meta.data() + 2 * ((size_t)op.base + (size_t)id * op.K + op.k);
+            d0 = md[0];
+            d1 = md[1];
+        }
+        s.meta[2 * ((size_t)base + id)] = d0;
+        s.meta[2 * ((size_t)base + id) + 1] = d1;
+    }
+    if (!rows) {  // nothing nests two deep: the walk has no use for a second descriptor table
+        s.meta.resize(meta0);
+        return;
+    }
+    s.hop2_base = base;
+    s.hop2_nrows = op.nrows;
+    s.hop2_slot = best_slot;
+    s.hop2_cls = cls;
+    s.hop2_rows = rows;
+    s.hop2_words = s.edges.size() - edges0;
+}
+
 }  // namespace
 
 // tables are sized for objects that do not exist yet, so that writes naming new objects can be patched in
@@ -384,6 +478,7 @@ void debug_rows_report(const Store &store, const Snapshot &s) {
                     "slow %llu, largest %u buckets, largest fast %u buckets\n",
             (unsigned long long)rows, (unsigned long long)two, (unsigned long long)nb_two, (unsigned long long)ids, (unsigned long long)nbs,
             nbs ? ids / (4.0 * nbs) : 0.0, nbs * 16 / 1e6, (unsigned long long)slow, nb_max, nb_max_fast);
+    fprintf(stderr, "[aclgpu] two-hop rows: %u descriptors, %u two-hop rows, %llu words\n", s.hop2_nrows, s.hop2_rows, (unsigned long long)(s.hop2_nrows ? s.hop2_words : 0));
     fflush(stderr);
 }
 
@@ -668,6 +763,7 @@ void build_forward(Store &store, int64_t now, Snapshot *snap, ShardSpec shard) {
         }
     }
     s.lay = std::move(lay);
+    build_hop2(s, shard.world);  // (behind the leaf bits: a grandchild's flag is composed from the rows as they stand)
     *snap = std::move(s);
     debug_rows_report(store, *snap);
 }
@@ -753,8 +849,17 @@ struct Patcher {
     // an object of type t got its first enumerable row: edges elsewhere may still flag it as a leaf.  Leaf flags are
     // an optimisation; switch their authority off for every op whose children are of type t (the kernel then looks
     // at the child's rows, which are exact) until the next rebuild recomputes them.
+    // The two-hop rows are composed from the one-hop rows of their class and from its leaf flags: when either changes they are dropped, not patched -- the
+    // walk reads the one-hop rows until the next build (DevGraph takes hop2_nrows from the snapshot with every pass).  Their words are garbage from here on.
+    void drop_hop2() {
+        if (!s.hop2_nrows) return;
+        s.garbage_words += s.hop2_words + 2 * (uint64_t)s.hop2_nrows;
+        s.hop2_nrows = s.hop2_rows = 0;
+        s.hop2_words = 0;
+    }
     void distrust_leaf_flags(int t) {
         const Schema &sc = store.schema();
+        if (s.hop2_nrows && sc.slot_owner[s.hop2_slot].first == t) drop_hop2();
         for (FwdOp &op : s.ops)
             if ((op.flags & OP_ENUM) && (op.flags & OP_LEAFBIT) && sc.slot_owner[op.key].first == t) {
                 op.flags &= ~(uint32_t)OP_LEAFBIT;
@@ -872,6 +977,7 @@ bool patch_forward(Store &store, int64_t now, Snapshot *snap, ShardSpec shard, s
         } else {
             uint32_t pos;
             const bool have = P.sorted_find(P.sdesc(l, cl, res), sid, &pos);
+            if (want != have && s.hop2_nrows && (uint32_t)c.slot == s.hop2_slot && (uint32_t)c.cls == s.hop2_cls) P.drop_hop2();  // group nesting edited
             if (want && !have) P.sorted_add(c.slot, c.cls, l, cl, res, sid);
             else if (!want && have) P.sorted_remove(l, cl, res, sid);
             if (want != have) s.patched++;
@@ -982,6 +1088,33 @@ bool verify_snapshot(Store &store, int64_t now, const Snapshot &s, ShardSpec sha
                 if (stored != live) return bad(rel + ": " + std::to_string(stored) + " stored vs " + std::to_string(live) + " live relationships");
             }
         }
+    }
+    // two-hop rows: every descriptor against the one-hop rows it was composed from (ids, order, both flag bits, the cap); an object without a
+    // two-hop row must name its one-hop row
+    if (s.hop2_nrows) {
+        const FwdOp *hop = hop2_op_of(s, s.hop2_slot);
+        if (shard.world != 1 || !hop) return bad("two-hop rows on a class that does not qualify for them");
+        const FwdOp op = *hop;
+        if (op.nrows != s.hop2_nrows || 2 * ((size_t)s.hop2_base + s.hop2_nrows) > s.meta.size()) return bad("two-hop descriptors do not cover the class's objects");
+        if (s.hop2_cls >= s.lay[s.hop2_slot].cls.size() || s.lay[s.hop2_slot].cls[s.hop2_cls].hashed || s.lay[s.hop2_slot].cls[s.hop2_cls].ks != op.k)
+            return bad("two-hop rows name the wrong class");
+        std::vector<uint32_t> row;
+        uint32_t rows = 0;
+        uint64_t words = 0;
+        for (uint32_t id = 0; id < op.nrows; id++) {
+            const uint32_t *d = s.meta.data() + 2 * ((size_t)s.hop2_base + id);
+            const uint32_t *md = s.meta.data() + 2 * ((size_t)op.base + (size_t)id * op.K + op.k);
+            if (d[1] < d[0] || d[1] > s.edges.size()) return bad("two-hop descriptor out of range");
+            if (!hop2_compose(s, op, id, &row)) {
+                if (d[0] != md[0] || d[1] != md[1]) return bad("object without a two-hop row does not name its one-hop row");
+                continue;
+            }
+            if (row.size() > kHop2MaxRow) return bad("two-hop row beyond the cap");
+            if (d[1] - d[0] != row.size() || !std::equal(row.begin(), row.end(), s.edges.begin() + d[0])) return bad("stale two-hop row");
+            rows++;
+            words += row.size();
+        }
+        if (rows != s.hop2_rows || words != s.hop2_words) return bad("two-hop row count does not match the rows");
     }
     // leaf flags: wherever an op still trusts them, a flagged child must really have nothing to enumerate
     for (const FwdOp &op : s.ops) {

@@ -92,6 +92,11 @@ ACL_HD inline uint32_t hrow_bucket2(uint32_t id, uint32_t y, uint32_t h1) {
 }
 constexpr uint32_t kLeafBit = 0x80000000u;  // object ids are < 2^31
 constexpr uint32_t kIdMask = 0x7FFFFFFFu;
+// Two-hop rows (Snapshot::hop2_*): bit 30 of an edge says "this id is a GRANDCHILD of the row's object": its state lies one dispatch level further on than a
+// child's.  Only rows of a type with fewer than 2^30 objects carry it; every other row's ids keep all 31 bits.
+constexpr uint32_t kHop2Bit = 1u << 30;
+constexpr uint32_t kHop2MaxRow = 16;  // children + grandchildren of a two-hop row, at most: 64 * kHeadWords / 128 (kernels.hip) -- a pair of segments of such rows
+                                      // always fits the direct form's head-bit window
 
 struct FwdOp {        // 32 B
     uint32_t flags;   // OP_* bits; PROBE|ENUM may be combined (userset class)
@@ -174,6 +179,20 @@ struct Snapshot {
     // (what the walk's deep levels probe every child in: `group#member@user` on a nested-groups schema); the one with the most subject rows where several
     // qualify, hot_cnrows == 0 where none does.  A hint: the walk fetches this class's row descriptor once per request instead of once per entry.
     uint32_t hot_cbase = 0, hot_cnrows = 0, hot_ckey = 0;
+    // Two-hop rows of the one self-nested sorted class (`group#member@group#member`): the enumerate op (OP_ENUM | OP_LEAFBIT) whose target slot is its own slot
+    // and whose child program is what the walk's direct form takes (one OP_PROBE_HASH + that same op); the one with the most rows where several qualify.
+    //   meta[hop2_base + id] = {start, end} into edges, one descriptor per object of the type (hop2_nrows, headroom included)
+    //   two-hop row of g  = [children of g, ascending, every one with kLeafBit: "probe, do not push" -- their expansion is already in the row]
+    //                    ++ [union of the children's children, ascending, distinct, each | kHop2Bit, | kLeafBit where it has nothing to enumerate]
+    //                       for a g with >= 1 grandchild and children + grandchildren <= kHop2MaxRow;
+    //   any other g       = the descriptor of its ordinary (one-hop) row: no copy.
+    // An id that is child AND grandchild is in both parts: two states, at different levels.  Which groups a group's children contain does not depend on the
+    // request; it changes when somebody edits group nesting, and then the rows are DROPPED (patch_forward: hop2_nrows = 0 -- the walk reads the one-hop rows,
+    // which are exact, until the next build), never patched.  Built for unsharded snapshots, non-combine slots and types of fewer than 2^30 objects.
+    uint32_t hop2_base = 0, hop2_nrows = 0;  // hop2_nrows == 0: no two-hop rows (none qualifies, or dropped)
+    uint32_t hop2_slot = 0, hop2_cls = 0;    // the class's slot and its class index in lay[hop2_slot].cls
+    uint32_t hop2_rows = 0;                  // rows that ARE two-hop (the others point at their one-hop row)
+    uint64_t hop2_words = 0;                 // edge words they take
     std::vector<uint32_t> bexpr;  // boolean programs of the combine slots (word 0 unused: SlotProg::combine == 0 means none)
     bool has_combine = false;     // some slot's rewrite uses `&` / `-`: evaluations run the kernels' combine instantiations
     std::vector<uint8_t> slot_nonmono;  // [nslots] the slot's value can depend on a combine program: LookupResources = candidates + a forward Check

@@ -25,7 +25,7 @@ d_items = torch.from_numpy(items.view(np.uint8).copy()).cuda()
 d_perm = torch.zeros(n, dtype=torch.uint8, device="cuda")
 d_err = torch.zeros(n, dtype=torch.int32, device="cuda")
 lib = C.CDLL(os.environ["ACLGPU_LIB"])
-out = (C.c_ulonglong * 18)()
+out = (C.c_ulonglong * 20)()
 for _ in range(3):
     e.check_bulk_ids_device(d_items.data_ptr(), n, d_perm.data_ptr(), d_err.data_ptr())
 torch.cuda.synchronize()
@@ -51,4 +51,8 @@ if out[12]:
 if out[16]:
     print(f"  simple-expansion steps per batch {out[16] / K / 1e3:.0f} k, windows without a valid lane {out[17] / K / 1e3:.0f} k = {out[17] / out[16]:.2f} per step "
           f"({100.0 * out[17] / (3 * out[16]):.1f} % of the windows of full-width steps)")
+# counters of the two-hop rows (slots 18-19): pairs of the self-nested class's states expanded from two-hop rows, and pairs that fell back to the one-hop rows
+# (a depth guard of the second hop, or a pair beyond the head-bit window)
+if out[18] or out[19]:
+    print(f"  pairs expanded from two-hop rows per batch {out[18] / K / 1e3:.1f} k, fallen back to one-hop rows {out[19] / K / 1e3:.2f} k; two-hop rows in the snapshot {st_['hop2_rows']}")
 e.close()

@@ -378,6 +378,52 @@ int acl_watch_wait(acl_engine_t *h, uint64_t after_revision, const int *types, i
  * CheckPermission per update, watch.go:50-67); cb once per update, in commit order, with the decision (permissionship, per-item error). */
 typedef void (*acl_watch_check_cb)(void *user, uint64_t revision, int32_t op, const acl_relationship_t *rel, uint8_t permissionship, int32_t err);
 int acl_watch_recheck(acl_engine_t *h, uint64_t after_revision, const acl_check_item_t *templ, acl_watch_check_cb cb, void *user, uint64_t *revision_out);
+/* ---- watch sets: which resources did each open watch gain or lose, whatever kind of write caused it ----
+ * RunWatch subscribes to relationship updates of the WATCHED type only (watch.go:29-31) and issues one CheckPermission per update
+ * (watch.go:50-67); the decisions feed the filter's allowedNames (responsefilterer.go:689-705).  acl_watch_recheck above is that path.  It cannot
+ * see a change that arrives as an update of another type -- a user put into a group, a group nested into a group, a namespace grant, an expiring
+ * grant running out -- although any of them changes which objects the watcher may see.  A watch set answers the real question: it keeps, in device
+ * memory, the LookupResources row of every watcher (subjects of one class against one (type, permission)) as of the last poll; a poll walks all
+ * watchers on the current snapshot in one batch, XORs new against old rows on the device and brings back only the changes.  This goes beyond the
+ * reference on purpose; acl_watch_poll / _wait / _recheck are unchanged.
+ *  - poll: afterwards the set's rows are the watchers' LookupResources answers on ONE snapshot, *revision_out its revision.  *changes_out (release
+ *    with acl_free; NULL when *n_out == 0) is new XOR old for every watcher, ascending by (watcher, resource_id).  A watcher added without
+ *    ACL_WATCHER_FROM_NOW starts from the empty row, as allowedNames starts empty (responsefilterer.go:509): its first poll reports all it holds as
+ *    gained.  A poll that finds the snapshot unchanged and no watcher added since the last one touches no device and reports nothing.  Polls of one
+ *    set serialise; polls of different sets and every other call run beside them.
+ *  - failure is atomic: a poll that fails (ACL_ERR_DEPTH from a candidate's confirming Check under `&` / `-` unless ACL_FLAG_LENIENT_LOOKUP,
+ *    RESOURCE_EXHAUSTED, CANCELLED, DEADLINE_EXCEEDED) leaves rows and baseline as they were; the next successful poll reports the whole difference.
+ *  - ids: watcher ids count up from 0 and are never reused within a set.  A watcher's subject is interned pinned, as acl_intern does: its id is not
+ *    recycled under the watch -- and, as with acl_intern, the pin is for the life of the schema: remove / close do not release it, so the pinned
+ *    ids grow with the number of DISTINCT subjects ever watched (one name-table entry each), not with the number of watches.  Resource ids in the changes follow the contract of a LookupResources bitmap: resolve names (acl_object_name_copy)
+ *    within the recycling quarantine.
+ *  - refusals: sharded engine FAILED_PRECONDITION; store-only engine UNAVAILABLE (at open); unknown type / permission / subject relation
+ *    FAILED_PRECONDITION; unknown watcher, ill-formed subject id or a row buffer too small INVALID_ARGUMENT; more than 1 GiB of device memory for
+ *    the set's two row arrays RESOURCE_EXHAUSTED (at add, or at a poll when the type has grown).  A poll whose difference is more than 2^28
+ *    records (4 GiB of them) fails with RESOURCE_EXHAUSTED too, and since a failed poll keeps the baseline the next one meets the same difference
+ *    or a larger one: that state is PERMANENT for the set -- close it and open sets with fewer watchers (add after an initial list with
+ *    ACL_WATCHER_FROM_NOW, which reports nothing, rather than from the empty row).  acl_close releases the sets still open; a set does
+ *    not outlive the schema it was opened under (acl_load_bootstrap: close it and open a new one).
+ *  - lifetime: add / remove / poll / row / stats on one set may run beside each other (they serialise), but acl_watch_set_close -- like acl_close
+ *    for the engine -- must not run beside any other call on THAT set, and no call may be made on it afterwards: the set is freed.
+ *  - replicas (acl_open_replicas): a set is bound to the device of the replica that open picks and its polls run there; writes reach every replica
+ *    before they return, so a poll sees every write that returned before it. */
+typedef struct acl_watch_set acl_watch_set_t;
+typedef struct { uint32_t watcher, resource_id, gained /* 1 gained, 0 lost */, reserved; } acl_watch_change_t;
+#define ACL_WATCHER_FROM_NOW 1u   /* baseline = what the subject holds at the first poll after the add: nothing is reported for it */
+int acl_watch_set_open(acl_engine_t *h, int rtype, int permission, int stype, int srel /* -1 none */, acl_watch_set_t **out);
+int acl_watch_set_add(acl_engine_t *h, acl_watch_set_t *s, const char *subject_id, uint32_t flags, uint32_t *watcher_out);
+int acl_watch_set_remove(acl_engine_t *h, acl_watch_set_t *s, uint32_t watcher);
+int acl_watch_set_poll(acl_engine_t *h, acl_watch_set_t *s, const acl_call_opts_t *opts,
+                       acl_watch_change_t **changes_out /* acl_free */, size_t *n_out, uint64_t *revision_out);
+/* the watcher's row as of the last successful poll (empty before the first): `words` >= the row's width, the rest is zeroed */
+int acl_watch_set_row(acl_engine_t *h, acl_watch_set_t *s, uint32_t watcher, uint32_t *bitmap_out, size_t words);
+/* per set: polls asked for, polls that walked, change records reported */
+int acl_watch_set_stats(acl_engine_t *h, acl_watch_set_t *s, uint64_t *polls, uint64_t *walks, uint64_t *changes);
+int acl_watch_set_close(acl_engine_t *h, acl_watch_set_t *s);
+/* test hook (GPU): runs the diff kernels alone on caller rows (host arrays [n_rows][words], packed); old rows may be narrower than new ones */
+int acl_selfcheck_rows_diff(acl_engine_t *h, const uint32_t *old_rows, size_t old_words, const uint32_t *new_rows, size_t new_words,
+                            size_t n_rows, acl_watch_change_t **changes_out, size_t *n_out);
 /* Micro-batching front-end for the proxy's call shape -- many concurrent 1-item checks (check.go:76-94 one goroutine
  * per check expression, watch.go:50 one per update).  acl_check_one blocks its caller; while a batcher runs,
  * concurrent callers share ONE device pass (drained after at most max_wait_us or when max_items are waiting). */

@@ -29,12 +29,16 @@ type Config struct {
 	BatchMaxItems      uint32 // 0 = no micro-batching of single checks
 	BatchMaxWaitMicros uint32
 	Contexts           uint32 // evaluations in flight on the device at once (own HIP stream each); 0 = default (4)
+	WatchSets          bool   // watches report what a watcher gains or loses on ANY write (watch_set.go: OpenWatchSet / Watch / Run) instead of re-checking
+	                          // updates of the watched type only (watch.go:29-31,50-67); off by default -- OpenWatchSet answers FailedPrecondition without
+	                          // it -- because it reports changes the reference's watch misses
 }
 
 // Engine owns one acl_engine_t.  All methods are safe for concurrent use (the C ABI is).
 type Engine struct {
 	h  *C.acl_engine_t
 	cq *completions // non-nil while the micro-batcher runs: single checks go through the completion queue (completions.go)
+	watchSets bool  // Config.WatchSets: OpenWatchSet refuses without it
 }
 
 func lastError(rc C.int) error {
@@ -71,11 +75,11 @@ func Open(cfg Config, schema, relationships string) (*Engine, error) {
 			C.acl_close(h)
 			return nil, lastError(rc)
 		}
-		e := &Engine{h: h}
+		e := &Engine{h: h, watchSets: cfg.WatchSets}
 		e.startPoller()
 		return e, nil
 	}
-	return &Engine{h: h}, nil
+	return &Engine{h: h, watchSets: cfg.WatchSets}, nil
 }
 
 // OpenBootstrap replaces spicedb.NewServer(ctx, bootstrapFilePath, bootstrapContent) (reference pkg/spicedb/spicedb.go:18-24) for

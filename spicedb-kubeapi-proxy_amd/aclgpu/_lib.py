@@ -30,6 +30,8 @@ SYMBOLS = [
     "acl_lookup_one_submit", "acl_lookup_completions", "acl_prefilter_response", "acl_open_replicas", "acl_replica_calls", "acl_watch_wait", "acl_watch_recheck", "acl_load_bootstrap_yaml",
     "acl_check_bulk_v_opts", "acl_object_name_copy", "acl_resolve_bulk_v", "acl_check_bulk_packed", "acl_check_bulk_keep_v", "acl_check_bulk_keep_packed", "acl_selfcheck_json_array", "acl_bitmap_names",
     "acl_lookup_subjects_batch", "acl_lookup_subjects", "acl_shard_subjects_bulk", "acl_shard_subjects_bulk_rccl",
+    "acl_watch_set_open", "acl_watch_set_add", "acl_watch_set_remove", "acl_watch_set_poll", "acl_watch_set_row", "acl_watch_set_stats", "acl_watch_set_close",
+    "acl_selfcheck_rows_diff",
 ]
 
 
@@ -67,6 +69,11 @@ class CheckItem(C.Structure):
 class Completion(C.Structure):
     """acl_completion_t: one answered acl_check_one_submit."""
     _fields_ = [("tag", C.c_uint64), ("rc", C.c_int32), ("err", C.c_int32), ("perm", C.c_uint8), ("pad", C.c_uint8 * 3)]
+
+
+class WatchChange(C.Structure):
+    """acl_watch_change_t: one resource a watcher of a watch set gained (1) or lost (0)."""
+    _fields_ = [("watcher", C.c_uint32), ("resource_id", C.c_uint32), ("gained", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class ListRequest(C.Structure):
@@ -219,6 +226,14 @@ def load():
     L.acl_lookup_subjects.argtypes = [H, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(CallOpts), C.POINTER(C.POINTER(C.c_uint32)),
                                       C.POINTER(C.c_size_t), C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.POINTER(C.c_uint32))]
     L.acl_free.restype = None
+    L.acl_watch_set_open.argtypes = [H, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    L.acl_watch_set_add.argtypes = [H, C.c_void_p, C.c_char_p, C.c_uint32, C.POINTER(C.c_uint32)]
+    L.acl_watch_set_remove.argtypes = [H, C.c_void_p, C.c_uint32]
+    L.acl_watch_set_poll.argtypes = [H, C.c_void_p, C.POINTER(CallOpts), C.POINTER(C.POINTER(WatchChange)), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]
+    L.acl_watch_set_row.argtypes = [H, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t]
+    L.acl_watch_set_stats.argtypes = [H, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.acl_watch_set_close.argtypes = [H, C.c_void_p]
+    L.acl_selfcheck_rows_diff.argtypes = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.POINTER(WatchChange)), C.POINTER(C.c_size_t)]
     L.acl_check_one_opts.argtypes = [H, C.POINTER(CheckItem), C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(CallOpts)]
     L.acl_check_one_submit.argtypes = [H, C.POINTER(CheckItem), C.c_uint64]
     L.acl_check_completions.argtypes = [H, C.POINTER(Completion), C.c_size_t, C.c_int64, C.POINTER(C.c_size_t)]

@@ -17,7 +17,7 @@ from __future__ import annotations
 from dataclasses import dataclass, field
 from typing import Iterator, List, Optional
 
-from .engine import (AclError, Engine, OP_CREATE, OP_DELETE, OP_TOUCH, PERM_HAS, PRE_MUST_MATCH, PRE_MUST_NOT_MATCH)
+from .engine import (AclError, ERR_DEADLINE_EXCEEDED, ERR_FAILED_PRECONDITION, Engine, OP_CREATE, OP_DELETE, OP_TOUCH, PERM_HAS, PRE_MUST_MATCH, PRE_MUST_NOT_MATCH)
 
 # authzed.api.v1 enums
 PERMISSIONSHIP_UNSPECIFIED, PERMISSIONSHIP_NO_PERMISSION, PERMISSIONSHIP_HAS_PERMISSION, PERMISSIONSHIP_CONDITIONAL_PERMISSION = 0, 1, 2, 3
@@ -327,3 +327,41 @@ class PrefilterResult:
 def is_allowed(pair: CheckBulkPermissionsPair) -> bool:
     """The reference's allow rule: no error and HAS_PERMISSION (pkg/authz/check.go:55-69)."""
     return pair.error is None and pair.item is not None and pair.item.permissionship == PERM_HAS
+
+
+def run_watch_set(engine: Engine, watch_set, sinks: Optional[dict] = None, polls: Optional[int] = None, timeout_s: Optional[float] = None) -> Iterator[tuple]:
+    """THE poll loop of one watch set -- the mirror of RunWatch's loop body (reference pkg/authz/watch.go:38-108) for all its watchers at once.
+    Where the reference re-checks the object of every update of the watched type (watch.go:50-67) and sends resultChange{allowed, namespacedName}
+    (watch.go:103-108), this waits for ANY committed write (acl_watch_wait over all types), polls the set and, per change, calls
+    sinks[watcher](allowed, object_id) when that watcher has a sink and yields (allowed, object_id, watcher) -- the changes the reference's watch
+    cannot hear (a membership, a nesting, a namespace grant) included.
+
+    A poll consumes the changes of EVERY watcher of the set (it moves all baselines), so a set has one loop: every record is handed on, none is
+    filtered away, and a second run_watch_set on a set whose loop is still open raises FAILED_PRECONDITION.  `sinks` may be changed by the caller
+    while the loop runs (a watch opens: WatchSet.add, then its sink; a watch closes: its sink goes, then WatchSet.remove).
+    polls: stop after that many polls (None: for ever); timeout_s: how long one wait may block before it polls anyway (expirations arrive
+    without a write)."""
+    if getattr(watch_set, "_poller", False):
+        raise AclError(ERR_FAILED_PRECONDITION, "this watch set already has its poll loop: a second poller would consume the other watchers' changes")
+    watch_set._poller = True
+    try:
+        rev = engine.revision
+        done = 0
+        while polls is None or done < polls:
+            _rev, recs = watch_set.poll()
+            done += 1
+            for r in recs:
+                w, allowed, oid = int(r["watcher"]), bool(r["gained"]), engine.object_name(watch_set._rt, int(r["resource_id"]))
+                sink = sinks.get(w) if sinks else None
+                if sink is not None:
+                    sink(allowed, oid)
+                yield allowed, oid, w
+            if polls is not None and done >= polls:
+                return
+            try:
+                rev = engine.watch_wait(rev, (), timeout_s=timeout_s)
+            except AclError as ex:
+                if ex.code != ERR_DEADLINE_EXCEEDED:
+                    raise
+    finally:
+        watch_set._poller = False

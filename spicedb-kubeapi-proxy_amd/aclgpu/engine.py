@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import CallOpts, CheckItem, Completion, Config, Filter, READ_CB, Relationship, Stats, Update, WATCH_CB, WATCH_CHECK_CB
+from ._lib import CallOpts, CheckItem, Completion, Config, Filter, READ_CB, Relationship, Stats, Update, WATCH_CB, WATCH_CHECK_CB, WatchChange
 
 PERM_UNSPECIFIED, PERM_NO, PERM_HAS, PERM_CONDITIONAL = 0, 1, 2, 3
 OP_CREATE, OP_TOUCH, OP_DELETE = 1, 2, 3
@@ -26,6 +26,9 @@ NO_RELATION = 0xFFFF
 ITEM_DTYPE = np.dtype([("resource_type", "<u2"), ("permission", "<u2"), ("resource_id", "<u4"), ("subject_type", "<u2"),
                        ("subject_relation", "<u2"), ("subject_id", "<u4")])
 assert ITEM_DTYPE.itemsize == 16
+WATCHER_FROM_NOW = 1  # ACL_WATCHER_FROM_NOW
+WATCH_CHANGE_DTYPE = np.dtype([("watcher", "<u4"), ("resource_id", "<u4"), ("gained", "<u4"), ("reserved", "<u4")])  # acl_watch_change_t
+assert WATCH_CHANGE_DTYPE.itemsize == C.sizeof(WatchChange) == 16
 
 
 class AclError(Exception):
@@ -540,6 +543,35 @@ class Engine:
         self._check(self._L.acl_watch_recheck(self._h, after_revision, C.byref(templ), WATCH_CHECK_CB(cb), None, C.byref(cur)))
         return out, cur.value
 
+    # ---- watch sets (include/aclgpu.h "watch sets": what every open watch gained or lost, whatever kind of write caused it)
+    def watch_set(self, rt, perm, st, srel="") -> "WatchSet":
+        """Opens a watch set for subjects `st[#srel]` against `rt#perm`.  An unknown type, permission or subject relation: FAILED_PRECONDITION."""
+        sr = self.relation_id(st, srel)
+        if srel and sr < 0:
+            sr = -2  # (a relation that does not exist is not "no relation")
+        out = C.c_void_p()
+        self._check(self._L.acl_watch_set_open(self._h, self.type_id(rt), self.relation_id(rt, perm), self.type_id(st), sr, C.byref(out)))
+        return WatchSet(self, out, rt)
+
+    def _changes(self, recs, n):
+        try:
+            if not n:
+                return np.zeros(0, dtype=WATCH_CHANGE_DTYPE)
+            return np.ctypeslib.as_array(C.cast(recs, C.POINTER(C.c_uint32)), shape=(n * 4,)).copy().view(WATCH_CHANGE_DTYPE)
+        finally:
+            if recs:
+                self._L.acl_free(recs)
+
+    def selfcheck_rows_diff(self, old_rows: np.ndarray, new_rows: np.ndarray):
+        """Test hook: the diff kernels alone on [n, old_words] / [n, new_words] uint32 rows -> records (WATCH_CHANGE_DTYPE; watcher = row)."""
+        old_rows = np.ascontiguousarray(old_rows, dtype=np.uint32)
+        new_rows = np.ascontiguousarray(new_rows, dtype=np.uint32)
+        assert old_rows.ndim == new_rows.ndim == 2 and old_rows.shape[0] == new_rows.shape[0]
+        recs, n = C.POINTER(WatchChange)(), C.c_size_t()
+        self._check(self._L.acl_selfcheck_rows_diff(self._h, old_rows.ctypes.data, old_rows.shape[1], new_rows.ctypes.data, new_rows.shape[1], new_rows.shape[0],
+                                                    C.byref(recs), C.byref(n)))
+        return self._changes(recs, n.value)
+
     def batcher_start(self, max_items: int = 4096, max_wait_us: int = 200):
         self._check(self._L.acl_batcher_start(self._h, max_items, max_wait_us))
 
@@ -732,3 +764,49 @@ class Engine:
 
     def set_timing(self, on: bool):
         self._check(self._L.acl_set_timing(self._h, 1 if on else 0))
+
+
+class WatchSet:
+    """One acl_watch_set_t: the LookupResources rows of many watchers of one (type, permission), kept on the device between polls."""
+
+    def __init__(self, engine: Engine, handle, rtype: str):
+        self._e, self._s, self._rt = engine, handle, rtype
+
+    def add(self, sid: str, from_now: bool = False) -> int:
+        """-> the watcher's id.  from_now: its baseline is what it holds at the next poll (nothing reported for it); else the empty row."""
+        w = C.c_uint32()
+        self._e._check(self._e._L.acl_watch_set_add(self._e._h, self._s, _b(sid), WATCHER_FROM_NOW if from_now else 0, C.byref(w)))
+        return w.value
+
+    def remove(self, w: int):
+        self._e._check(self._e._L.acl_watch_set_remove(self._e._h, self._s, int(w)))
+
+    def poll(self, cancel=None, timeout_s=None):
+        """-> (revision, records): records is a WATCH_CHANGE_DTYPE array ordered by (watcher, resource_id); gained = 1, lost = 0."""
+        recs, n, rev = C.POINTER(WatchChange)(), C.c_size_t(), C.c_uint64()
+        o = Engine._opts(cancel, timeout_s)
+        self._e._check(self._e._L.acl_watch_set_poll(self._e._h, self._s, C.byref(o) if o else None, C.byref(recs), C.byref(n), C.byref(rev)))
+        return rev.value, self._e._changes(recs, n.value)
+
+    def row(self, w: int) -> np.ndarray:
+        """The watcher's row as of the last successful poll: sorted resource ids."""
+        words = max(1, (self._e.object_count(self._rt) + 31) // 32)
+        bm = np.zeros(words, dtype=np.uint32)
+        self._e._check(self._e._L.acl_watch_set_row(self._e._h, self._s, int(w), bm.ctypes.data, words))
+        return np.flatnonzero(np.unpackbits(bm.view(np.uint8), bitorder="little")).astype(np.uint32)
+
+    def stats(self) -> dict:
+        p, w, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._e._check(self._e._L.acl_watch_set_stats(self._e._h, self._s, C.byref(p), C.byref(w), C.byref(c)))
+        return {"polls": p.value, "walks": w.value, "changes": c.value}
+
+    def close(self):
+        if self._s is not None and getattr(self._e, "_h", None):
+            self._e._check(self._e._L.acl_watch_set_close(self._e._h, self._s))
+        self._s = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()

@@ -137,6 +137,7 @@ void acl_close(acl_engine_t *h) {
     intern_pool_destroy(h);
     (void)acl_shard_rccl_destroy(h);
     compaction_join(h);
+    watch_sets_release(h);
     if (h->store_only) {
         delete h;
         return;

@@ -1,7 +1,7 @@
 // engine_internal.hpp -- shared by the translation units behind the C ABI (engine.cpp: the ABI functions, open / close;
 // engine_snapshot.cpp, engine_pass.cpp, engine_intern.cpp, engine_lookup.cpp, engine_keep.cpp: the core, by concern;
 // engine_shard.cpp: acl_shard_*, engine_callers.cpp: keep mask / bitmap test / watch / micro-batcher,
-// engine_async.cpp: submit/wait + pinned host buffers).
+// engine_async.cpp: submit/wait + pinned host buffers, engine_watchset.cpp: watch sets).
 //
 // Threading model (the seam is called from arbitrary goroutines: reference pkg/authz/check.go:77-93,
 // responsefilterer.go:165, watch.go:50):
@@ -437,6 +437,9 @@ struct acl_engine {
         }
         feed_cv.notify_all();
     }
+    // open watch sets (engine_watchset.cpp): acl_close releases what is left
+    std::mutex watch_sets_mu;
+    std::vector<struct acl_watch_set *> watch_sets;
     uint32_t max_sub_batch = 1u << 20;
     uint32_t local_max_items = 1u << 20;  // batches up to this size take the single-launch path (k_check_local) first; 0 = never.  Measured on C4
                                           // (profiles/r02_walk_vs_levels.txt): faster than the level loop at every batch size, 1.5x at 262 144 items
@@ -567,7 +570,8 @@ int check_device(acl_engine *h, PassCtx *c, const uint4 *d_items, size_t n, uint
 int check_ids_host(acl_engine *h, PassCtx *c, const acl_item_t *items, size_t n, uint8_t *perm_out, int32_t *err_out, bool items_on_device = false);  // items_on_device: c->d_items already holds them (items is not read)
 int lookup_candidate_error(acl_engine *h, int32_t code, uint32_t id, uint32_t sid);  // fails a LookupResources call with a candidate's Check error (lookups.go:75-83)
 int lookup_batch(acl_engine *h, PassCtx *c, int rtype, int perm, int stype, int srel, const uint32_t *sids, size_t n, uint32_t *bitmaps, size_t words,
-                 uint64_t *counts);
+                 uint64_t *counts, uint32_t *d_dst = nullptr /* watch sets: the rows stay on the device (engine_lookup.cpp) */, size_t dstride = 0);
+void watch_sets_release(acl_engine_t *h);  // engine_watchset.cpp: acl_close frees the sets still open
 bool empty(const char *s);
 FilterText to_filter(const acl_filter_t *f);
 // strings -> interned item; returns 0 or the per-item error the pair carries (check.go:55).  Caller holds names_mu shared.

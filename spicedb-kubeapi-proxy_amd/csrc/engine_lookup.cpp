@@ -7,17 +7,19 @@ namespace aclint {
 
 // Single-launch LookupResources over m subjects already staged in c->h_in (pinned).  Result rows go to `bitmaps` directly when the
 // caller's buffer is pinned (acl_host_alloc), else through the context's pinned staging.  kTakeLevelLoop: a block outgrew its share.
+// d_dst != NULL (watch sets, engine_watchset.cpp): the rows stay on the device, row i at d_dst + i * dstride (dstride >= cw words, the words behind cw
+// zeroed); `bitmaps` is not touched.
 static int lookup_pass_local(acl_engine *h, PassCtx *c, const DevReverse &r, uint32_t key, uint32_t target, size_t m, uint32_t *bitmaps, size_t words, size_t cw,
-                             uint64_t *counts) {
+                             uint64_t *counts, uint32_t *d_dst = nullptr, size_t dstride = 0) {
     // private frontier regions: 8-byte entries carved from the context's two frontier buffers (16 B per entry there)
     uint64_t cap64 = std::min<uint64_t>(c->frontier_entries * 2 / std::max<size_t>(m, 1), 1u << 22);
     if (h->local_cap_limit) cap64 = std::min<uint64_t>(cap64, h->local_cap_limit);
     if (cap64 < 64 || words > 0xFFFFFFFFull || m > 0x7FFFFFFFull || r.nslots > kRevLdsSlots || r.nrops > kRevLdsOps) return kTakeLevelLoop;
-    const bool direct = words && h->is_pinned(bitmaps, m * words * sizeof(uint32_t));
-    const size_t ostride = direct ? words : cw;
+    const bool direct = !d_dst && words && h->is_pinned(bitmaps, m * words * sizeof(uint32_t));
+    const size_t ostride = d_dst ? dstride : direct ? words : cw;
     // staging: [flag (64 B)] [counts m x 8] [rows m x cw x 4]
     const size_t rows_off = 64 + m * sizeof(uint64_t);
-    HIP_TRY(c->h_out.ensure(rows_off + (direct ? 0 : m * std::max<size_t>(cw, 1) * 4)));
+    HIP_TRY(c->h_out.ensure(rows_off + ((direct || d_dst) ? 0 : m * std::max<size_t>(cw, 1) * 4)));
     uint32_t *flag = (uint32_t *)c->h_out.p;
     uint64_t *h_counts = (uint64_t *)((char *)c->h_out.p + 64);
     uint32_t *h_rows = (uint32_t *)((char *)c->h_out.p + rows_off);
@@ -28,10 +30,11 @@ static int lookup_pass_local(acl_engine *h, PassCtx *c, const DevReverse &r, uin
     HIP_TRY(hipHostGetDevicePointer(&d_out, c->h_out.p, 0));
     // Result rows: written by the kernel straight into host memory (each block as it finishes), or -- rev_rows_device, A/B knob
     // ACL_REV_ROWS=device -- into a device buffer that one DMA copy brings over afterwards.
-    const bool via_device = h->rev_rows_device && ostride;
-    const bool spin = m <= h->spin_max && !c->timing && !via_device;
+    const bool via_device = h->rev_rows_device && ostride && !d_dst;
+    const bool spin = m <= h->spin_max && !c->timing && !via_device && !d_dst;
     const uint32_t done_val = spin ? next_done_val(c) : 0u;
-    if (via_device) {
+    if (d_dst) d_rows = d_dst;
+    else if (via_device) {
         HIP_TRY(c->d_rows.ensure(m * ostride));
         d_rows = c->d_rows.p;
     } else if (direct) HIP_TRY(hipHostGetDevicePointer(&d_rows, bitmaps, 0));
@@ -105,7 +108,7 @@ static int lookup_pass_local(acl_engine *h, PassCtx *c, const DevReverse &r, uin
     for (size_t i = 0; i < m; i++) {  // count | levels walked << 56
         levels = std::max<uint32_t>(levels, (uint32_t)(h_counts[i] >> 56));
         if (counts) counts[i] = h_counts[i] & 0x00FFFFFFFFFFFFFFull;
-        if (!direct) {
+        if (!direct && !d_dst) {
             uint32_t *dst = bitmaps + i * words;
             if (cw) std::memcpy(dst, h_rows + i * cw, cw * 4);
             std::fill(dst + cw, dst + words, 0u);
@@ -173,9 +176,11 @@ static int lookup_refine(acl_engine *h, PassCtx *c, int rtype, int perm, int sty
     return flush(n);
 }
 
-// one batched reverse walk: n subjects of one class against one (type, permission); bitmaps in host memory
+// one batched reverse walk: n subjects of one class against one (type, permission); bitmaps in host memory -- or, with d_dst, left on the device
+// (row i at d_dst + i * dstride, dstride >= the words the type's ids need, zero behind them; `bitmaps`, `words` and `counts` are not used, and the
+// permission must be monotone: candidates under `&` / `-` are confirmed on host rows)
 int lookup_batch(acl_engine *h, PassCtx *c, int rtype, int perm, int stype, int srel, const uint32_t *sids, size_t n, uint32_t *bitmaps, size_t words,
-                 uint64_t *counts) {
+                 uint64_t *counts, uint32_t *d_dst, size_t dstride) {
     int rc = not_sharded(h);
     if (rc) return rc;
     const Schema &sc = h->store.schema();
@@ -183,6 +188,11 @@ int lookup_batch(acl_engine *h, PassCtx *c, int rtype, int perm, int stype, int 
     const uint32_t key = sc.subject_key(stype, srel < 0 ? kNoRelation : srel);
     const uint32_t nobj = h->store.objects(rtype).count();
     const size_t need = (nobj + 31) / 32;
+    if (d_dst) {
+        if (dstride < need || (!h->snap.slot_nonmono.empty() && h->snap.slot_nonmono[target])) return fail(ACL_ERR_INTERNAL, "lookup: device rows too narrow, or asked for a permission with `&` / `-`");
+        words = dstride;
+        counts = nullptr;
+    }
     if (words < need) return fail_detail(ACL_ERR_INVALID_ARGUMENT, kDetailBitmapTooSmall, "lookup: bitmap too small (" + std::to_string(need) + " words needed)");
     // the walk can only mark the ids the snapshot's bitmap slot covers (the build-time count plus headroom); ids interned
     // since then have no relationship in this snapshot, so their bits are zero -- never copy past the slot (advice r1)
@@ -211,14 +221,16 @@ int lookup_batch(acl_engine *h, PassCtx *c, int rtype, int perm, int stype, int 
                 HIP_TRY(hipMemsetAsync(c->d_visited.p, 0, m * vwords * 4, c->stream));
                 c->visited_zero_words = m * vwords;
             }
-            rc = lookup_pass_local(h, c, r, key, target, m, bitmaps + b * words, words, cw, counts ? counts + b : nullptr);
+            rc = lookup_pass_local(h, c, r, key, target, m, d_dst ? nullptr : bitmaps + b * words, words, cw, counts ? counts + b : nullptr, d_dst ? d_dst + b * dstride : nullptr,
+                                   dstride);
             if (rc == ACL_OK) continue;
             c->visited_zero_words = 0;  // a block gave up half-way (or the call failed): its marks are still there
             if (rc != kTakeLevelLoop) return rc;
         }
         c->visited_zero_words = 0;  // (the level loop below marks and does not clear)
         HIP_TRY(hipMemcpyAsync(c->d_sids.p, c->h_in.p, m * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c->h_out.ensure(m * std::max<size_t>(cw, 1) * 4));
+        if (d_dst) HIP_TRY(hipMemsetAsync(d_dst + b * dstride, 0, m * dstride * 4, c->stream));  // (the copy below brings cw words per row)
+        else HIP_TRY(c->h_out.ensure(m * std::max<size_t>(cw, 1) * 4));
         for (int attempt = 0;; attempt++) {
             if (m > c->frontier_entries) {
                 rc = alloc_frontier(h, c, m * 4);
@@ -235,8 +247,10 @@ int lookup_batch(acl_engine *h, PassCtx *c, int rtype, int perm, int stype, int 
             rc = level_loop(h, c, kMaxLevels + 1, [&](uint32_t it) { launch_rev_expand(c->stream, rl, f, it); }, &levels, [&] {
                 // speculative epilogue: the result rows of the target slot, one strided copy for all requests
                 if (cw) {
-                    hipError_t e = hipMemcpy2DAsync(c->h_out.p, cw * 4, c->d_visited.p + h->snap.slot_bit_base[target] / 32, vwords * 4, cw * 4, m,
-                                                    hipMemcpyDeviceToHost, c->stream);
+                    hipError_t e = d_dst ? hipMemcpy2DAsync(d_dst + b * dstride, dstride * 4, c->d_visited.p + h->snap.slot_bit_base[target] / 32, vwords * 4, cw * 4, m,
+                                                            hipMemcpyDeviceToDevice, c->stream)
+                                         : hipMemcpy2DAsync(c->h_out.p, cw * 4, c->d_visited.p + h->snap.slot_bit_base[target] / 32, vwords * 4, cw * 4, m,
+                                                            hipMemcpyDeviceToHost, c->stream);
                     if (e != hipSuccess) cpe = e;
                 }
             });
@@ -252,14 +266,14 @@ int lookup_batch(acl_engine *h, PassCtx *c, int rtype, int perm, int stype, int 
             break;
         }
         c->stats.lookup_requests += m;
-        for (size_t i = 0; i < m; i++) {
+        for (size_t i = 0; i < m && !d_dst; i++) {
             uint32_t *dst = bitmaps + (b + i) * words;
             if (cw) std::memcpy(dst, (const uint32_t *)c->h_out.p + i * cw, cw * 4);
             std::fill(dst + cw, dst + words, 0u);
             if (counts) counts[b + i] = popcount_words(dst, cw);
         }
     }
-    if (!h->snap.slot_nonmono.empty() && h->snap.slot_nonmono[target]) return lookup_refine(h, c, rtype, perm, stype, srel, sids, n, bitmaps, words, cw, counts);
+    if (!d_dst && !h->snap.slot_nonmono.empty() && h->snap.slot_nonmono[target]) return lookup_refine(h, c, rtype, perm, stype, srel, sids, n, bitmaps, words, cw, counts);
     return ACL_OK;
 }
 

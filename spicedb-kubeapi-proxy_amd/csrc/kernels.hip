@@ -3383,4 +3383,129 @@ void launch_subj_fold(hipStream_t st, const uint32_t *gathered, uint32_t world, 
     hipLaunchKernelGGL(k_subj_fold, dim3((uint32_t)std::min<size_t>((total + 255) / 256, 4096)), dim3(256), 0, st, gathered, world, m, row_words, out, out_stride);
 }
 
+// ---- watch sets: the records of new XOR old (kernels.hpp DevRowsDiff) ----
+// Two passes over the rows so that the answer's order does not depend on which wave finishes first: the popcount of every tile, an exclusive scan of the
+// tile counts, then every tile's wave writes its records where the scan says.  A wave walks its tile in steps of 256 words: lane l holds words
+// 4 l .. 4 l + 3 of the step, so consecutive lanes hold consecutive bits and a wave prefix sum of the lanes' popcounts (DPP, wave_incl_scan) orders the records.
+constexpr uint32_t kDiffStepWords = 256;  // 64 lanes x 4 words
+static_assert(kDiffTileWords % kDiffStepWords == 0, "a tile is whole steps");
+
+// words w0 .. w0 + 3 of a row of `width` words (w0 a multiple of 4); words from `width` on read as zero
+template <bool VEC>
+__device__ __forceinline__ uint4 diff_load4(const uint32_t *__restrict__ row, uint32_t width, uint32_t w0) {
+    if (VEC) return w0 < width ? *reinterpret_cast<const uint4 *>(row + w0) : make_uint4(0u, 0u, 0u, 0u);  // (width is a multiple of 4: inside or outside as a whole)
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (w0 < width) v.x = row[w0];
+    if (w0 + 1u < width) v.y = row[w0 + 1u];
+    if (w0 + 2u < width) v.z = row[w0 + 2u];
+    if (w0 + 3u < width) v.w = row[w0 + 3u];
+    return v;
+}
+struct DiffTile {
+    const uint32_t *orow, *nrow;
+    uint32_t owidth, row, w_begin, w_end;
+};
+__device__ __forceinline__ DiffTile diff_tile(const DevRowsDiff &d, uint32_t ntiles, uint64_t t) {
+    DiffTile x;
+    x.row = (uint32_t)(t / ntiles);
+    const uint32_t tile = (uint32_t)(t - (uint64_t)x.row * ntiles);
+    x.owidth = x.row < d.old_nrows ? d.old_words : 0u;  // (a row the old array does not have: empty)
+    x.orow = d.old_rows + (size_t)x.row * d.old_words;
+    x.nrow = d.new_rows + (size_t)x.row * d.new_words;
+    x.w_begin = tile * kDiffTileWords;
+    x.w_end = min(x.w_begin + kDiffTileWords, max(d.old_words, d.new_words));
+    return x;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_rows_diff_count(DevRowsDiff d, uint32_t ntiles, uint32_t *__restrict__ tile_counts) {
+    const uint32_t lane = lane_id();
+    const uint64_t total = (uint64_t)ntiles * d.n_rows;
+    for (uint64_t t = (uint64_t)blockIdx.x * 4u + uniform(threadIdx.x >> 6); t < total; t += (uint64_t)gridDim.x * 4u) {
+        const DiffTile x = diff_tile(d, ntiles, t);
+        uint32_t cnt = 0;
+        if (!d.row_ids || d.row_ids[x.row] != kDiffSkipRow)
+            for (uint32_t w0 = x.w_begin + lane * 4u; w0 < x.w_end; w0 += kDiffStepWords) {
+                const uint4 a = diff_load4<VEC>(x.orow, x.owidth, w0), b = diff_load4<VEC>(x.nrow, d.new_words, w0);
+                cnt += __popc(a.x ^ b.x) + __popc(a.y ^ b.y) + __popc(a.z ^ b.z) + __popc(a.w ^ b.w);
+            }
+        const uint32_t sum = wave_last(wave_incl_scan(cnt, 0u));
+        if (lane == 0) tile_counts[t] = sum;
+    }
+}
+
+// one block: offs[i] = counts[0] + ... + counts[i - 1], offs[n] = the total.  1024 counts per trip: a DPP scan per wave, the sixteen wave totals through LDS.
+// (A tile holds at most 2^17 records, a trip at most 2^27: 32-bit sums inside a trip, the carry between trips is 64-bit.)
+__global__ __launch_bounds__(1024) void k_rows_diff_scan(const uint32_t *__restrict__ counts, uint64_t n, unsigned long long *__restrict__ offs) {
+    __shared__ uint32_t s_wave[16];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+    unsigned long long carry = 0;
+    for (uint64_t base = 0; base < n; base += 1024u) {
+        const uint64_t i = base + tid;
+        const uint32_t v = i < n ? counts[i] : 0u;
+        const uint32_t incl = wave_incl_scan(v, 0u);
+        if (lane == 63u) s_wave[wv] = incl;
+        __syncthreads();
+        uint32_t below = 0, all = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < 16u; k++) {
+            const uint32_t s = s_wave[k];
+            all += s;
+            if (k < wv) below += s;
+        }
+        if (i < n) offs[i] = carry + below + (incl - v);
+        carry += all;
+        __syncthreads();
+    }
+    if (tid == 0) offs[n] = carry;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_rows_diff_emit(DevRowsDiff d, uint32_t ntiles, const unsigned long long *__restrict__ offs, uint4 *__restrict__ out,
+                                                        unsigned long long out_cap) {
+    const uint32_t lane = lane_id();
+    const uint64_t total = (uint64_t)ntiles * d.n_rows;
+    for (uint64_t t = (uint64_t)blockIdx.x * 4u + uniform(threadIdx.x >> 6); t < total; t += (uint64_t)gridDim.x * 4u) {
+        unsigned long long base = offs[t];
+        if (offs[t + 1] == base) continue;  // (nothing changed in this tile: the usual case, and what a skipped row looks like)
+        const DiffTile x = diff_tile(d, ntiles, t);
+        const uint32_t who = d.row_ids ? d.row_ids[x.row] : x.row;
+        for (uint32_t ws = x.w_begin; ws < x.w_end; ws += kDiffStepWords) {  // (wave-uniform trip count: the prefix sum needs every lane)
+            const uint32_t w0 = ws + lane * 4u;
+            const uint4 a = diff_load4<VEC>(x.orow, x.owidth, w0), b = diff_load4<VEC>(x.nrow, d.new_words, w0);
+            const uint32_t nw[4] = {b.x, b.y, b.z, b.w};
+            uint32_t xw[4] = {a.x ^ b.x, a.y ^ b.y, a.z ^ b.z, a.w ^ b.w};
+            const uint32_t cnt = __popc(xw[0]) + __popc(xw[1]) + __popc(xw[2]) + __popc(xw[3]);
+            const uint32_t incl = wave_incl_scan(cnt, 0u);
+            unsigned long long pos = base + (incl - cnt);
+            base += wave_last(incl);
+#pragma unroll
+            for (uint32_t k = 0; k < 4u; k++)
+                for (uint32_t m = xw[k]; m; m &= m - 1u) {
+                    const uint32_t bit = (uint32_t)__ffs((int)m) - 1u;
+                    if (pos < out_cap) out[pos] = make_uint4(who, (w0 + k) * 32u + bit, (nw[k] >> bit) & 1u, 0u);
+                    pos++;
+                }
+        }
+    }
+}
+
+static uint32_t rows_diff_blocks(uint64_t tiles) { return (uint32_t)std::min<uint64_t>((tiles + 3) / 4, 4096); }
+static bool rows_diff_vec(const DevRowsDiff &d) { return d.old_words % 4u == 0 && d.new_words % 4u == 0; }
+void launch_rows_diff_count(hipStream_t st, const DevRowsDiff &d, uint32_t *tile_counts, uint64_t *offs) {
+    const uint32_t ntiles = rows_diff_tiles(d);
+    const uint64_t tiles = (uint64_t)ntiles * d.n_rows;
+    if (tiles)
+        with_flag(rows_diff_vec(d), [&](auto vec) { hipLaunchKernelGGL((k_rows_diff_count<vec()>), dim3(rows_diff_blocks(tiles)), dim3(256), 0, st, d, ntiles, tile_counts); });
+    hipLaunchKernelGGL(k_rows_diff_scan, dim3(1), dim3(1024), 0, st, tile_counts, tiles, (unsigned long long *)offs);
+}
+void launch_rows_diff_emit(hipStream_t st, const DevRowsDiff &d, const uint64_t *offs, uint4 *out, uint64_t out_cap) {
+    const uint32_t ntiles = rows_diff_tiles(d);
+    const uint64_t tiles = (uint64_t)ntiles * d.n_rows;
+    if (!tiles || !out_cap) return;
+    with_flag(rows_diff_vec(d), [&](auto vec) {
+        hipLaunchKernelGGL((k_rows_diff_emit<vec()>), dim3(rows_diff_blocks(tiles)), dim3(256), 0, st, d, ntiles, (const unsigned long long *)offs, out, (unsigned long long)out_cap);
+    });
+}
+
 }  // namespace acl

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 
 #include "plan.hpp"
@@ -209,6 +210,26 @@ void launch_subj_import_gathered(hipStream_t s, const DevSubjLevel &g, const Dev
                                  uint32_t rank, uint32_t cap, bool have_data, uint32_t *ctrl);
 // out[m][out_stride] = OR over the `world` gathered partial rows [world][m][row_words] (words behind row_words: zero)
 void launch_subj_fold(hipStream_t s, const uint32_t *gathered, uint32_t world, uint32_t m, uint32_t row_words, uint32_t *out, uint32_t out_stride);
+// Watch sets (engine_watchset.cpp): the records of new XOR old over n_rows rows, ordered by (row, bit) -- three launches on `s`.  Rows are packed
+// ([row][words], 16-byte aligned bases); the old rows may be narrower or wider than the new ones and there may be fewer of them (old_nrows): whatever
+// is not there reads as zero, and neither array is read past its end.  A tile is kDiffTileWords words of one row, walked by one wave in steps of
+// 64 lanes x 4 words (one 16-byte load per lane and array where both widths are multiples of 4, word loads otherwise).
+//   count: tile_counts[row * ntiles + tile] = popcount(old ^ new) over the tile
+//   scan : offs[i] = sum of tile_counts[0 .. i) as 64-bit, offs[n_rows * ntiles] = the total
+//   emit : record k of a tile at out[offs[tile] + k] = {row_ids ? row_ids[row] : row, bit, bit of NEW (1 gained, 0 lost), 0}, one 16-byte store each;
+//          nothing is written at or beyond out_cap
+// row_ids[row] == kDiffSkipRow: the row contributes nothing (a watcher whose baseline is "now").
+constexpr uint32_t kDiffTileWords = 4096;
+constexpr uint32_t kDiffSkipRow = 0xFFFFFFFFu;
+struct DevRowsDiff {
+    const uint32_t *old_rows, *new_rows;
+    uint32_t old_words, new_words;  // words per row
+    uint32_t old_nrows, n_rows;
+    const uint32_t *row_ids;        // [n_rows] or NULL
+};
+inline uint32_t rows_diff_tiles(const DevRowsDiff &d) { return (std::max(d.old_words, d.new_words) + kDiffTileWords - 1) / kDiffTileWords; }  // per row
+void launch_rows_diff_count(hipStream_t s, const DevRowsDiff &d, uint32_t *tile_counts, uint64_t *offs);  // count + scan
+void launch_rows_diff_emit(hipStream_t s, const DevRowsDiff &d, const uint64_t *offs, uint4 *out, uint64_t out_cap);
 // blocks per expand launch for this device (all co-resident); nwaves = blocks * kWavesPerBlock
 int expand_grid_blocks(int device);
 

@@ -302,6 +302,41 @@ int acl_lookup_subjects(acl_engine_t *h, const char *resource_type, const char *
                         const char *subject_relation, const acl_call_opts_t *opts, uint32_t **bitmap_out, size_t *words_out, uint64_t *count_out,
                         int *wildcard_out, uint32_t **excluded_out);
 
+/* ---- Explain: Check + a witness, the chain of stored relationships that grants the item ----
+ * perm_out / err_out per item are exactly what acl_check_bulk_ids answers for the same items on the same snapshot (the Check and the walk run inside one
+ * evaluation).  An item that answers HAS_PERMISSION on a permission built from `+`, `->` and references alone also gets a witness: hops
+ * [hop_off_out[i], hop_off_out[i + 1]) of *hops_out, at most 50 relationships that chain from the item's resource to its subject --
+ *   - the first hop's resource is the item's resource object; every hop's subject object is the next hop's resource object (an arrow's tupleset hop and a
+ *     userset hop `...@group:g#member` alike); the last hop names the item's subject, or with ACL_HOP_WILDCARD the subject type's `*` (sid is its id);
+ *   - an item whose subject carries a relation may end at that object's own state: `group:g#member @ group:g#member` is granted by zero hops;
+ *   - every hop is a relationship live at the call's revision and `now`, and the hops alone, loaded into an empty store under the same schema, grant the
+ *     item.  The witness is a short one, not the shortest: the walk stops at the first dispatch level that finds the subject, which is never deeper than a
+ *     shortest chain by more than the schema's deepest inlined computed userset.  Which chain wins among equals is unspecified.
+ * flags_out per item: ACL_EXPLAIN_WITNESS -- the hops prove it (possibly zero of them); ACL_EXPLAIN_UNSUPPORTED -- the item is granted by a permission
+ * that holds `-`, `&` or `.all()` anywhere beneath: answered, not explained (that needs a tree of proofs and absences, not a chain), no hops; 0 -- not
+ * granted (NO_PERMISSION or a per-item error such as ACL_ERR_DEPTH): no hops.  Items may mix resource types, permissions and subject classes.
+ * A granted item for which no chain is found fails the call with ACL_ERR_INTERNAL (the message names the item); a walk that outgrows 2^24 states:
+ * ACL_ERR_RESOURCE_EXHAUSTED.  Sharded engines answer ACL_ERR_FAILED_PRECONDITION, store-only engines ACL_ERR_UNAVAILABLE.  err_out and flags_out may be
+ * NULL.  *hops_out is the engine's (one allocation, release with acl_free; NULL when the call fails or n == 0); hop_off_out holds n + 1 offsets. */
+typedef struct {
+    uint16_t rtype, relation; /* the stored relationship's resource type and relation (member index, acl_relation_id) */
+    uint32_t rid;
+    uint16_t stype, srel; /* ACL_NO_RELATION = none */
+    uint32_t sid;
+    uint32_t flags; /* ACL_HOP_* */
+} acl_explain_hop_t;
+#define ACL_HOP_WILDCARD 1u        /* sid is the id of `stype:*` */
+#define ACL_EXPLAIN_WITNESS 1u     /* per item: hops [hop_off[i], hop_off[i+1]) prove it (possibly zero of them) */
+#define ACL_EXPLAIN_UNSUPPORTED 2u /* per item: the permission holds -, & or .all(): answered, not explained */
+int acl_explain_bulk_ids(acl_engine_t *h, const acl_item_t *items, size_t n, uint8_t *perm_out, int32_t *err_out, uint8_t *flags_out, uint32_t *hop_off_out,
+                         acl_explain_hop_t **hops_out, const acl_call_opts_t *opts);
+/* string form, one item: *text_out = the witness, one relationship per line in the tuple grammar `type:id#relation@type:id[#relation]` (the engine's:
+ * acl_free; an empty string when there are no hops).  Names are handled as acl_check_bulk handles them: a field the API's validation refuses fails the
+ * call with ACL_ERR_INVALID_ARGUMENT, an unknown type / permission / relation is the item's own error in *err_out, an unknown object id has no
+ * relationships.  flags_out may be NULL. */
+int acl_explain(acl_engine_t *h, const acl_check_item_t *item, uint8_t *perm_out, int32_t *err_out, uint32_t *flags_out, char **text_out,
+                const acl_call_opts_t *opts);
+
 /* ---- the callers either side of the kernels ----
  * PostFilter: filterItemsWithBulkPermissions (postfilter.go:58-182).  The K list items' resolved pairs are ONE bulk
  * check; pairs [item_off[i], item_off[i+1]) belong to list item i (itemToRequestMap, postfilter.go:65,117-119);
@@ -585,6 +620,16 @@ int acl_selfcheck_compaction(acl_engine_t *h, int phase, int *adopted_out);
  * (cap elements at most), *n_out elements, *close_out the offset of `]`.  ACL_ERR_INVALID_ARGUMENT when the array or one of its elements is not JSON. */
 int acl_selfcheck_json_array(acl_engine_t *h, const char *body, size_t body_len, size_t arr_open, size_t chunk_bytes, size_t *spans_out, size_t cap, size_t *n_out,
                              size_t *close_out);
+/* Explain's per-op side table for the current programs, one record per program op (cap at most, *n_out in all).  Store-only engines only:
+ * it first brings the host snapshot up to date through acl_selfcheck_snapshot, whose refusal (ACL_ERR_FAILED_PRECONDITION on an engine with a device) is this call's. */
+typedef struct {
+    uint16_t rtype, relation; /* the class of relationships the op reads; rtype 0xFFFF: none -- a rewrite step or a reflexive op */
+    uint16_t stype, srel;     /* ACL_NO_RELATION = none */
+    uint32_t slot;            /* the slot whose program holds the op (the type's first slot + member index); 0xFFFFFFFF: no program's */
+    uint32_t dlevel;          /* the op's dispatch-depth offset (> 0: an inlined computed userset's) */
+    uint32_t kind;            /* the op's kind bits (csrc/plan.hpp OP_*) */
+} acl_explain_op_t;
+int acl_selfcheck_explain_ops(acl_engine_t *h, acl_explain_op_t *out, size_t cap, size_t *n_out);
 /* ---- measurement ---- */
 typedef struct {
     uint64_t check_items;      /* items answered since open / last reset */

@@ -32,6 +32,7 @@ SYMBOLS = [
     "acl_lookup_subjects_batch", "acl_lookup_subjects", "acl_shard_subjects_bulk", "acl_shard_subjects_bulk_rccl",
     "acl_watch_set_open", "acl_watch_set_add", "acl_watch_set_remove", "acl_watch_set_poll", "acl_watch_set_row", "acl_watch_set_stats", "acl_watch_set_close",
     "acl_selfcheck_rows_diff",
+    "acl_explain_bulk_ids", "acl_explain", "acl_selfcheck_explain_ops",
 ]
 
 
@@ -74,6 +75,18 @@ class Completion(C.Structure):
 class WatchChange(C.Structure):
     """acl_watch_change_t: one resource a watcher of a watch set gained (1) or lost (0)."""
     _fields_ = [("watcher", C.c_uint32), ("resource_id", C.c_uint32), ("gained", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class ExplainHop(C.Structure):
+    """acl_explain_hop_t: one stored relationship of a witness (ids; flags bit 0: sid is the id of `stype:*`)."""
+    _fields_ = [("rtype", C.c_uint16), ("relation", C.c_uint16), ("rid", C.c_uint32), ("stype", C.c_uint16), ("srel", C.c_uint16), ("sid", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
+class ExplainOpRec(C.Structure):
+    """acl_explain_op_t: one record of Explain's per-op side table (acl_selfcheck_explain_ops)."""
+    _fields_ = [("rtype", C.c_uint16), ("relation", C.c_uint16), ("stype", C.c_uint16), ("srel", C.c_uint16), ("slot", C.c_uint32), ("dlevel", C.c_uint32),
+                ("kind", C.c_uint32)]
 
 
 class ListRequest(C.Structure):
@@ -226,6 +239,9 @@ def load():
     L.acl_lookup_subjects.argtypes = [H, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(CallOpts), C.POINTER(C.POINTER(C.c_uint32)),
                                       C.POINTER(C.c_size_t), C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.POINTER(C.c_uint32))]
     L.acl_free.restype = None
+    L.acl_explain_bulk_ids.argtypes = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.POINTER(ExplainHop)), C.POINTER(CallOpts)]
+    L.acl_explain.argtypes = [H, C.POINTER(CheckItem), C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_void_p), C.POINTER(CallOpts)]
+    L.acl_selfcheck_explain_ops.argtypes = [H, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.acl_watch_set_open.argtypes = [H, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     L.acl_watch_set_add.argtypes = [H, C.c_void_p, C.c_char_p, C.c_uint32, C.POINTER(C.c_uint32)]
     L.acl_watch_set_remove.argtypes = [H, C.c_void_p, C.c_uint32]

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import CallOpts, CheckItem, Completion, Config, Filter, READ_CB, Relationship, Stats, Update, WATCH_CB, WATCH_CHECK_CB, WatchChange
+from ._lib import CallOpts, CheckItem, Completion, Config, ExplainHop, ExplainOpRec, Filter, READ_CB, Relationship, Stats, Update, WATCH_CB, WATCH_CHECK_CB, WatchChange
 
 PERM_UNSPECIFIED, PERM_NO, PERM_HAS, PERM_CONDITIONAL = 0, 1, 2, 3
 OP_CREATE, OP_TOUCH, OP_DELETE = 1, 2, 3
@@ -29,6 +29,12 @@ assert ITEM_DTYPE.itemsize == 16
 WATCHER_FROM_NOW = 1  # ACL_WATCHER_FROM_NOW
 WATCH_CHANGE_DTYPE = np.dtype([("watcher", "<u4"), ("resource_id", "<u4"), ("gained", "<u4"), ("reserved", "<u4")])  # acl_watch_change_t
 assert WATCH_CHANGE_DTYPE.itemsize == C.sizeof(WatchChange) == 16
+HOP_DTYPE = np.dtype([("rtype", "<u2"), ("relation", "<u2"), ("rid", "<u4"), ("stype", "<u2"), ("srel", "<u2"), ("sid", "<u4"), ("flags", "<u4")])  # acl_explain_hop_t
+assert HOP_DTYPE.itemsize == C.sizeof(ExplainHop) == 20
+EXPLAIN_OP_DTYPE = np.dtype([("rtype", "<u2"), ("relation", "<u2"), ("stype", "<u2"), ("srel", "<u2"), ("slot", "<u4"), ("dlevel", "<u4"), ("kind", "<u4")])  # acl_explain_op_t
+assert EXPLAIN_OP_DTYPE.itemsize == C.sizeof(ExplainOpRec) == 20
+HOP_WILDCARD = 1                                # ACL_HOP_WILDCARD
+EXPLAIN_WITNESS, EXPLAIN_UNSUPPORTED = 1, 2     # per-item flags of Explain
 
 
 class AclError(Exception):
@@ -721,6 +727,46 @@ class Engine:
         """LookupSubjects(rt:rid#perm, subject type st[#srel]) -> (subject names, wildcard: bool, excluded names); names through acl_bitmap_names."""
         a, _, wild, e = self.lookup_subjects_bitmap(rt, rid, perm, st, srel)
         return set(self.bitmap_names(st, a)), wild, (set(self.bitmap_names(st, e)) if e is not None else set())
+
+    # ---- Explain
+    def explain_ids(self, items: np.ndarray, cancel=None, timeout_s=None):
+        """acl_explain_bulk_ids: Check + a witness per granted item -> (perm u8[n], err i32[n], flags u8[n], hop_off u32[n + 1], hops HOP_DTYPE[]);
+        item i's witness is hops[hop_off[i]:hop_off[i + 1]], a chain of stored relationships from its resource to its subject."""
+        items = np.ascontiguousarray(items, dtype=ITEM_DTYPE)
+        n = items.size
+        perm = np.zeros(max(1, n), dtype=np.uint8)
+        err = np.zeros(max(1, n), dtype=np.int32)
+        flags = np.zeros(max(1, n), dtype=np.uint8)
+        off = np.zeros(n + 1, dtype=np.uint32)
+        hp = C.POINTER(ExplainHop)()
+        o = self._opts(cancel, timeout_s)
+        self._check(self._L.acl_explain_bulk_ids(self._h, items.ctypes.data, n, perm.ctypes.data, err.ctypes.data, flags.ctypes.data, off.ctypes.data, C.byref(hp),
+                                                 C.byref(o) if o else None))
+        try:
+            total = int(off[n])
+            hops = np.frombuffer(C.string_at(hp, total * HOP_DTYPE.itemsize), dtype=HOP_DTYPE).copy() if total else np.zeros(0, dtype=HOP_DTYPE)
+        finally:
+            self._L.acl_free(hp)
+        return perm[:n], err[:n], flags[:n], off, hops
+
+    def explain(self, rt, rid, perm, st, sid, srel=""):
+        """acl_explain: (permissionship, error code, flags, [relationship strings in the tuple grammar of aclgpu/text.py])."""
+        it = CheckItem(*[_b(x if x is not None else "") for x in (rt, rid, perm, st, sid, srel)])
+        p, e, f, txt = C.c_uint8(), C.c_int32(), C.c_uint32(), C.c_void_p()
+        self._check(self._L.acl_explain(self._h, C.byref(it), C.byref(p), C.byref(e), C.byref(f), C.byref(txt), None))
+        try:
+            lines = C.string_at(txt).decode().splitlines() if txt.value else []
+        finally:
+            self._L.acl_free(txt)
+        return p.value, e.value, f.value, lines
+
+    def selfcheck_explain_ops(self) -> np.ndarray:
+        """Test hook (store-only engines): Explain's per-op side table, one EXPLAIN_OP_DTYPE record (acl_explain_op_t) per program op."""
+        n = C.c_size_t()
+        self._check(self._L.acl_selfcheck_explain_ops(self._h, None, 0, C.byref(n)))
+        out = np.zeros(max(1, n.value), dtype=EXPLAIN_OP_DTYPE)
+        self._check(self._L.acl_selfcheck_explain_ops(self._h, out.ctypes.data, n.value, C.byref(n)))
+        return out[:n.value]
 
     def selfcheck_snapshot(self) -> bool:
         """Test hook (store-only engines): update + verify the host snapshot; True when the update was an in-place patch."""

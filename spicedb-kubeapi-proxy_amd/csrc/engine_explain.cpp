@@ -1,0 +1,267 @@
+// engine_explain.cpp -- Explain (include/aclgpu.h acl_explain*): Check + a witness chain of stored relationships for every item a monotone permission grants.
+//
+// One Eval holds the call: the batch is answered by the ordinary Check (check_ids_host), then the items that came back HAS on a monotone slot are walked once
+// more by k_explain_local (kernels.hip), one block each, which remembers how it reached every state and stops at the level that finds the item's subject.  The
+// kernel hands back (op index, parent id, child id) records in path order; the per-op side table (plan.hpp ExplainOp) names the relation and the subject class
+// each op reads, which turns a record into a relationship.  Steps through a computed userset that was not inlined (OP_PUSH_SAME) stay on their object and
+// produce no hop.  A granted item without a chain would be a disagreement between the two kernels: the call fails rather than return an empty witness.
+#include "engine_internal.hpp"
+#include "validate.hpp"
+
+namespace aclint {
+
+namespace {
+
+constexpr uint32_t kExplainCapFirst = 1u << 14;  // log entries (16 B) per block of the first attempt
+constexpr uint32_t kExplainCapMax = 1u << 24;    // ... and at most: beyond, ACL_ERR_RESOURCE_EXHAUSTED
+
+std::string item_text(const acl_item_t &it, size_t i) {
+    return "item " + std::to_string(i) + " (type " + std::to_string(it.resource_type) + " id " + std::to_string(it.resource_id) + " permission " +
+           std::to_string(it.permission) + " @ type " + std::to_string(it.subject_type) + " id " + std::to_string(it.subject_id) + ")";
+}
+
+// walks the items listed in `pick` (indices into items; all HAS on a monotone slot) and appends their hops; count[k] = hops of pick[k]
+int explain_walk(acl_engine *h, PassCtx *c, const acl_item_t *items, const std::vector<uint32_t> &pick, std::vector<acl_explain_hop_t> *hops, std::vector<uint32_t> *count) {
+    const Schema &sc = h->store.schema();
+    const SubjectRows &sr = h->subj;
+    const DevState &d = *c->dev;
+    DevSubjects g{d.d_meta.p, d.d_edges.p, d.d_ops.p, d.d_progs.p, d.d_sops.p, d.d_smeta.p, d.d_sids.p, d.d_svbase.p, d.d_svn.p,
+                  h->snap.nslots, (uint32_t)h->snap.ops.size(), sr.visited_words, sr.max_ops, sr.max_ops_rel};
+    if (sr.xops.size() != h->snap.ops.size()) return fail(ACL_ERR_INTERNAL, "Explain: the per-op side table does not match the programs");
+    const size_t vwords = sr.visited_words, n = pick.size();
+    count->assign(n, 0);
+    uint32_t cap = kExplainCapFirst;
+    for (size_t b = 0; b < n;) {
+        int rc = check_opts(c->opts);
+        if (rc) return rc;
+        size_t m = std::min<size_t>(n - b, std::max<size_t>(1, c->frontier_entries / cap));  // (the frontier buffer holds the blocks' logs: 16-byte entries)
+        m = std::min<size_t>(m, std::max<size_t>(1, ((size_t)1 << 28) / std::max<size_t>(vwords, 1)));  // <= 1 GiB of visited bits
+        if ((size_t)cap * m > c->frontier_entries) {  // (one block's log beyond the frontier buffer: grow it)
+            rc = alloc_frontier(h, c, (uint64_t)cap * m);
+            if (rc) return rc;
+            if ((size_t)cap * m > c->frontier_entries) return fail(ACL_ERR_RESOURCE_EXHAUSTED, "Explain: walk region beyond the frontier buffer");
+        }
+        const size_t trace_words = m * kExplainTraceRecs * 4;
+        HIP_TRY(c->d_items.ensure(m));
+        HIP_TRY(c->d_subj_visited.ensure(m * vwords));
+        HIP_TRY(c->d_subj_rows.ensure(trace_words));
+        HIP_TRY(c->d_subj_flags.ensure(m));
+        HIP_TRY(c->h_in.ensure(m * sizeof(uint4)));
+        HIP_TRY(c->h_out.ensure(trace_words * 4 + m * 4));
+        uint4 *recs_in = (uint4 *)c->h_in.p;
+        for (size_t i = 0; i < m; i++) {
+            const acl_item_t &it = items[pick[b + i]];
+            const uint32_t key = sc.subject_key(it.subject_type, it.subject_relation == ACL_NO_RELATION ? kNoRelation : (int)it.subject_relation);
+            recs_in[i] = make_uint4(it.resource_id, (uint32_t)sc.slot(it.resource_type, it.permission), key, it.subject_id);
+        }
+        HIP_TRY(hipMemcpyAsync(c->d_items.p, recs_in, m * sizeof(uint4), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemsetAsync(c->d_subj_visited.p, 0, m * vwords * 4, c->stream));
+        HIP_TRY(hipMemsetAsync(c->d_subj_flags.p, 0xFF, m * 4, c->stream));  // (a block that never ran leaves no "found")
+        HIP_TRY(hipMemsetAsync(c->d_status.p, 0, sizeof(uint32_t), c->stream));
+        ev_begin(c, 0);
+        launch_explain_local(c->stream, g, d.d_buckets.p, c->d_items.p, (uint32_t)m, c->d_fbuf[0].p, cap, c->d_subj_visited.p, (uint4 *)c->d_subj_rows.p,
+                             c->d_subj_flags.p, c->d_status.p);
+        ev_end(c);
+        HIP_TRY(hipGetLastError());
+        uint4 *h_tr = (uint4 *)c->h_out.p;
+        uint32_t *h_cnt = (uint32_t *)(h_tr + m * kExplainTraceRecs);
+        HIP_TRY(hipMemcpyAsync(h_tr, c->d_subj_rows.p, trace_words * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(h_cnt, c->d_subj_flags.p, m * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->h_status, c->d_status.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        ev_collect(c);
+        const uint32_t status = c->h_status[0];
+        if (status == 2u) return fail(ACL_ERR_RESOURCE_EXHAUSTED, "Explain: a row longer than the walk enumerates in one task (2^21 ids)");
+        if (status == 1u) {  // a block's log overflowed: redo the chunk with larger regions
+            c->stats.overflow_retries++;
+            if (cap >= kExplainCapMax) return fail(ACL_ERR_RESOURCE_EXHAUSTED, "Explain: the walk of one item outgrew its region (2^24 states)");
+            cap = std::min(cap * 8u, kExplainCapMax);
+            continue;
+        }
+        for (size_t i = 0; i < m; i++) {
+            const size_t idx = pick[b + i];
+            const uint32_t state = h_cnt[i] >> 16, nrec = h_cnt[i] & 0xFFFFu;
+            if (state != kExplainFound || nrec > kExplainTraceRecs)
+                return fail(ACL_ERR_INTERNAL, "Explain: Check grants " + item_text(items[idx], idx) + " but the walk " +
+                                                  (state == kExplainNotFound ? "found no chain of relationships" : "could not trace its chain back") + " (the two kernels disagree)");
+            uint32_t nh = 0;
+            for (uint32_t k = 0; k < nrec; k++) {
+                const uint4 r = h_tr[i * kExplainTraceRecs + k];
+                if (r.x >= sr.xops.size()) return fail(ACL_ERR_INTERNAL, "Explain: a trace record of " + item_text(items[idx], idx) + " names no op");
+                const ExplainOp &x = sr.xops[r.x];
+                if (x.rtype == ExplainOp::kExplainRewrite) {
+                    if (h->snap.ops[r.x].flags & OP_PUSH_SAME) continue;  // a rewrite step: same object, no relationship
+                    return fail(ACL_ERR_INTERNAL, "Explain: a trace record of " + item_text(items[idx], idx) + " names an op that reads no relationships");
+                }
+                hops->push_back(acl_explain_hop_t{x.rtype, x.relation, r.y, x.stype, x.srel, r.z, (r.w & kExplainRecWild) ? ACL_HOP_WILDCARD : 0u});
+                nh++;
+            }
+            (*count)[b + i] = nh;
+        }
+        b += m;
+    }
+    return ACL_OK;
+}
+
+// caller holds an Eval with the subject rows current
+int explain_batch(acl_engine *h, PassCtx *c, const acl_item_t *items, size_t n, uint8_t *perm, int32_t *err, uint8_t *flags, uint32_t *hop_off,
+                  acl_explain_hop_t **hops_out) {
+    const Schema &sc = h->store.schema();
+    const size_t chunk = std::max<size_t>(h->max_sub_batch, 1);
+    for (size_t b = 0; b < n; b += chunk) {
+        int rc = check_ids_host(h, c, items + b, std::min(chunk, n - b), perm + b, err + b);
+        if (rc) return rc;
+    }
+    std::vector<uint32_t> pick;
+    for (size_t i = 0; i < n; i++) {
+        flags[i] = 0;
+        const acl_item_t &it = items[i];
+        if (err[i] || perm[i] != ACL_PERM_HAS_PERMISSION) continue;
+        // (a granted item passed the device's validation; the host reads the same fields, so it checks them again before it indexes with them)
+        if (it.resource_type >= sc.defs.size() || it.subject_type >= sc.defs.size() || it.permission >= sc.defs[it.resource_type].members.size() ||
+            (it.subject_relation != ACL_NO_RELATION && it.subject_relation >= sc.defs[it.subject_type].members.size()))
+            return fail(ACL_ERR_INTERNAL, "Explain: Check grants the ill-formed " + item_text(it, i));
+        const size_t slot = (size_t)sc.slot(it.resource_type, it.permission);
+        if (slot < h->snap.slot_nonmono.size() && h->snap.slot_nonmono[slot]) {
+            flags[i] = ACL_EXPLAIN_UNSUPPORTED;
+            continue;
+        }
+        pick.push_back((uint32_t)i);
+    }
+    std::vector<acl_explain_hop_t> hops;
+    std::vector<uint32_t> count;
+    int rc = explain_walk(h, c, items, pick, &hops, &count);
+    if (rc) return rc;
+    std::fill(hop_off, hop_off + n + 1, 0u);
+    for (size_t k = 0; k < pick.size(); k++) {
+        flags[pick[k]] = ACL_EXPLAIN_WITNESS;
+        hop_off[pick[k] + 1] = count[k];
+    }
+    for (size_t i = 0; i < n; i++) hop_off[i + 1] += hop_off[i];
+    acl_explain_hop_t *out = (acl_explain_hop_t *)std::malloc(std::max<size_t>(hops.size(), 1) * sizeof(acl_explain_hop_t));
+    if (!out) return fail(ACL_ERR_RESOURCE_EXHAUSTED, "out of host memory for the witness");
+    if (!hops.empty()) std::memcpy(out, hops.data(), hops.size() * sizeof(acl_explain_hop_t));
+    *hops_out = out;
+    return ACL_OK;
+}
+
+int explain_call(acl_engine_t *h, const acl_item_t *items, size_t n, uint8_t *perm_out, int32_t *err_out, uint8_t *flags_out, uint32_t *hop_off_out,
+                 acl_explain_hop_t **hops_out, const acl_call_opts_t *o) {
+    if (!hop_off_out || !hops_out || (n && (!items || !perm_out))) return fail(ACL_ERR_INVALID_ARGUMENT, "acl_explain_bulk_ids: NULL buffer");
+    *hops_out = nullptr;
+    hop_off_out[0] = 0;
+    if (n >= 0xFFFFFFFFull) return fail(ACL_ERR_INVALID_ARGUMENT, "acl_explain_bulk_ids: too many items");
+    CallOpts opts;
+    if (o) {
+        opts.cancel = o->cancel;
+        if (o->timeout_ns > 0) opts.deadline_ns = mono_ns() + o->timeout_ns;
+    }
+    if (h->store_only) return fail(ACL_ERR_UNAVAILABLE, "engine was opened store-only (no GPU): Explain is unavailable");
+    {
+        std::shared_lock<RwLock> slk(h->state_mu);
+        if (!h->store.has_schema()) return fail(ACL_ERR_FAILED_PRECONDITION, "no schema loaded");
+        int rc = not_sharded(h);
+        if (rc) return rc;
+    }
+    if (!n) return ACL_OK;
+    std::vector<int32_t> err_local;
+    std::vector<uint8_t> flags_local;
+    if (!err_out) {
+        err_local.assign(n, 0);
+        err_out = err_local.data();
+    }
+    if (!flags_out) {
+        flags_local.assign(n, 0);
+        flags_out = flags_local.data();
+    }
+    Eval ev;
+    int rc = ev.begin(h, false, opts, -1, -1, true);
+    if (rc) return rc;
+    rc = not_sharded(h);
+    if (rc) return rc;
+    return explain_batch(h, ev.c, items, n, perm_out, err_out, flags_out, hop_off_out, hops_out);
+}
+
+}  // namespace
+
+}  // namespace aclint
+
+int acl_explain_bulk_ids(acl_engine_t *h, const acl_item_t *items, size_t n, uint8_t *perm_out, int32_t *err_out, uint8_t *flags_out, uint32_t *hop_off_out,
+                         acl_explain_hop_t **hops_out, const acl_call_opts_t *opts) {
+    return explain_call(h, items, n, perm_out, err_out, flags_out, hop_off_out, hops_out, opts);
+}
+
+int acl_explain(acl_engine_t *h, const acl_check_item_t *item, uint8_t *perm_out, int32_t *err_out, uint32_t *flags_out, char **text_out, const acl_call_opts_t *opts) {
+    if (!item || !perm_out || !err_out || !text_out) return fail(ACL_ERR_INVALID_ARGUMENT, "acl_explain: NULL argument");
+    *perm_out = ACL_PERM_UNSPECIFIED;
+    *err_out = 0;
+    *text_out = nullptr;
+    if (flags_out) *flags_out = 0;
+    acl_item_t it{};
+    int32_t code;
+    {
+        std::shared_lock<RwLock> slk(h->state_mu);
+        std::shared_lock<std::shared_mutex> nlk(h->names_mu);
+        if (!h->store.has_schema()) return fail(ACL_ERR_FAILED_PRECONDITION, "no schema loaded");
+        code = intern_check_item(h, *item, &it);
+    }
+    // as acl_check_bulk: a request the API's validation refuses fails as a whole, an unknown type / permission / relation is the item's own error
+    if (code == ACL_ERR_INVALID_ARGUMENT && !h->per_item_validation) return fail(ACL_ERR_INVALID_ARGUMENT, "invalid CheckPermissionRequest: a field is empty or does not match the API's pattern");
+    if (h->store_only) return fail(ACL_ERR_UNAVAILABLE, "engine was opened store-only (no GPU): Explain is unavailable");
+    std::string text;
+    if (code) {
+        *err_out = code;
+    } else {
+        uint8_t fl = 0;
+        uint32_t off[2] = {0, 0};
+        acl_explain_hop_t *hops = nullptr;
+        const int rc = explain_call(h, &it, 1, perm_out, err_out, &fl, off, &hops, opts);
+        if (rc) return rc;
+        if (flags_out) *flags_out = fl;
+        {
+            // names are read under the names lock, as acl_object_name_copy reads them (the hops' objects take part in relationships: their names stay)
+            std::shared_lock<std::shared_mutex> nlk(h->names_mu);
+            const Schema &sc = h->store.schema();
+            for (uint32_t k = off[0]; k < off[1]; k++) {
+                const acl_explain_hop_t &hp = hops[k];
+                if (hp.rtype >= sc.defs.size() || hp.stype >= sc.defs.size() || hp.relation >= sc.defs[hp.rtype].members.size() ||
+                    (hp.srel != ACL_NO_RELATION && hp.srel >= sc.defs[hp.stype].members.size())) {
+                    std::free(hops);
+                    return fail(ACL_ERR_UNAVAILABLE, "acl_explain: the schema changed while the witness was named");
+                }
+                const std::string *rn = h->store.objects(hp.rtype).name(hp.rid), *sn = h->store.objects(hp.stype).name(hp.sid);
+                if (!rn || (!sn && !(hp.flags & ACL_HOP_WILDCARD))) {  // (the evaluation has ended: a write since may have taken a hop's object away; objects loaded by id never had a name)
+                    std::free(hops);
+                    return fail(ACL_ERR_UNAVAILABLE, "acl_explain: an object of the witness has no name (loaded by id, or renamed by a write since the walk): use acl_explain_bulk_ids, or ask again");
+                }
+                text += sc.defs[hp.rtype].name + ":" + *rn + "#" + sc.defs[hp.rtype].members[hp.relation].name + "@" + sc.defs[hp.stype].name + ":" +
+                        ((hp.flags & ACL_HOP_WILDCARD) ? std::string("*") : *sn);
+                if (hp.srel != ACL_NO_RELATION) text += "#" + sc.defs[hp.stype].members[hp.srel].name;
+                text += "\n";
+            }
+        }
+        std::free(hops);
+    }
+    char *out = (char *)std::malloc(text.size() + 1);
+    if (!out) return fail(ACL_ERR_RESOURCE_EXHAUSTED, "out of host memory for the witness");
+    std::memcpy(out, text.c_str(), text.size() + 1);
+    *text_out = out;
+    return ACL_OK;
+}
+
+// Test hook: the per-op side table of the current programs (plan.hpp ExplainOp), one acl_explain_op_t per FwdOp.  Store-only engines only: it brings the
+// HOST snapshot up to date itself, as acl_selfcheck_snapshot does.
+int acl_selfcheck_explain_ops(acl_engine_t *h, acl_explain_op_t *out, size_t cap, size_t *n_out) {
+    if (!n_out || (cap && !out)) return fail(ACL_ERR_INVALID_ARGUMENT, "acl_selfcheck_explain_ops: bad argument");
+    int rc = acl_selfcheck_snapshot(h, nullptr);
+    if (rc) return rc;
+    std::lock_guard<RwLock> lk(h->state_mu);
+    const Snapshot &s = h->snap;
+    const std::vector<ExplainOp> x = explain_ops(h->store.schema(), s);
+    std::vector<uint32_t> owner(s.ops.size(), 0xFFFFFFFFu);
+    for (size_t slot = 0; slot < s.progs.size(); slot++)
+        for (uint32_t j = 0; j < s.progs[slot].n_total && s.progs[slot].first + j < owner.size(); j++) owner[s.progs[slot].first + j] = (uint32_t)slot;
+    *n_out = x.size();
+    for (size_t j = 0; j < x.size() && j < cap; j++) out[j] = acl_explain_op_t{x[j].rtype, x[j].relation, x[j].stype, x[j].srel, owner[j], s.ops[j].dlevel, s.ops[j].flags};
+    return ACL_OK;
+}

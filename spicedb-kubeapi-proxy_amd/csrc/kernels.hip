@@ -3120,6 +3120,273 @@ void launch_subj_local(hipStream_t s, const DevSubjects &g, const uint32_t *rids
                        flags_out, status);
 }
 
+// ---- Explain: k_explain_local (engine_explain.cpp).  k_subj_local's walk with a memory and an early exit: one block walks ONE item -- from the item's resource
+// down the forward programs -- and where k_subj_local emits the ids of a row, this kernel TESTS the row for the item's one subject, with the device functions
+// k_check_local's interpreter uses (subject_row_contains, row_contains): a hit here is a hit of Check's.  Log entries are 16 bytes and carry how the state was
+// reached: {id, slot | level << 16 | marks, log index of the parent, index of the op that produced it}.  The log discipline and the depth arithmetic are
+// k_subj_local's (levels one at a time, a child one level down marked at append, later levels moved behind the current one), so a state counts at the least level
+// it can be reached at and a witness exists exactly where Check answers HAS.  A hit does an LDS atomicMin of (log index << 32 | op index); the walk ends behind
+// the first level that produced one and one lane follows the parent indices back to entry 0, writing {op, parent id, child id, flags} records in path order.
+namespace {
+struct ExplainTaskLds {
+    uint32_t start[kSubjThreads];
+    uint32_t prefix[kSubjThreads + 1];
+    uint32_t tag[kSubjThreads];     // child level << 16 | child slot
+    uint32_t parent[kSubjThreads];  // log index of the state the row belongs to
+    uint32_t opi[kSubjThreads];     // index of the enumerating op
+};
+}  // namespace
+
+__global__ __launch_bounds__(kSubjThreads) void k_explain_local(DevSubjects g, const uint32_t *__restrict__ buckets, const uint4 *__restrict__ items, uint4 *logs,
+                                                                uint32_t cap, uint32_t *visited_all, uint32_t prog_lds, uint4 *__restrict__ traces,
+                                                                uint32_t *__restrict__ counts, uint32_t *status) {
+    __shared__ ExplainTaskLds t;
+    __shared__ uint32_t s_end, s_stop, s_wave_tot[kSubjThreads / 64];
+    __shared__ unsigned long long s_hit;
+    extern __shared__ uint4 s_dyn[];  // [programs | ops | side table] when prog_lds
+    const uint32_t tid = threadIdx.x, lane = lane_id(), wib = tid >> 6;
+    const uint32_t req = blockIdx.x;
+    const SlotProg *progs = g.progs;
+    const FwdOp *ops = g.ops;
+    const SubjOp *sops = g.sops;
+    if (prog_lds) {
+        SlotProg *lp = reinterpret_cast<SlotProg *>(s_dyn);
+        FwdOp *lo = reinterpret_cast<FwdOp *>(lp + g.nslots);
+        SubjOp *ls = reinterpret_cast<SubjOp *>(lo + g.nops);
+        for (uint32_t i = tid; i < g.nslots; i += kSubjThreads) lp[i] = g.progs[i];
+        for (uint32_t i = tid; i < g.nops; i += kSubjThreads) {
+            lo[i] = g.ops[i];
+            ls[i] = g.sops[i];
+        }
+        progs = lp;
+        ops = lo;
+        sops = ls;
+    }
+    const uint4 item = items[req];  // {resource id, target slot, subject key, subject id}
+    const uint32_t key = item.z, sid = item.w;
+    uint32_t *__restrict__ visited = visited_all + (size_t)req * g.visited_words;
+    uint4 *const log = logs + (size_t)req * cap;
+    if (tid == 0) {
+        s_end = 1;
+        s_stop = 0;
+        s_hit = ~0ull;
+        log[0] = make_uint4(item.x, item.y | (1u << 16) | kSubjMarked, 0u, 0u);  // (the root is walked whatever its id: an object no relationship names can still be its own subject)
+    }
+    __syncthreads();
+    const bool rel_key = key < g.nslots;  // the subject carries a relation: REFLEX ops count
+    const uint32_t W = rel_key ? g.max_ops_rel : g.max_ops;
+    const uint2 *__restrict__ meta2 = reinterpret_cast<const uint2 *>(g.meta);
+    DevGraph dg{};  // (what subject_row_contains reads: the forward row descriptors and the hashed buckets)
+    dg.meta = g.meta;
+    dg.edges = g.edges;
+    dg.buckets = buckets;
+
+    auto append = [&](bool push, uint32_t id, uint32_t y, uint32_t par, uint32_t opi) {
+        const uint64_t b = __ballot(push);
+        if (!b) return;
+        uint32_t base = 0;
+        if (lane == 0) base = atomicAdd(&s_end, (uint32_t)__popcll(b));
+        base = uniform(base);
+        if (base + (uint32_t)__popcll(b) > cap) {
+            if (lane == 0) s_stop = 1u;
+            return;
+        }
+        if (push) log[base + lanes_below(b)] = make_uint4(id, y, par, opi);
+    };
+    auto first_visit = [&](uint32_t slot, uint32_t id) -> bool {
+        const uint32_t vb = g.slot_vbase[slot];
+        if (vb == kSubjNoBits) return true;
+        if (id >= g.slot_vn[slot]) return false;
+        const uint32_t m = 1u << (id & 31u);
+        return !(__hip_atomic_fetch_or(visited + vb + (id >> 5), m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) & m);
+    };
+    auto child = [&](uint32_t id, uint32_t slot, uint32_t lvl, uint32_t cur, bool valid, uint32_t par, uint32_t opi) {
+        bool push = false;
+        uint32_t y = slot | (lvl << 16);
+        if (valid) {
+            if (lvl == cur + 1u) {
+                push = first_visit(slot, id);
+                y |= kSubjMarked;
+            } else {
+                push = true;
+            }
+        }
+        append(push, id, y, par, opi);
+    };
+
+    if (tid == 0) (void)first_visit(item.y, item.x);  // (ordered before every other visit by the first level's barriers)
+    uint32_t lo = 0, level = 1;
+    int stop = 0;
+    bool found = false;
+    for (; level <= kMaxLevels; level++) {
+        const uint32_t hi = s_end;
+        __syncthreads();
+        if (hi == lo || hi > cap) break;
+        // ---- stage A: entries of later levels move behind this one (with their parents); unmarked entries of this level decide their visit now
+        for (uint32_t b0 = lo; b0 < hi; b0 += kSubjThreads) {
+            const uint32_t i = b0 + tid;
+            bool later = false;
+            uint4 en = make_uint4(0u, 0u, 0u, 0u);
+            if (i < hi) {
+                en = log[i];
+                const uint32_t lv = (en.y >> 16) & 63u;
+                if (lv > level) {
+                    later = true;
+                    log[i].y = en.y | kSubjDead;
+                } else if (!(en.y & kSubjMarked) && !first_visit(en.y & 0xFFFFu, en.x)) {
+                    log[i].y = en.y | kSubjDead;
+                }
+            }
+            append(later, en.x, en.y & ~(kSubjMarked | kSubjDead), en.z, en.w);
+        }
+        __syncthreads();
+        // ---- stage B: (state, op) pairs, one per thread and round
+        const uint32_t npairs = (hi - lo) * W;
+        for (uint32_t pb = 0; pb < npairs; pb += kSubjThreads) {
+            const uint32_t q = pb + tid;
+            uint32_t deg = 0, start = 0, tag = 0, id = 0, one_slot = 0, one_lvl = 0, me = 0, opi = 0;
+            bool one_child = false, hit = false;
+            if (q < npairs) {
+                const uint32_t e = q / W, j = q - e * W;
+                me = lo + e;
+                const uint4 en = log[me];
+                if (!(en.y & kSubjDead)) {
+                    const SlotProg p = progs[en.y & 0xFFFFu];
+                    const uint32_t nops = rel_key ? p.n_total : p.n_main;
+                    id = en.x;
+                    opi = p.first + j;
+                    if (j < nops && !(sops[opi].flags & kSubjSkip)) {
+                        const FwdOp op = ops[opi];
+                        const uint32_t L = level + op.dlevel;
+                        if (L <= kMaxLevels) {
+                            if (op.flags & OP_REFLEX) {
+                                hit = op.key == key && id == sid;
+                            } else if (op.flags & OP_PUSH_SAME) {
+                                if (L + 1u <= kMaxLevels) {
+                                    one_child = true;
+                                    one_slot = op.key;
+                                    one_lvl = L + 1u;
+                                }
+                            } else if (op.flags & OP_PROBE_HASH) {
+                                if (op.key == key) hit = subject_row_contains(dg, op, id, sid);
+                            } else if (id < op.nrows) {
+                                const uint2 md = meta2[op.base + id * op.K + op.k];
+                                if (md.y > md.x) {
+                                    if ((op.flags & OP_PROBE) && op.key == key) hit = row_contains(g.edges, md.x, md.y, sid);
+                                    if ((op.flags & OP_ENUM) && L + 1u <= kMaxLevels) {
+                                        if (md.y - md.x > kSubjMaxRow) {
+                                            s_stop = 2u;
+                                        } else {
+                                            start = md.x;
+                                            deg = md.y - md.x;
+                                            tag = ((L + 1u) << 16) | op.key;
+                                        }
+                                    }
+                                }
+                            }
+                        }
+                    }
+                }
+            }
+            if (hit) atomicMin(&s_hit, ((unsigned long long)me << 32) | opi);
+            child(id, one_slot, one_lvl, level, one_child, me, opi);
+            // ---- block-wide exclusive prefix of the degrees
+            const uint32_t incl = wave_incl_scan(deg, lane);
+            if (lane == 63) s_wave_tot[wib] = incl;
+            __syncthreads();
+            uint32_t before = 0, total = 0;
+#pragma unroll
+            for (uint32_t w = 0; w < kSubjThreads / 64; w++) {
+                const uint32_t wt = s_wave_tot[w];
+                before += w < wib ? wt : 0u;
+                total += wt;
+            }
+            if (total) {  // (block-uniform)
+                t.prefix[tid] = before + incl - deg;
+                t.start[tid] = start;
+                t.tag[tid] = tag;
+                t.parent[tid] = me;
+                t.opi[tid] = opi;
+                __syncthreads();
+                for (uint32_t wb = 0; wb < total; wb += kSubjThreads) {
+                    const uint32_t w = wb + tid;
+                    const bool valid = w < total;
+                    const uint32_t wv = valid ? w : total - 1u;
+                    uint32_t jt = 0;
+#pragma unroll
+                    for (uint32_t step = kSubjThreads / 2; step >= 1; step >>= 1)
+                        if (t.prefix[jt + step] <= wv) jt += step;
+                    const uint32_t tg = t.tag[jt];
+                    const uint32_t v = gld(g.edges, t.start[jt] + (wv - t.prefix[jt])) & kIdMask;
+                    child(v, tg & 0xFFFFu, (tg >> 16) & 63u, level, valid, t.parent[jt], t.opi[jt]);
+                }
+            }
+            // (also the barrier behind the task list: every lane is done with it before the next round overwrites it)
+            stop = __syncthreads_or(s_stop != 0u);
+            if (stop) break;
+        }
+        // (behind a barrier either way: block-uniform)  A log that overflowed on children of the level that found the subject does not matter: the hit state
+        // and its ancestors were appended before this level began, and nothing below them is needed.  An enumerated row beyond the limit (2) still fails.
+        // (s_stop is last-writer-wins: an append's 1 may overwrite a 2 of the same round.  That only decides whether a witness already found is returned; it is valid either way.)
+        if (s_hit != ~0ull && s_stop != 2u) {
+            found = true;
+            break;
+        }
+        if (stop) break;
+        lo = hi;
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    // ---- back-trace (one lane): at most kMaxLevels states lie on a path (their levels ascend), every index is checked before it is followed
+    if (s_stop && !found) {
+        *status = s_stop;
+        counts[req] = 1u << 16;
+        return;
+    }
+    if (!found) {
+        counts[req] = 1u << 16;  // not found
+        return;
+    }
+    const uint32_t end = min(s_end, cap);
+    const uint32_t h = (uint32_t)(s_hit >> 32), ho = (uint32_t)s_hit;
+    uint32_t depth = 0, i = h;
+    bool bad = h >= end || ho >= g.nops;
+    for (uint32_t k = 0; !bad && k < kMaxLevels && i != 0u; k++) {
+        const uint32_t par = log[i].z;
+        if (par >= end || par >= i) bad = true;  // (a parent was appended before its child)
+        i = par;
+        depth++;
+    }
+    if (bad || i != 0u) {
+        counts[req] = 2u << 16;  // the log does not lead back to the item's resource
+        return;
+    }
+    uint4 *const rec = traces + (size_t)req * (kMaxLevels + 1u);
+    uint32_t n = depth;
+    const FwdOp fo = ops[ho];
+    if (!(fo.flags & OP_REFLEX)) {
+        const bool wild = (fo.flags & OP_WILD) != 0u;
+        rec[n++] = make_uint4(ho, log[h].x, wild ? fo.K : sid, wild ? 1u : 0u);
+    }
+    i = h;
+    for (uint32_t k = depth; k > 0u; k--) {
+        const uint4 en = log[i];
+        const uint32_t par = en.z < end ? en.z : 0u;
+        rec[k - 1u] = make_uint4(en.w, log[par].x, en.x, 0u);
+        i = par;
+    }
+    counts[req] = n;
+}
+
+void launch_explain_local(hipStream_t s, const DevSubjects &g, const uint32_t *buckets, const uint4 *items, uint32_t n, void *logs, uint32_t cap, uint32_t *visited,
+                          uint4 *traces, uint32_t *counts, uint32_t *status) {
+    if (!n) return;
+    const size_t prog_bytes = (size_t)g.nslots * sizeof(SlotProg) + (size_t)g.nops * (sizeof(FwdOp) + sizeof(SubjOp));
+    const uint32_t prog_lds = prog_bytes <= kSubjLdsProgBytes ? 1u : 0u;
+    hipLaunchKernelGGL(k_explain_local, dim3(n), dim3(kSubjThreads), prog_lds ? prog_bytes : 0u, s, g, buckets, items, (uint4 *)logs, cap, visited, prog_lds, traces,
+                       counts, status);
+}
+
 // ---- LookupSubjects, level-synchronous: k_subj_expand (the sharded graph's native loop, engine_shard_subjects.cpp).  One launch = one dispatch level of ALL
 // lookups of a chunk on all CUs, over the chunked frontier of k_expand / k_rev_expand.  Entry: x = object id, y = lookup index, z = slot | level << 16 |
 // kSubjMarked, w = 0.  The emission rules and the depth arithmetic per op are k_subj_local's; what differs is WHEN a visit is decided.  There, unmarked

@@ -191,6 +191,19 @@ struct DevSubjects {
 constexpr uint32_t kSubjLdsProgBytes = 16u << 10;  // programs + ops + side table staged in LDS up to this size
 void launch_subj_local(hipStream_t s, const DevSubjects &g, const uint32_t *rids, uint32_t n, uint32_t target_slot, uint32_t key, void *logs, uint32_t cap,
                        uint32_t *visited, uint32_t *rows, uint32_t row_words, uint32_t *flags_out, uint32_t *status);
+// single-launch Explain (kernels.hip k_explain_local): block b walks the forward programs from item b's resource, as k_subj_local does, until the level at
+// which the item's ONE subject is found, and writes the path that led there.  items: [n] {resource id, target slot, subject key, subject id}; buckets: the forward
+// snapshot's hashed rows (DevGraph::buckets); logs: [n][cap] 16-byte entries; visited: [n][g.visited_words] zeroed by the caller.
+//   counts[b] = records written | state << 16 (kExplainFound: a path; kExplainNotFound: no level produced a hit, or the walk stopped; kExplainBadTrace: the
+//               log did not lead back to entry 0)
+//   traces[b * kExplainTraceRecs ...] = {op index, parent object id, child object id, flags (kExplainRecWild: the child is the op's `T:*` id)} in path order --
+//               one record per state on the path below the root (the op that produced it) and, unless the hit was a reflexive op's, one for the hit itself
+// *status != 0 afterwards (the caller zeroes it): 1 = a block's log overflowed (redo with a larger cap), 2 = an enumerated row beyond kSubjMaxRow.
+constexpr uint32_t kExplainTraceRecs = kMaxLevels + 1;
+constexpr uint32_t kExplainFound = 0, kExplainNotFound = 1, kExplainBadTrace = 2;
+constexpr uint32_t kExplainRecWild = 1u;
+void launch_explain_local(hipStream_t s, const DevSubjects &g, const uint32_t *buckets, const uint4 *items, uint32_t n, void *logs, uint32_t cap, uint32_t *visited,
+                          uint4 *traces, uint32_t *counts, uint32_t *status);
 // level-synchronous LookupSubjects (kernels.hip k_subj_expand; the sharded graph's native loop): one launch per dispatch level over the chunked frontier, all
 // lookups of a chunk at once.  visited: [m][g.visited_words], rows: this shard's PARTIAL rows [m][row_words], flags: [m] bytes (1: a `T:*` row was reached) --
 // all zeroed by the caller.  A row beyond the per-task enumeration limit raises overflow code 2 in the frontier's status block.

@@ -243,6 +243,16 @@ struct SubjOp {         // 16 B, one per FwdOp (same index as Snapshot::ops): wh
     uint32_t flags;     // kSubjSkip: the op lies inside the subtracted operand of an exclusion (the positive relaxation drops it)
     uint32_t pad;
 };
+// Explain's host-only side table, one entry per FwdOp (same index as Snapshot::ops): the class of relationships the op reads -- what turns a walk's
+// (op index, parent id, child id) into a stored relationship.  An inlined computed userset's op reads a relation other than its state's slot, which is why
+// the op index travels with every state of k_explain_local's log.
+struct ExplainOp {
+    uint16_t rtype = kExplainRewrite, relation = 0;  // the relation whose rows the op reads (type, member index); rtype == kExplainRewrite: no relationship --
+                                                     // OP_PUSH_SAME (a computed userset on the same object), OP_REFLEX, or an op of no live class
+    uint16_t stype = 0, srel = 0xFFFFu;              // the class's subject type and relation (0xFFFF: none)
+    static constexpr uint16_t kExplainRewrite = 0xFFFFu;
+};
+std::vector<ExplainOp> explain_ops(const Schema &sc, const Snapshot &snap);
 constexpr uint32_t kSubjSkip = 1u;
 constexpr uint32_t kSubjNoBits = 0xFFFFFFFFu;  // SubjectRows::slot_vbase: the slot's states are never a walk's children (no visited bits)
 struct SubjectRows {
@@ -250,6 +260,7 @@ struct SubjectRows {
     std::vector<uint32_t> smeta;      // uint2 {start, end} per (hashed class, resource id) into sids
     std::vector<uint32_t> sids;       // subject ids, ascending per row
     std::vector<SubjOp> sops;         // [Snapshot::ops.size()]
+    std::vector<ExplainOp> xops;      // [Snapshot::ops.size()] host only (Explain)
     std::vector<uint32_t> slot_vbase; // [nslots] first visited WORD of the slot's states in a lookup's region (kSubjNoBits: none)
     std::vector<uint32_t> slot_vn;    // [nslots] ids those bits cover
     std::vector<uint32_t> type_cover; // [ntypes] object count of each type the rows were sized for (a larger count: rebuild)

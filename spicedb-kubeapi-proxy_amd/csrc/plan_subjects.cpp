@@ -45,6 +45,42 @@ std::vector<uint8_t> subject_skip_ops(const Snapshot &s) {
     return skip;
 }
 
+std::vector<ExplainOp> explain_ops(const Schema &sc, const Snapshot &s) {
+    // a hashed op names its class by the descriptor base of the class's hashed rows, a sorted op by its relation's descriptor base + its sorted-class index
+    struct Cls {
+        uint32_t base, k;
+        bool hashed;
+        ExplainOp x;
+    };
+    std::vector<Cls> cls;
+    for (int slot = 0; slot < sc.nslots && (size_t)slot < s.lay.size(); slot++) {
+        const RelLayout &l = s.lay[slot];
+        const Member &m = sc.defs[sc.slot_owner[slot].first].members[sc.slot_owner[slot].second];
+        for (size_t k = 0; k < l.cls.size() && k < m.classes.size(); k++) {
+            const ClassLayout &c = l.cls[k];
+            if (!c.live) continue;
+            ExplainOp x;
+            x.rtype = (uint16_t)sc.slot_owner[slot].first;
+            x.relation = (uint16_t)sc.slot_owner[slot].second;
+            x.stype = (uint16_t)m.classes[k].stype;
+            x.srel = m.classes[k].srel == kNoRelation ? (uint16_t)0xFFFFu : (uint16_t)m.classes[k].srel;
+            cls.push_back(Cls{c.hashed ? c.smeta_base : l.meta_base, c.hashed ? 0u : c.ks, c.hashed, x});
+        }
+    }
+    std::vector<ExplainOp> out(s.ops.size());
+    for (size_t j = 0; j < s.ops.size(); j++) {
+        const FwdOp &op = s.ops[j];
+        if (!(op.flags & (OP_PROBE | OP_ENUM | OP_PROBE_HASH)) || (op.flags & (OP_PUSH_SAME | OP_REFLEX))) continue;
+        const bool hashed = (op.flags & OP_PROBE_HASH) != 0;
+        for (const Cls &c : cls)
+            if (c.hashed == hashed && c.base == op.base && (hashed || c.k == op.k)) {
+                out[j] = c.x;
+                break;
+            }
+    }
+    return out;
+}
+
 void build_subjects(Store &store, int64_t now, const Snapshot &s, SubjectRows *out) {
     const Schema &sc = store.schema();
     SubjectRows r;
@@ -107,6 +143,7 @@ void build_subjects(Store &store, int64_t now, const Snapshot &s, SubjectRows *o
         so.base = flat[it->second].first;
         so.nrows = flat[it->second].second;
     }
+    r.xops = explain_ops(sc, s);
     // ---- visited bits: only slots some op produces children in (the resource's own state is the walk's root and is expanded once)
     r.slot_vbase.assign(sc.nslots, kSubjNoBits);
     r.slot_vn.assign(sc.nslots, 0);

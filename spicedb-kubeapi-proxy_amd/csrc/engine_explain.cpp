@@ -25,82 +25,67 @@ int explain_walk(acl_engine *h, PassCtx *c, const acl_item_t *items, const std::
     const Schema &sc = h->store.schema();
     const SubjectRows &sr = h->subj;
     const DevState &d = *c->dev;
-    DevSubjects g{d.d_meta.p, d.d_edges.p, d.d_ops.p, d.d_progs.p, d.d_sops.p, d.d_smeta.p, d.d_sids.p, d.d_svbase.p, d.d_svn.p,
-                  h->snap.nslots, (uint32_t)h->snap.ops.size(), sr.visited_words, sr.max_ops, sr.max_ops_rel};
+    const DevSubjects g = dev_subjects(h, c);
     if (sr.xops.size() != h->snap.ops.size()) return fail(ACL_ERR_INTERNAL, "Explain: the per-op side table does not match the programs");
-    const size_t vwords = sr.visited_words, n = pick.size();
-    count->assign(n, 0);
-    uint32_t cap = kExplainCapFirst;
-    for (size_t b = 0; b < n;) {
-        int rc = check_opts(c->opts);
-        if (rc) return rc;
-        size_t m = std::min<size_t>(n - b, std::max<size_t>(1, c->frontier_entries / cap));  // (the frontier buffer holds the blocks' logs: 16-byte entries)
-        m = std::min<size_t>(m, std::max<size_t>(1, ((size_t)1 << 28) / std::max<size_t>(vwords, 1)));  // <= 1 GiB of visited bits
-        if ((size_t)cap * m > c->frontier_entries) {  // (one block's log beyond the frontier buffer: grow it)
-            rc = alloc_frontier(h, c, (uint64_t)cap * m);
-            if (rc) return rc;
-            if ((size_t)cap * m > c->frontier_entries) return fail(ACL_ERR_RESOURCE_EXHAUSTED, "Explain: walk region beyond the frontier buffer");
-        }
-        const size_t trace_words = m * kExplainTraceRecs * 4;
-        HIP_TRY(c->d_items.ensure(m));
-        HIP_TRY(c->d_subj_visited.ensure(m * vwords));
-        HIP_TRY(c->d_subj_rows.ensure(trace_words));
-        HIP_TRY(c->d_subj_flags.ensure(m));
-        HIP_TRY(c->h_in.ensure(m * sizeof(uint4)));
-        HIP_TRY(c->h_out.ensure(trace_words * 4 + m * 4));
-        uint4 *recs_in = (uint4 *)c->h_in.p;
-        for (size_t i = 0; i < m; i++) {
-            const acl_item_t &it = items[pick[b + i]];
-            const uint32_t key = sc.subject_key(it.subject_type, it.subject_relation == ACL_NO_RELATION ? kNoRelation : (int)it.subject_relation);
-            recs_in[i] = make_uint4(it.resource_id, (uint32_t)sc.slot(it.resource_type, it.permission), key, it.subject_id);
-        }
-        HIP_TRY(hipMemcpyAsync(c->d_items.p, recs_in, m * sizeof(uint4), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemsetAsync(c->d_subj_visited.p, 0, m * vwords * 4, c->stream));
-        HIP_TRY(hipMemsetAsync(c->d_subj_flags.p, 0xFF, m * 4, c->stream));  // (a block that never ran leaves no "found")
-        HIP_TRY(hipMemsetAsync(c->d_status.p, 0, sizeof(uint32_t), c->stream));
-        ev_begin(c, 0);
-        launch_explain_local(c->stream, g, d.d_buckets.p, c->d_items.p, (uint32_t)m, c->d_fbuf[0].p, cap, c->d_subj_visited.p, (uint4 *)c->d_subj_rows.p,
-                             c->d_subj_flags.p, c->d_status.p);
-        ev_end(c);
-        HIP_TRY(hipGetLastError());
-        uint4 *h_tr = (uint4 *)c->h_out.p;
-        uint32_t *h_cnt = (uint32_t *)(h_tr + m * kExplainTraceRecs);
-        HIP_TRY(hipMemcpyAsync(h_tr, c->d_subj_rows.p, trace_words * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(h_cnt, c->d_subj_flags.p, m * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(c->h_status, c->d_status.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        ev_collect(c);
-        const uint32_t status = c->h_status[0];
-        if (status == 2u) return fail(ACL_ERR_RESOURCE_EXHAUSTED, "Explain: a row longer than the walk enumerates in one task (2^21 ids)");
-        if (status == 1u) {  // a block's log overflowed: redo the chunk with larger regions
-            c->stats.overflow_retries++;
-            if (cap >= kExplainCapMax) return fail(ACL_ERR_RESOURCE_EXHAUSTED, "Explain: the walk of one item outgrew its region (2^24 states)");
-            cap = std::min(cap * 8u, kExplainCapMax);
-            continue;
-        }
-        for (size_t i = 0; i < m; i++) {
-            const size_t idx = pick[b + i];
-            const uint32_t state = h_cnt[i] >> 16, nrec = h_cnt[i] & 0xFFFFu;
-            if (state != kExplainFound || nrec > kExplainTraceRecs)
-                return fail(ACL_ERR_INTERNAL, "Explain: Check grants " + item_text(items[idx], idx) + " but the walk " +
-                                                  (state == kExplainNotFound ? "found no chain of relationships" : "could not trace its chain back") + " (the two kernels disagree)");
-            uint32_t nh = 0;
-            for (uint32_t k = 0; k < nrec; k++) {
-                const uint4 r = h_tr[i * kExplainTraceRecs + k];
-                if (r.x >= sr.xops.size()) return fail(ACL_ERR_INTERNAL, "Explain: a trace record of " + item_text(items[idx], idx) + " names no op");
-                const ExplainOp &x = sr.xops[r.x];
-                if (x.rtype == ExplainOp::kExplainRewrite) {
-                    if (h->snap.ops[r.x].flags & OP_PUSH_SAME) continue;  // a rewrite step: same object, no relationship
-                    return fail(ACL_ERR_INTERNAL, "Explain: a trace record of " + item_text(items[idx], idx) + " names an op that reads no relationships");
-                }
-                hops->push_back(acl_explain_hop_t{x.rtype, x.relation, r.y, x.stype, x.srel, r.z, (r.w & kExplainRecWild) ? ACL_HOP_WILDCARD : 0u});
-                nh++;
+    count->assign(pick.size(), 0);
+    const BlockWalk w{"Explain", "item", 1 /* (16-byte log entries) */, 0, kExplainCapFirst, kExplainCapMax};
+    uint4 *h_tr = nullptr;
+    uint32_t *h_cnt = nullptr;
+    return block_walk_chunks(
+        h, c, w, pick.size(),
+        [&](size_t b, size_t m) {
+            const size_t trace_words = m * kExplainTraceRecs * 4;
+            HIP_TRY(c->d_items.ensure(m));
+            HIP_TRY(c->d_subj_rows.ensure(trace_words));
+            HIP_TRY(c->d_subj_flags.ensure(m));
+            HIP_TRY(c->h_in.ensure(m * sizeof(uint4)));
+            HIP_TRY(c->h_out.ensure(trace_words * 4 + m * 4));
+            uint4 *recs_in = (uint4 *)c->h_in.p;
+            for (size_t i = 0; i < m; i++) {
+                const acl_item_t &it = items[pick[b + i]];
+                const uint32_t key = sc.subject_key(it.subject_type, it.subject_relation == ACL_NO_RELATION ? kNoRelation : (int)it.subject_relation);
+                recs_in[i] = make_uint4(it.resource_id, (uint32_t)sc.slot(it.resource_type, it.permission), key, it.subject_id);
             }
-            (*count)[b + i] = nh;
-        }
-        b += m;
-    }
-    return ACL_OK;
+            HIP_TRY(hipMemcpyAsync(c->d_items.p, recs_in, m * sizeof(uint4), hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemsetAsync(c->d_subj_flags.p, 0xFF, m * 4, c->stream));  // (a block that never ran leaves no "found")
+            return (int)ACL_OK;
+        },
+        [&](size_t m, uint32_t cap) {
+            const size_t trace_words = m * kExplainTraceRecs * 4;
+            ev_begin(c, 0);
+            launch_explain_local(c->stream, g, d.d_buckets.p, c->d_items.p, (uint32_t)m, c->d_fbuf[0].p, cap, c->d_subj_visited.p, (uint4 *)c->d_subj_rows.p,
+                                 c->d_subj_flags.p, c->d_status.p);
+            ev_end(c);
+            HIP_TRY(hipGetLastError());
+            h_tr = (uint4 *)c->h_out.p;
+            h_cnt = (uint32_t *)(h_tr + m * kExplainTraceRecs);
+            HIP_TRY(hipMemcpyAsync(h_tr, c->d_subj_rows.p, trace_words * 4, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipMemcpyAsync(h_cnt, c->d_subj_flags.p, m * 4, hipMemcpyDeviceToHost, c->stream));
+            return (int)ACL_OK;
+        },
+        [&](size_t b, size_t m) {
+            for (size_t i = 0; i < m; i++) {
+                const size_t idx = pick[b + i];
+                const uint32_t state = h_cnt[i] >> 16, nrec = h_cnt[i] & 0xFFFFu;
+                if (state != kExplainFound || nrec > kExplainTraceRecs)
+                    return fail(ACL_ERR_INTERNAL, "Explain: Check grants " + item_text(items[idx], idx) + " but the walk " +
+                                                      (state == kExplainNotFound ? "found no chain of relationships" : "could not trace its chain back") + " (the two kernels disagree)");
+                uint32_t nh = 0;
+                for (uint32_t k = 0; k < nrec; k++) {
+                    const uint4 r = h_tr[i * kExplainTraceRecs + k];
+                    if (r.x >= sr.xops.size()) return fail(ACL_ERR_INTERNAL, "Explain: a trace record of " + item_text(items[idx], idx) + " names no op");
+                    const ExplainOp &x = sr.xops[r.x];
+                    if (x.rtype == ExplainOp::kExplainRewrite) {
+                        if (h->snap.ops[r.x].flags & OP_PUSH_SAME) continue;  // a rewrite step: same object, no relationship
+                        return fail(ACL_ERR_INTERNAL, "Explain: a trace record of " + item_text(items[idx], idx) + " names an op that reads no relationships");
+                    }
+                    hops->push_back(acl_explain_hop_t{x.rtype, x.relation, r.y, x.stype, x.srel, r.z, (r.w & kExplainRecWild) ? ACL_HOP_WILDCARD : 0u});
+                    nh++;
+                }
+                (*count)[b + i] = nh;
+            }
+            return (int)ACL_OK;
+        });
 }
 
 // caller holds an Eval with the subject rows current

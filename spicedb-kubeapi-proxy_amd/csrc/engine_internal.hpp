@@ -644,4 +644,64 @@ int level_loop(acl_engine *h, PassCtx *c, uint32_t max_iter, F launch, uint32_t 
     }
 }
 
+// the device's forward snapshot and subject rows as the subject walks read them (LookupSubjects, its sharded loop, Explain)
+inline DevSubjects dev_subjects(const acl_engine *h, const PassCtx *c) {
+    const DevState &d = *c->dev;
+    const SubjectRows &sr = h->subj;
+    return DevSubjects{d.d_meta.p, d.d_edges.p, d.d_ops.p, d.d_progs.p, d.d_sops.p, d.d_smeta.p, d.d_sids.p, d.d_svbase.p, d.d_svn.p,
+                       h->snap.nslots, (uint32_t)h->snap.ops.size(), sr.visited_words, sr.max_ops, sr.max_ops_rel};
+}
+
+// The host side of the one-block subject walks (k_subj_local, k_explain_local): units [0, n), one block each, in chunks.  A block logs into its own region of
+// `cap` entries of the frontier buffer and marks visited bits in its own h->subj.visited_words words; a chunk holds as many blocks as the buffer and a 1 GiB
+// budget allow.  A chunk in which a block's log overflowed (status 1) is walked again with regions 8 times as large, up to cap_max.
+struct BlockWalk {
+    const char *op;           // the messages' prefix
+    const char *unit;         // what one block walks, for the messages
+    uint32_t logs_per_entry;  // log entries per 16-byte frontier entry: 2 (8-byte entries) or 1
+    size_t extra_words;       // words per block that count against the budget besides the visited bits
+    uint32_t cap_first, cap_max;
+};
+// prepare(b, m): buffers, uploads and memsets of chunk [b, b + m) other than the visited bits and the status word; run(m, cap): the launch (between
+// ev_begin / ev_end) and the copies back, all on c->stream; collect(b, m): the chunk's results, after the stream was synchronised with status 0.
+template <typename Prepare, typename Run, typename Collect>
+int block_walk_chunks(acl_engine *h, PassCtx *c, const BlockWalk &w, size_t n, Prepare prepare, Run run, Collect collect) {
+    const std::string op = w.op;
+    const size_t vwords = h->subj.visited_words;
+    uint32_t cap = w.cap_first;
+    for (size_t b = 0; b < n;) {
+        int rc = check_opts(c->opts);
+        if (rc) return rc;
+        size_t m = std::min<size_t>(n - b, std::max<size_t>(1, c->frontier_entries * w.logs_per_entry / cap));
+        m = std::min<size_t>(m, std::max<size_t>(1, ((size_t)1 << 28) / std::max<size_t>(vwords + w.extra_words, 1)));  // <= 1 GiB of visited bits (and rows)
+        if ((size_t)cap * m > c->frontier_entries * w.logs_per_entry) {  // (one block's log beyond the frontier buffer: grow it)
+            rc = alloc_frontier(h, c, ((uint64_t)cap * m + w.logs_per_entry - 1) / w.logs_per_entry);
+            if (rc) return rc;
+            if ((size_t)cap * m > c->frontier_entries * w.logs_per_entry) return fail(ACL_ERR_RESOURCE_EXHAUSTED, op + ": walk region beyond the frontier buffer");
+        }
+        HIP_TRY(c->d_subj_visited.ensure(m * vwords));
+        rc = prepare(b, m);
+        if (rc) return rc;
+        HIP_TRY(hipMemsetAsync(c->d_subj_visited.p, 0, m * vwords * 4, c->stream));
+        HIP_TRY(hipMemsetAsync(c->d_status.p, 0, sizeof(uint32_t), c->stream));
+        rc = run(m, cap);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(c->h_status, c->d_status.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        ev_collect(c);
+        const uint32_t status = c->h_status[0];
+        if (status == 2u) return fail(ACL_ERR_RESOURCE_EXHAUSTED, op + ": a row longer than the walk enumerates in one task (2^21 ids)");
+        if (status == 1u) {  // a block's log overflowed: redo the chunk with larger regions
+            c->stats.overflow_retries++;
+            if (cap >= w.cap_max) return fail(ACL_ERR_RESOURCE_EXHAUSTED, op + ": the walk of one " + w.unit + " outgrew its region (2^24 states)");
+            cap = std::min(cap * 8u, w.cap_max);
+            continue;
+        }
+        rc = collect(b, m);
+        if (rc) return rc;
+        b += m;
+    }
+    return ACL_OK;
+}
+
 }  // namespace aclint

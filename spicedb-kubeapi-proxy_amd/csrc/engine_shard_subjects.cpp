@@ -74,9 +74,7 @@ int acl_shard_subjects_bulk(acl_engine_t *h, const acl_shard_comm_t *comm, int r
         if (rids[i] >= nres) return fail(ACL_ERR_INVALID_ARGUMENT, "lookup_subjects: resource id " + std::to_string(rids[i]) + " beyond the type's objects");
     const uint32_t world = h->shard.world;
     const SubjectRows &sr = h->subj;
-    const DevState &d = *c->dev;
-    const DevSubjects g{d.d_meta.p, d.d_edges.p, d.d_ops.p, d.d_progs.p, d.d_sops.p, d.d_smeta.p, d.d_sids.p, d.d_svbase.p, d.d_svn.p,
-                        h->snap.nslots, (uint32_t)h->snap.ops.size(), sr.visited_words, sr.max_ops, sr.max_ops_rel};
+    const DevSubjects g = dev_subjects(h, c);
     const size_t vwords = sr.visited_words;
     // lookups per chunk, from what every rank shares: the visited words if EVERY slot had bits for its type's objects as they are now (a bound of this
     // shard's own vwords, whenever its rows were built), the row words, the world

@@ -29,62 +29,43 @@ namespace {
 // one launch per group of resources: rows of `row_words` words into bitmaps (stride `words`), wildcard reached into wild[]
 int subjects_walk(acl_engine *h, PassCtx *c, uint32_t target, uint32_t key, const uint32_t *rids, size_t n, uint32_t *bitmaps, size_t words, size_t row_words,
                   uint8_t *wild) {
-    const SubjectRows &sr = h->subj;
-    const DevState &d = *c->dev;
-    DevSubjects g{d.d_meta.p, d.d_edges.p, d.d_ops.p, d.d_progs.p, d.d_sops.p, d.d_smeta.p, d.d_sids.p, d.d_svbase.p, d.d_svn.p,
-                  h->snap.nslots, (uint32_t)h->snap.ops.size(), sr.visited_words, sr.max_ops, sr.max_ops_rel};
-    const size_t vwords = sr.visited_words;
-    const size_t log_entries = c->frontier_entries * 2;  // (the frontier buffer holds the blocks' logs: 8-byte entries)
-    uint32_t cap = kSubjCapFirst;
-    for (size_t b = 0; b < n;) {
-        int rc = check_opts(c->opts);
-        if (rc) return rc;
-        size_t m = std::min<size_t>(n - b, std::max<size_t>(1, log_entries / cap));
-        m = std::min<size_t>(m, std::max<size_t>(1, ((size_t)1 << 28) / std::max<size_t>(vwords + row_words, 1)));  // <= 1 GiB of visited bits and rows
-        if ((size_t)cap * m > log_entries) {  // (one block's log beyond the frontier buffer: grow it)
-            rc = alloc_frontier(h, c, ((uint64_t)cap * m + 1) / 2);
-            if (rc) return rc;
-            if ((size_t)cap * m > c->frontier_entries * 2) return fail(ACL_ERR_RESOURCE_EXHAUSTED, "LookupSubjects: walk region beyond the frontier buffer");
-        }
-        HIP_TRY(c->d_sids.ensure(m));
-        HIP_TRY(c->d_subj_visited.ensure(m * vwords));
-        HIP_TRY(c->d_subj_rows.ensure(std::max<size_t>(m * row_words, 1)));
-        HIP_TRY(c->d_subj_flags.ensure(m));
-        HIP_TRY(c->h_in.ensure(m * sizeof(uint32_t)));
-        HIP_TRY(c->h_out.ensure(std::max<size_t>(m * row_words, 1) * 4 + m * 4));
-        std::memcpy(c->h_in.p, rids + b, m * sizeof(uint32_t));
-        HIP_TRY(hipMemcpyAsync(c->d_sids.p, c->h_in.p, m * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemsetAsync(c->d_subj_visited.p, 0, m * vwords * 4, c->stream));
-        if (row_words) HIP_TRY(hipMemsetAsync(c->d_subj_rows.p, 0, m * row_words * 4, c->stream));
-        HIP_TRY(hipMemsetAsync(c->d_status.p, 0, sizeof(uint32_t), c->stream));
-        ev_begin(c, 0);
-        launch_subj_local(c->stream, g, c->d_sids.p, (uint32_t)m, target, key, c->d_fbuf[0].p, cap, c->d_subj_visited.p, c->d_subj_rows.p, (uint32_t)row_words,
-                          c->d_subj_flags.p, c->d_status.p);
-        ev_end(c);
-        HIP_TRY(hipGetLastError());
-        uint32_t *h_rows = (uint32_t *)c->h_out.p, *h_flags = h_rows + m * row_words;
-        if (row_words) HIP_TRY(hipMemcpyAsync(h_rows, c->d_subj_rows.p, m * row_words * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(h_flags, c->d_subj_flags.p, m * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(c->h_status, c->d_status.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        ev_collect(c);
-        const uint32_t status = c->h_status[0];
-        if (status == 2u) return fail(ACL_ERR_RESOURCE_EXHAUSTED, "LookupSubjects: a row longer than the walk enumerates in one task (2^21 ids)");
-        if (status == 1u) {  // a block's log overflowed: redo the group with larger regions
-            c->stats.overflow_retries++;
-            if (cap >= kSubjCapMax) return fail(ACL_ERR_RESOURCE_EXHAUSTED, "LookupSubjects: the walk of one resource outgrew its region (2^24 states)");
-            cap = std::min(cap * 8u, kSubjCapMax);
-            continue;
-        }
-        for (size_t i = 0; i < m; i++) {
-            uint32_t *dst = bitmaps + (b + i) * words;
-            if (row_words) std::memcpy(dst, h_rows + i * row_words, row_words * 4);
-            std::fill(dst + row_words, dst + words, 0u);
-            wild[b + i] = h_flags[i] ? 1 : 0;
-        }
-        b += m;
-    }
-    return ACL_OK;
+    const DevSubjects g = dev_subjects(h, c);
+    const BlockWalk w{"LookupSubjects", "resource", 2 /* (8-byte log entries) */, row_words, kSubjCapFirst, kSubjCapMax};
+    uint32_t *h_rows = nullptr, *h_flags = nullptr;
+    return block_walk_chunks(
+        h, c, w, n,
+        [&](size_t b, size_t m) {
+            HIP_TRY(c->d_sids.ensure(m));
+            HIP_TRY(c->d_subj_rows.ensure(std::max<size_t>(m * row_words, 1)));
+            HIP_TRY(c->d_subj_flags.ensure(m));
+            HIP_TRY(c->h_in.ensure(m * sizeof(uint32_t)));
+            HIP_TRY(c->h_out.ensure(std::max<size_t>(m * row_words, 1) * 4 + m * 4));
+            std::memcpy(c->h_in.p, rids + b, m * sizeof(uint32_t));
+            HIP_TRY(hipMemcpyAsync(c->d_sids.p, c->h_in.p, m * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+            if (row_words) HIP_TRY(hipMemsetAsync(c->d_subj_rows.p, 0, m * row_words * 4, c->stream));
+            return (int)ACL_OK;
+        },
+        [&](size_t m, uint32_t cap) {
+            ev_begin(c, 0);
+            launch_subj_local(c->stream, g, c->d_sids.p, (uint32_t)m, target, key, c->d_fbuf[0].p, cap, c->d_subj_visited.p, c->d_subj_rows.p, (uint32_t)row_words,
+                              c->d_subj_flags.p, c->d_status.p);
+            ev_end(c);
+            HIP_TRY(hipGetLastError());
+            h_rows = (uint32_t *)c->h_out.p;
+            h_flags = h_rows + m * row_words;
+            if (row_words) HIP_TRY(hipMemcpyAsync(h_rows, c->d_subj_rows.p, m * row_words * 4, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipMemcpyAsync(h_flags, c->d_subj_flags.p, m * 4, hipMemcpyDeviceToHost, c->stream));
+            return (int)ACL_OK;
+        },
+        [&](size_t b, size_t m) {
+            for (size_t i = 0; i < m; i++) {
+                uint32_t *dst = bitmaps + (b + i) * words;
+                if (row_words) std::memcpy(dst, h_rows + i * row_words, row_words * 4);
+                std::fill(dst + row_words, dst + words, 0u);
+                wild[b + i] = h_flags[i] ? 1 : 0;
+            }
+            return (int)ACL_OK;
+        });
 }
 
 // forward Checks of (rt, pm) @ (st, srel) over `items`' subjects, in chunks: answers / errors by index

@@ -2065,6 +2065,49 @@ constexpr uint32_t kRevTaskCap = kRevLocalThreads;  // one (state, op) pair per 
 constexpr uint32_t kRevLocalBudget = 1u << 22;      // children of one round a single block may enumerate
 constexpr uint32_t kRevTerminal = 0x80000000u;      // task target flag: children are only marked, never expanded
 constexpr uint32_t kRevNoMark = 0x40000000u;        // task target flag (OP_NOMARK seed ops): every child is a first visit by construction -- no visited bit
+
+// ---- block primitives of the one-block walks (k_rev_local here; k_subj_local and k_explain_local through subj_block_walk)
+// Block-wide exclusive scan of one degree per thread: before = the sum over the threads below this one, total = the block's sum (block-uniform).
+// One barrier, between the store of the wave totals and their read; a caller that scans again puts a barrier of its own between the two.
+template <int THREADS>
+__device__ __forceinline__ void block_excl_scan(uint32_t deg, uint32_t lane, uint32_t wib, uint32_t *s_wave_tot, uint32_t &before, uint32_t &total) {
+    const uint32_t incl = wave_incl_scan(deg, lane);
+    if (lane == 63) s_wave_tot[wib] = incl;
+    __syncthreads();
+    before = incl - deg;
+    total = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < THREADS / 64; w++) {
+        const uint32_t wt = s_wave_tot[w];
+        before += w < wib ? wt : 0u;
+        total += wt;
+    }
+}
+// Wave-cooperative append of the flagged lanes' entries (uint2 or uint4) to the block's log of `cap` entries, whose end lives in LDS.  A wave that does not
+// fit raises *s_stop = 1 and stores nothing.  Call in wave-uniform control flow.
+template <typename E>
+__device__ __forceinline__ void log_append(E *log, uint32_t cap, uint32_t *s_end, uint32_t *s_stop, uint32_t lane, bool push, const E &e) {
+    const uint64_t b = __ballot(push);
+    if (!b) return;
+    uint32_t base = 0;
+    if (lane == 0) base = atomicAdd(s_end, (uint32_t)__popcll(b));
+    base = uniform(base);
+    if (base + (uint32_t)__popcll(b) > cap) {
+        if (lane == 0) *s_stop = 1u;
+        return;
+    }
+    if (push) log[base + lanes_below(b)] = e;
+}
+// The task that owns output index w: the last of CAP tasks whose exclusive prefix is <= w (threads without a task have degree 0, so it is never one of them)
+template <uint32_t CAP>
+__device__ __forceinline__ uint32_t task_owner(const uint32_t *prefix, uint32_t w) {
+    uint32_t jt = 0;
+#pragma unroll
+    for (uint32_t step = CAP / 2; step >= 1; step >>= 1)
+        if (prefix[jt + step] <= w) jt += step;
+    return jt;
+}
+
 struct RevTaskLds {
     uint32_t start[kRevTaskCap];       // first resource id of the row in `redges`
     uint32_t prefix[kRevTaskCap + 1];  // exclusive prefix of the degrees (a thread without a task: degree 0)
@@ -2207,18 +2250,7 @@ __global__ __launch_bounds__(kRevLocalThreads) void k_rev_local(DevReverse r, co
         return push;
     };
     // wave-cooperative append to the block's log (call in wave-uniform control flow)
-    auto append = [&](bool push, uint32_t id, uint32_t slot) {
-        const uint64_t b = __ballot(push);
-        if (!b) return;
-        uint32_t base = 0;
-        if (lane == 0) base = atomicAdd(&s_end, (uint32_t)__popcll(b));
-        base = uniform(base);
-        if (base + (uint32_t)__popcll(b) > cap) {
-            if (lane == 0) s_stop = 1u;
-            return;
-        }
-        if (push) log[base + lanes_below(b)] = make_uint2(id, slot);
-    };
+    auto append = [&](bool push, uint32_t id, uint32_t slot) { log_append(log, cap, &s_end, &s_stop, lane, push, make_uint2(id, slot)); };
 
     uint32_t lvl_lo = 0, cnt = 1, level = 1;
     int stop = 0;  // block-uniform copy of s_stop (taken through a barrier: s_stop itself may be raised by a faster wave at any time)
@@ -2282,16 +2314,8 @@ __global__ __launch_bounds__(kRevLocalThreads) void k_rev_local(DevReverse r, co
                 append(push, id, tgt & ~(kRevTerminal | kRevNoMark));
             }
             // ---- block-wide exclusive prefix of the degrees
-            const uint32_t incl = wave_incl_scan(deg, lane);
-            if (lane == 63) s_wave_tot[wib] = incl;
-            __syncthreads();
-            uint32_t before = 0, total = 0;
-#pragma unroll
-            for (uint32_t w = 0; w < kRevLocalThreads / 64; w++) {
-                const uint32_t wt = s_wave_tot[w];
-                before += w < wib ? wt : 0u;
-                total += wt;
-            }
+            uint32_t before, total;
+            block_excl_scan<kRevLocalThreads>(deg, lane, wib, s_wave_tot, before, total);
             if (dfr.tasks && total >= dfr.min_children) {  // (block-uniform) a heavy round: its terminal rows of the result slot go to the chip-wide launch
                 const bool mine = deg != 0u && (tgt & kRevTerminal) && (tgt & ~(kRevTerminal | kRevNoMark)) == target_slot;
                 const uint64_t b = __ballot(mine);
@@ -2307,21 +2331,10 @@ __global__ __launch_bounds__(kRevLocalThreads) void k_rev_local(DevReverse r, co
                     }
                 }
                 __syncthreads();  // (every wave has read the totals above)
-                const uint32_t incl2 = wave_incl_scan(deg, lane);
-                if (lane == 63) s_wave_tot[wib] = incl2;
-                __syncthreads();
-                before = 0;
-                total = 0;
-#pragma unroll
-                for (uint32_t w = 0; w < kRevLocalThreads / 64; w++) {
-                    const uint32_t wt = s_wave_tot[w];
-                    before += w < wib ? wt : 0u;
-                    total += wt;
-                }
-                before += incl2 - incl;  // (the code below takes this thread's exclusive prefix as before + incl - deg)
+                block_excl_scan<kRevLocalThreads>(deg, lane, wib, s_wave_tot, before, total);  // (without the deferred rows)
             }
             if (total) {  // (block-uniform)
-                t.prefix[tid] = before + incl - deg;
+                t.prefix[tid] = before;
                 t.start[tid] = start;
                 t.target[tid] = tgt;
                 if (tid == 0 && total > kRevLocalBudget) s_stop = 1u;  // one block should not enumerate this alone: the level loop takes the batch
@@ -2338,10 +2351,7 @@ __global__ __launch_bounds__(kRevLocalThreads) void k_rev_local(DevReverse r, co
                             const uint32_t w = wb + (uint32_t)k * kRevLocalThreads + tid;
                             valid[k] = w < total;
                             const uint32_t wv = valid[k] ? w : total - 1;  // inactive lanes shadow the last child: every load stays in range
-                            uint32_t jt = 0;
-#pragma unroll
-                            for (uint32_t step = kRevTaskCap / 2; step >= 1; step >>= 1)
-                                if (t.prefix[jt + step] <= wv) jt += step;
+                            const uint32_t jt = task_owner<kRevTaskCap>(t.prefix, wv);
                             tj[k] = jt;
                             edge[k] = gld(redges, t.start[jt] + (wv - t.prefix[jt]));
                         }
@@ -2847,17 +2857,22 @@ void launch_rev_import(hipStream_t s, const DevReverse &r, const DevFrontier &f,
     hipLaunchKernelGGL(k_import<false>, dim3(import_blocks(n)), dim3(256), 0, s, f, iter, in, n, (const SlotProg *)nullptr, r.rprogs, 0u);
 }
 
-// ---- LookupSubjects: k_subj_local (plan.hpp SubjectRows).  One block walks one lookup -- the resource's own state and everything the FORWARD programs
-// reach from it -- and writes the subjects of type T (of `key`) it finds into a row of T's ids.  The walk is the positive relaxation of the Check the
-// programs encode: ops inside the subtracted operand of an exclusion are skipped (SubjOp kSubjSkip), both sides of `&` and the tupleset of `.all()` are
-// walked.  Emission rules per op, at dispatch level L = the state's level + op.dlevel <= kMaxLevels (k_check_local's rule: a Check answers HAS there):
+// ---- the forward walk of LookupSubjects and Explain (plan.hpp SubjectRows).  A walk starts at one resource's state and follows the FORWARD programs: the
+// positive relaxation of the Check they encode -- ops inside the subtracted operand of an exclusion are skipped (SubjOp kSubjSkip), both sides of `&` and the
+// tupleset of `.all()` are walked.  Three kernels share it:
+//   k_subj_local     one block per lookup, every level in one launch: subj_block_walk with SubjectsPolicy -- reached rows of the subject class are EMITTED
+//   k_explain_local  one block per item, the same walk with ExplainPolicy -- reached rows are TESTED for the item's one subject, every state remembers its parent
+//   k_subj_expand    one launch per level over the chunked frontier (the sharded graph): its own loop, the same decode
+// subj_decode is the one place that says what an op does, at dispatch level L = the state's level + op.dlevel <= kMaxLevels (k_check_local's rule: a Check
+// answers HAS there):
 //   OP_PROBE_HASH of key T      -> every id of the class's subject row for the state's object (OP_WILD: the row is the wildcard's -> the flag)
 //   OP_PROBE of key T (sorted)  -> every id of the sorted row
 //   OP_REFLEX of key T#r        -> the state's own id
 //   OP_ENUM / OP_PUSH_SAME      -> child states at L + 1 (when L + 1 <= kMaxLevels); a userset row of key T#r is emitted through its children's REFLEX
 //                                  ops, or, when the children would lie beyond the limit, by the probe itself
-// Depth: a state counts at the LEAST level it can be reached at.  The log is processed level by level; a child one level below the current one gets its
-// visited bit when it is appended (nothing of a lower level is still to come), a child further down (an inlined computed userset's offset) is appended
+// (TEST, Explain: "every id of the row" becomes "does the row hold the subject", answered by the device functions of k_check_local's interpreter.)
+// Depth: a state counts at the LEAST level it can be reached at.  subj_block_walk processes its log level by level; a child one level below the current one
+// gets its visited bit when it is appended (nothing of a lower level is still to come), a child further down (an inlined computed userset's offset) is appended
 // unmarked and decides its visit when its own level comes round -- after every state of the levels before it has been marked.
 constexpr int kSubjThreads = 1024;
 constexpr uint32_t kSubjMaxRow = 1u << 21;        // ids of one row a task may enumerate (1 024 tasks x 2 M stay inside 32-bit prefix sums)
@@ -2865,11 +2880,6 @@ constexpr uint32_t kSubjMarked = 0x80000000u;     // log entry: its visit was de
 constexpr uint32_t kSubjDead = 0x40000000u;       // log entry: a second visit, or moved behind the current level: not expanded here
 constexpr uint32_t kSubjEmitEdges = 1u << 30, kSubjEmitIds = 2u << 30, kSubjChild = 3u << 30;  // task kinds (tag bits 30-31)
 namespace {
-struct SubjTaskLds {
-    uint32_t start[kSubjThreads];
-    uint32_t prefix[kSubjThreads + 1];
-    uint32_t tag[kSubjThreads];  // kind | child level << 16 | child slot
-};
 // ORs bit `id` into the result row; lanes holding the same 32-bit word (ascending ids of one row) fold their bits first and one lane issues the atomic.
 // Call in wave-uniform control flow.
 __device__ __forceinline__ void subj_mark(uint32_t *row, bool lds, uint32_t id, bool valid, uint32_t nbits, uint32_t lane) {
@@ -2887,218 +2897,327 @@ __device__ __forceinline__ void subj_mark(uint32_t *row, bool lds, uint32_t id, 
         else __hip_atomic_fetch_or(row + w, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
-}  // namespace
 
-__global__ __launch_bounds__(kSubjThreads) void k_subj_local(DevSubjects g, const uint32_t *__restrict__ rids, uint32_t target_slot, uint32_t key, uint2 *logs,
-                                                             uint32_t cap, uint32_t *visited_all, uint32_t *rows, uint32_t row_words, uint32_t lds_words, uint32_t prog_lds,
-                                                             uint32_t *flags_out, uint32_t *status) {
-    __shared__ SubjTaskLds t;
-    __shared__ uint32_t s_end, s_stop, s_wild, s_wave_tot[kSubjThreads / 64];
-    // dynamic LDS: [programs | ops | side table] when prog_lds, then the result row when lds_words
-    extern __shared__ uint4 s_dyn[];
-    const uint32_t tid = threadIdx.x, lane = lane_id(), wib = tid >> 6;
-    const uint32_t req = blockIdx.x;
-    const SlotProg *progs = g.progs;
-    const FwdOp *ops = g.ops;
-    const SubjOp *sops = g.sops;
-    uint32_t *dyn_words = reinterpret_cast<uint32_t *>(s_dyn);
-    if (prog_lds) {
-        SlotProg *lp = reinterpret_cast<SlotProg *>(s_dyn);
-        FwdOp *lo = reinterpret_cast<FwdOp *>(lp + g.nslots);
-        SubjOp *ls = reinterpret_cast<SubjOp *>(lo + g.nops);
-        for (uint32_t i = tid; i < g.nslots; i += kSubjThreads) lp[i] = g.progs[i];
-        for (uint32_t i = tid; i < g.nops; i += kSubjThreads) {
-            lo[i] = g.ops[i];
-            ls[i] = g.sops[i];
+struct SubjTables {  // what the decode reads: global memory, or a block's staged copy of the first three (subj_stage_programs)
+    const SlotProg *progs;
+    const FwdOp *ops;
+    const SubjOp *sops;
+    const uint2 *__restrict__ meta2, *__restrict__ smeta2;  // {first, end} of the sorted rows / of the subject rows
+};
+__device__ __forceinline__ SubjTables subj_tables(const DevSubjects &g) {
+    return SubjTables{g.progs, g.ops, g.sops, reinterpret_cast<const uint2 *>(g.meta), reinterpret_cast<const uint2 *>(g.smeta)};
+}
+// copies [programs | ops | side table] into dynamic LDS and points T at the copies; returns the first word behind them (no barrier: the caller's follows)
+__device__ __forceinline__ uint32_t *subj_stage_programs(const DevSubjects &g, uint4 *s_dyn, SubjTables &T, uint32_t tid) {
+    SlotProg *lp = reinterpret_cast<SlotProg *>(s_dyn);
+    FwdOp *lo = reinterpret_cast<FwdOp *>(lp + g.nslots);
+    SubjOp *ls = reinterpret_cast<SubjOp *>(lo + g.nops);
+    for (uint32_t i = tid; i < g.nslots; i += kSubjThreads) lp[i] = g.progs[i];
+    for (uint32_t i = tid; i < g.nops; i += kSubjThreads) {
+        lo[i] = g.ops[i];
+        ls[i] = g.sops[i];
+    }
+    T.progs = lp;
+    T.ops = lo;
+    T.sops = ls;
+    return reinterpret_cast<uint32_t *>(ls + g.nops);
+}
+
+struct SubjStep {  // what one (state, op) pair asks of the walk
+    uint32_t start = 0, deg = 0, tag = 0;  // a row to walk: [start, start + deg) of g.sids (kSubjEmitIds) or g.edges; tag = kind | child level << 16 | child slot
+    uint32_t one_slot = 0, one_lvl = 0;
+    uint32_t flags = 0;  // (bits of one word, not four booleans: a divergent boolean that outlives its branch is a 64-bit lane mask)
+    static constexpr uint32_t kOneChild = 1u;  // the state's own object is a child state (OP_PUSH_SAME)
+    static constexpr uint32_t kOneEmit = 2u;   // the state's own id is a subject (OP_REFLEX); TEST: this op finds the item's subject
+    static constexpr uint32_t kWild = 4u;      // a `T:*` row was reached (never with TEST: the wildcard's row is tested like any other)
+    static constexpr uint32_t kTooLong = 8u;   // a row beyond kSubjMaxRow that the walk would have to enumerate
+    __device__ __forceinline__ bool one_child() const { return (flags & kOneChild) != 0u; }
+    __device__ __forceinline__ bool one_emit() const { return (flags & kOneEmit) != 0u; }
+    __device__ __forceinline__ bool wild() const { return (flags & kWild) != 0u; }
+    __device__ __forceinline__ bool too_long() const { return (flags & kTooLong) != 0u; }
+};
+// what a probe does (subj_decode's mode): LookupSubjects hands the probed row back to be emitted, Explain tests it for the item's one subject
+struct SubjEmit {
+    static constexpr bool kTest = false;
+    __device__ __forceinline__ bool is(uint32_t) const { return true; }
+    __device__ __forceinline__ bool hashed_has(const FwdOp &, uint32_t) const { return false; }
+    __device__ __forceinline__ bool sorted_has(const uint2 &) const { return false; }
+};
+struct SubjTest {
+    static constexpr bool kTest = true;
+    const DevGraph *dg;  // what subject_row_contains reads: the forward row descriptors and the hashed buckets
+    uint32_t sid;
+    __device__ __forceinline__ bool is(uint32_t id) const { return id == sid; }
+    __device__ __forceinline__ bool hashed_has(const FwdOp &op, uint32_t id) const { return subject_row_contains(*dg, op, id, sid); }
+    __device__ __forceinline__ bool sorted_has(const uint2 &md) const { return row_contains(dg->edges, md.x, md.y, sid); }
+};
+// Op j of the `nops` ops of program p that count for the state (p's slot, id) at `level`, looking for subjects of `key` (nops: n_total when the subject
+// carries a relation -- REFLEX ops count -- else n_main; 0 for a lane without a state).  Side effects are the caller's: it turns `wild` and `too_long` into
+// its own flag and stop code.  SubjTest: a probed row is tested, which also guards the id, and only ENUMERATED rows can be too long; SubjEmit: the probed
+// row is handed back as a task, guarded by the side table's row count.
+template <typename Mode>
+__device__ __forceinline__ SubjStep subj_decode(const SubjTables &T, const SlotProg &p, uint32_t nops, uint32_t key, uint32_t id, uint32_t level, uint32_t j,
+                                                const Mode &mode) {
+    constexpr bool TEST = Mode::kTest;
+    SubjStep d;
+    if (j >= nops || (T.sops[p.first + j].flags & kSubjSkip)) return d;
+    const FwdOp op = T.ops[p.first + j];
+    const uint32_t L = level + op.dlevel;
+    if (L > kMaxLevels) return d;
+    if (op.flags & OP_REFLEX) {
+        if (op.key == key && mode.is(id)) d.flags = SubjStep::kOneEmit;
+    } else if (op.flags & OP_PUSH_SAME) {
+        if (L + 1u <= kMaxLevels) {
+            d.flags = SubjStep::kOneChild;
+            d.one_slot = op.key;
+            d.one_lvl = L + 1u;
         }
-        progs = lp;
-        ops = lo;
-        sops = ls;
-        dyn_words = reinterpret_cast<uint32_t *>(ls + g.nops);
+    } else if (op.flags & OP_PROBE_HASH) {
+        if (op.key != key) return d;
+        if (TEST) {
+            if (mode.hashed_has(op, id)) d.flags = SubjStep::kOneEmit;
+            return d;
+        }
+        const SubjOp so = T.sops[p.first + j];
+        if (id < so.nrows) {
+            const uint2 rd = T.smeta2[so.base + id];
+            if (rd.y > rd.x) {
+                if (op.flags & OP_WILD) d.flags = SubjStep::kWild;
+                else if (rd.y - rd.x > kSubjMaxRow) d.flags = SubjStep::kTooLong;
+                else {
+                    d.start = rd.x;
+                    d.deg = rd.y - rd.x;
+                    d.tag = kSubjEmitIds;
+                }
+            }
+        }
+    } else if (id < op.nrows) {
+        const uint2 md = T.meta2[op.base + id * op.K + op.k];
+        if (md.y > md.x) {
+            const bool probe = (op.flags & OP_PROBE) && op.key == key;
+            const bool enm = (op.flags & OP_ENUM) && L + 1u <= kMaxLevels;
+            if (TEST && probe && mode.sorted_has(md)) d.flags = SubjStep::kOneEmit;
+            if (md.y - md.x > kSubjMaxRow) {
+                if (enm || (!TEST && probe)) d.flags |= SubjStep::kTooLong;
+            } else if (enm) {
+                d.start = md.x;
+                d.deg = md.y - md.x;
+                d.tag = kSubjChild | ((L + 1u) << 16) | op.key;
+            } else if (!TEST && probe) {
+                d.start = md.x;
+                d.deg = md.y - md.x;
+                d.tag = kSubjEmitEdges;
+            }
+        }
     }
-    const bool row_lds = lds_words != 0u;
-    uint32_t *const row = row_lds ? dyn_words : rows + (size_t)req * row_words;
-    const uint32_t nbits = row_words * 32u;
-    uint32_t *__restrict__ visited = visited_all + (size_t)req * g.visited_words;
-    uint2 *const log = logs + (size_t)req * cap;
-    for (uint32_t i = tid; i < lds_words; i += kSubjThreads) row[i] = 0u;
-    if (tid == 0) {
-        s_end = 1;
-        s_stop = 0;
-        s_wild = 0;
-        log[0] = make_uint2(rids[req], target_slot | (1u << 16));
-    }
-    __syncthreads();
+    return d;
+}
+
+// first visit of state (slot, id) of the lookup whose visited bits start at `visited`?  SCOPE: workgroup where the region is one block's own (the one-block
+// walks), agent where the blocks of a launch share it (k_subj_expand: they sit on different XCDs, whose L2s are not coherent for anything less)
+template <int SCOPE>
+__device__ __forceinline__ bool subj_first_visit(const DevSubjects &g, uint32_t *__restrict__ visited, uint32_t slot, uint32_t id) {
+    const uint32_t vb = g.slot_vbase[slot];
+    if (vb == kSubjNoBits) return true;  // (nothing produces this slot's states: a lookup's own root)
+    if (id >= g.slot_vn[slot]) return false;
+    const uint32_t m = 1u << (id & 31u);
+    return !(__hip_atomic_fetch_or(visited + vb + (id >> 5), m, __ATOMIC_RELAXED, SCOPE) & m);
+}
+
+struct SubjTaskLds {
+    uint32_t start[kSubjThreads];
+    uint32_t prefix[kSubjThreads + 1];
+    uint32_t tag[kSubjThreads];  // kind | child level << 16 | child slot
+};
+struct ExplainTaskLds : SubjTaskLds {
+    uint32_t parent[kSubjThreads];  // log index of the state the row belongs to
+    uint32_t opi[kSubjThreads];     // index of the enumerating op
+};
+template <typename Tasks>
+struct SubjWalkLds {  // the walk's static LDS, declared alignas(16).  The kernel's thread 0 sets end = 1 (the root is log[0]) and stop = 0 before the walk.
+    uint32_t wave_tot[kSubjThreads / 64];  // (first: block_excl_scan reads them back as four 16-byte loads)
+    uint32_t end, stop;
+    Tasks t;
+};
+
+// The level loop of one block.  log[0] is the root, written by the kernel (which also decides whether the root's visit is marked there or left to stage A).
+// Per level: read the log's end behind the previous round's barrier; stage A; rounds of kSubjThreads (state, op) pairs -- decode, the state's own emit and
+// child, a block-wide scan of the degrees, then the lanes walk the concatenated rows (consecutive lanes, consecutive ids of one row); each round closes with
+// one __syncthreads_or of the stop word.  Stops: 1 = the log is full (log_append), 2 = a row too long; the word is last-writer-wins within a round.
+// Returns true when the policy's end-of-level test ended the walk, false when the log ran dry, the depth limit was reached or the walk stopped.
+// The policy P supplies (its hooks run in wave-uniform control flow and contain no barrier):
+//   Entry, entry(id, y, par, opi)   the log entry type; a child's entry from its producer (log index `par` of the parent state, op index `opi`)
+//   Tasks, keep_producer, producer  the task list, and what a row's task remembers of its producer for its children
+//   probe                           the decode's mode (SubjEmit / SubjTest)
+//   state(step, id, me, opi, lane)  the one-lane results of a pair: `wild`, and `one_emit` -- the state's own id is a subject / the op finds the subject
+//   element(v, emit, lane)          one id of an emitted row
+//   level_done(stop)                tested behind the last round of a level, before the stop
+template <typename P>
+__device__ __forceinline__ bool subj_block_walk(P &pol, const DevSubjects &g, const SubjTables &T, uint32_t key, typename P::Entry *log, uint32_t cap,
+                                                uint32_t *__restrict__ visited, SubjWalkLds<typename P::Tasks> &w, uint32_t tid, uint32_t lane, uint32_t wib) {
+    using Entry = typename P::Entry;
     const bool rel_key = key < g.nslots;  // the subject carries a relation: REFLEX ops count
     const uint32_t W = rel_key ? g.max_ops_rel : g.max_ops;
-    const uint2 *__restrict__ meta2 = reinterpret_cast<const uint2 *>(g.meta);
-    const uint2 *__restrict__ smeta2 = reinterpret_cast<const uint2 *>(g.smeta);
-
-    // wave-cooperative append to the block's log (wave-uniform control flow)
-    auto append = [&](bool push, uint32_t id, uint32_t y) {
-        const uint64_t b = __ballot(push);
-        if (!b) return;
-        uint32_t base = 0;
-        if (lane == 0) base = atomicAdd(&s_end, (uint32_t)__popcll(b));
-        base = uniform(base);
-        if (base + (uint32_t)__popcll(b) > cap) {
-            if (lane == 0) s_stop = 1u;
-            return;
-        }
-        if (push) log[base + lanes_below(b)] = make_uint2(id, y);
-    };
-    // first visit of state (slot, id)?  (workgroup scope: the region is this block's own)
-    auto first_visit = [&](uint32_t slot, uint32_t id) -> bool {
-        const uint32_t vb = g.slot_vbase[slot];
-        if (vb == kSubjNoBits) return true;  // (the root's slot when nothing else produces its states)
-        if (id >= g.slot_vn[slot]) return false;
-        const uint32_t m = 1u << (id & 31u);
-        return !(__hip_atomic_fetch_or(visited + vb + (id >> 5), m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) & m);
-    };
     // child (slot, id) at level lvl, produced while level `cur` is expanded
-    auto child = [&](uint32_t id, uint32_t slot, uint32_t lvl, uint32_t cur, bool valid) {
+    auto child = [&](uint32_t id, uint32_t slot, uint32_t lvl, uint32_t cur, bool valid, uint32_t par, uint32_t opi) {
         bool push = false;
         uint32_t y = slot | (lvl << 16);
         if (valid) {
             if (lvl == cur + 1u) {
-                push = first_visit(slot, id);
+                push = subj_first_visit<__HIP_MEMORY_SCOPE_WORKGROUP>(g, visited, slot, id);
                 y |= kSubjMarked;
             } else {
                 push = true;
             }
         }
-        append(push, id, y);
+        log_append(log, cap, &w.end, &w.stop, lane, push, pol.entry(id, y, par, opi));
     };
-
     uint32_t lo = 0, level = 1;
     int stop = 0;
     for (; level <= kMaxLevels; level++) {
-        const uint32_t hi = s_end;  // (behind the previous round's closing barrier)
+        const uint32_t hi = w.end;  // (behind the previous round's closing barrier)
         __syncthreads();            // (every wave has read it before the first append of this level moves it)
         if (hi == lo || hi > cap) break;
-        // ---- stage A: entries of later levels move behind this one; unmarked entries of this level decide their visit now
+        // ---- stage A: entries of later levels move behind this one (as they are, producer included); unmarked entries of this level decide their visit now
         for (uint32_t b0 = lo; b0 < hi; b0 += kSubjThreads) {
             const uint32_t i = b0 + tid;
             bool later = false;
-            uint2 en = make_uint2(0u, 0u);
+            Entry en = pol.entry(0u, 0u, 0u, 0u);
             if (i < hi) {
                 en = log[i];
                 const uint32_t lv = (en.y >> 16) & 63u;
                 if (lv > level) {
                     later = true;
                     log[i].y = en.y | kSubjDead;
-                } else if (!(en.y & kSubjMarked) && !first_visit(en.y & 0xFFFFu, en.x)) {
+                } else if (!(en.y & kSubjMarked) && !subj_first_visit<__HIP_MEMORY_SCOPE_WORKGROUP>(g, visited, en.y & 0xFFFFu, en.x)) {
                     log[i].y = en.y | kSubjDead;
                 }
             }
-            append(later, en.x, en.y & ~(kSubjMarked | kSubjDead));
+            en.y &= ~(kSubjMarked | kSubjDead);
+            log_append(log, cap, &w.end, &w.stop, lane, later, en);
         }
         __syncthreads();
         // ---- stage B: (state, op) pairs, one per thread and round
         const uint32_t npairs = (hi - lo) * W;
         for (uint32_t pb = 0; pb < npairs; pb += kSubjThreads) {
             const uint32_t q = pb + tid;
-            uint32_t deg = 0, start = 0, tag = 0, id = 0, one_slot = 0, one_lvl = 0;
-            bool one_child = false, one_emit = false;
+            SubjStep d;
+            uint32_t id = 0, me = 0, opi = 0;
             if (q < npairs) {
                 const uint32_t e = q / W, j = q - e * W;
-                const uint2 en = log[lo + e];
+                me = lo + e;
+                const Entry en = log[me];
+                id = en.x;  // (read with y whatever the entry's state: one load of the whole entry; a dead entry's id is never used)
                 if (!(en.y & kSubjDead)) {
-                    const SlotProg p = progs[en.y & 0xFFFFu];
-                    const uint32_t nops = rel_key ? p.n_total : p.n_main;
-                    id = en.x;
-                    if (j < nops && !(sops[p.first + j].flags & kSubjSkip)) {
-                        const FwdOp op = ops[p.first + j];
-                        const uint32_t L = level + op.dlevel;
-                        if (L <= kMaxLevels) {
-                            if (op.flags & OP_REFLEX) {
-                                one_emit = op.key == key;
-                            } else if (op.flags & OP_PUSH_SAME) {
-                                if (L + 1u <= kMaxLevels) {
-                                    one_child = true;
-                                    one_slot = op.key;
-                                    one_lvl = L + 1u;
-                                }
-                            } else if (op.flags & OP_PROBE_HASH) {
-                                const SubjOp so = sops[p.first + j];
-                                if (op.key == key && id < so.nrows) {
-                                    const uint2 rd = smeta2[so.base + id];
-                                    if (rd.y > rd.x) {
-                                        if (op.flags & OP_WILD) s_wild = 1u;
-                                        else if (rd.y - rd.x > kSubjMaxRow) s_stop = 2u;
-                                        else {
-                                            start = rd.x;
-                                            deg = rd.y - rd.x;
-                                            tag = kSubjEmitIds;
-                                        }
-                                    }
-                                }
-                            } else if (id < op.nrows) {
-                                const uint2 md = meta2[op.base + id * op.K + op.k];
-                                if (md.y > md.x) {
-                                    const bool probe = (op.flags & OP_PROBE) && op.key == key;
-                                    const bool enm = (op.flags & OP_ENUM) && L + 1u <= kMaxLevels;
-                                    if (md.y - md.x > kSubjMaxRow) {
-                                        if (probe || enm) s_stop = 2u;
-                                    } else if (enm) {
-                                        start = md.x;
-                                        deg = md.y - md.x;
-                                        tag = kSubjChild | ((L + 1u) << 16) | op.key;
-                                    } else if (probe) {
-                                        start = md.x;
-                                        deg = md.y - md.x;
-                                        tag = kSubjEmitEdges;
-                                    }
-                                }
-                            }
-                        }
-                    }
+                    const SlotProg p = T.progs[en.y & 0xFFFFu];
+                    opi = p.first + j;
+                    d = subj_decode(T, p, rel_key ? p.n_total : p.n_main, key, id, level, j, pol.probe);
                 }
             }
-            subj_mark(row, row_lds, id, one_emit, nbits, lane);
-            child(id, one_slot, one_lvl, level, one_child);
-            // ---- block-wide exclusive prefix of the degrees
-            const uint32_t incl = wave_incl_scan(deg, lane);
-            if (lane == 63) s_wave_tot[wib] = incl;
-            __syncthreads();
-            uint32_t before = 0, total = 0;
-#pragma unroll
-            for (uint32_t w = 0; w < kSubjThreads / 64; w++) {
-                const uint32_t wt = s_wave_tot[w];
-                before += w < wib ? wt : 0u;
-                total += wt;
-            }
+            if (d.too_long()) w.stop = 2u;
+            pol.state(d, id, me, opi, lane);
+            child(id, d.one_slot, d.one_lvl, level, d.one_child(), me, opi);
+            uint32_t before, total;
+            block_excl_scan<kSubjThreads>(d.deg, lane, wib, w.wave_tot, before, total);
             if (total) {  // (block-uniform)
-                t.prefix[tid] = before + incl - deg;
-                t.start[tid] = start;
-                t.tag[tid] = tag;
+                w.t.prefix[tid] = before;
+                w.t.start[tid] = d.start;
+                w.t.tag[tid] = d.tag;
+                pol.keep_producer(w.t, tid, me, opi);
                 __syncthreads();
-                // lanes walk the concatenated rows: consecutive lanes, consecutive ids of one row (one task: "the last whose prefix is <= w")
                 for (uint32_t wb = 0; wb < total; wb += kSubjThreads) {
-                    const uint32_t w = wb + tid;
-                    const bool valid = w < total;
-                    const uint32_t wv = valid ? w : total - 1u;
-                    uint32_t jt = 0;
-#pragma unroll
-                    for (uint32_t step = kSubjThreads / 2; step >= 1; step >>= 1)
-                        if (t.prefix[jt + step] <= wv) jt += step;
-                    const uint32_t tg = t.tag[jt], kind = tg & (3u << 30);
-                    const uint32_t pos = t.start[jt] + (wv - t.prefix[jt]);
+                    const uint32_t x = wb + tid;
+                    const bool valid = x < total;
+                    const uint32_t xv = valid ? x : total - 1u;  // (inactive lanes shadow the last id: every load stays in range)
+                    const uint32_t jt = task_owner<kSubjThreads>(w.t.prefix, xv);
+                    const uint32_t tg = w.t.tag[jt], kind = decltype(pol.probe)::kTest ? kSubjChild : tg & (3u << 30);  // (TEST: rows are only ever enumerated)
+                    const uint32_t pos = w.t.start[jt] + (xv - w.t.prefix[jt]);
                     const uint32_t v = kind == kSubjEmitIds ? gld(g.sids, pos) : (gld(g.edges, pos) & kIdMask);
-                    subj_mark(row, row_lds, v, valid && kind != kSubjChild, nbits, lane);
-                    child(v, tg & 0xFFFFu, (tg >> 16) & 63u, level, valid && kind == kSubjChild);
+                    pol.element(v, valid && kind != kSubjChild, lane);
+                    const uint2 from = pol.producer(w.t, jt);
+                    child(v, tg & 0xFFFFu, (tg >> 16) & 63u, level, valid && kind == kSubjChild, from.x, from.y);
                 }
             }
             // (also the barrier behind the task list: every lane is done with it before the next round overwrites it)
-            stop = __syncthreads_or(s_stop != 0u);
+            stop = __syncthreads_or(w.stop != 0u);
             if (stop) break;
         }
+        if (pol.level_done(w.stop)) return true;  // (behind a barrier either way: block-uniform)
         if (stop) break;
         lo = hi;
     }
+    return false;
+}
+
+struct SubjectsPolicy {  // LookupSubjects: 8-byte entries {id, slot | level << 16 | marks}; subjects are marked in the lookup's row
+    using Entry = uint2;
+    using Tasks = SubjTaskLds;
+    uint32_t *row;
+    bool row_lds;
+    uint32_t nbits;
+    uint32_t *s_wild;
+    SubjEmit probe;
+    __device__ __forceinline__ Entry entry(uint32_t id, uint32_t y, uint32_t, uint32_t) const { return make_uint2(id, y); }
+    __device__ __forceinline__ void keep_producer(Tasks &, uint32_t, uint32_t, uint32_t) const {}
+    __device__ __forceinline__ uint2 producer(const Tasks &, uint32_t) const { return make_uint2(0u, 0u); }
+    __device__ __forceinline__ void state(const SubjStep &d, uint32_t id, uint32_t, uint32_t, uint32_t lane) const {
+        if (d.wild()) *s_wild = 1u;
+        subj_mark(row, row_lds, id, d.one_emit(), nbits, lane);
+    }
+    __device__ __forceinline__ void element(uint32_t v, bool emit, uint32_t lane) const { subj_mark(row, row_lds, v, emit, nbits, lane); }
+    __device__ __forceinline__ bool level_done(uint32_t) const { return false; }
+};
+struct ExplainPolicy {  // Explain: 16-byte entries that also carry {log index of the parent, index of the op that produced the state}; the first hit ends the walk
+    using Entry = uint4;
+    using Tasks = ExplainTaskLds;
+    SubjTest probe;
+    unsigned long long *s_hit;  // min over the hits of (log index << 32 | op index)
+    __device__ __forceinline__ Entry entry(uint32_t id, uint32_t y, uint32_t par, uint32_t opi) const { return make_uint4(id, y, par, opi); }
+    __device__ __forceinline__ void keep_producer(Tasks &t, uint32_t tid, uint32_t me, uint32_t opi) const {
+        t.parent[tid] = me;
+        t.opi[tid] = opi;
+    }
+    __device__ __forceinline__ uint2 producer(const Tasks &t, uint32_t jt) const { return make_uint2(t.parent[jt], t.opi[jt]); }
+    __device__ __forceinline__ void state(const SubjStep &d, uint32_t, uint32_t me, uint32_t opi, uint32_t) const {
+        if (d.one_emit()) atomicMin(s_hit, ((unsigned long long)me << 32) | opi);
+    }
+    __device__ __forceinline__ void element(uint32_t, bool, uint32_t) const {}
+    // A log that overflowed on children of the level that found the subject does not matter: the hit state and its ancestors were appended before this level
+    // began, and nothing below them is needed.  An enumerated row beyond the limit (2) still fails.  (The stop word is last-writer-wins: an append's 1 may
+    // overwrite a 2 of the same round.  That only decides whether a witness already found is returned; it is valid either way.)
+    __device__ __forceinline__ bool level_done(uint32_t stop) const { return *s_hit != ~0ull && stop != 2u; }
+};
+}  // namespace
+
+// LookupSubjects, one block per lookup: setup, subj_block_walk, then the row and the wildcard flag go out.  The root is appended UNMARKED: stage A of the first
+// level decides its visit, so a resource id beyond its slot's visited bits is not walked.
+__global__ __launch_bounds__(kSubjThreads) void k_subj_local(DevSubjects g, const uint32_t *__restrict__ rids, uint32_t target_slot, uint32_t key, uint2 *logs,
+                                                             uint32_t cap, uint32_t *visited_all, uint32_t *rows, uint32_t row_words, uint32_t lds_words, uint32_t prog_lds,
+                                                             uint32_t *flags_out, uint32_t *status) {
+    __shared__ alignas(16) SubjWalkLds<SubjTaskLds> w;
+    __shared__ uint32_t s_wild;
+    // dynamic LDS: [programs | ops | side table] when prog_lds, then the result row when lds_words
+    extern __shared__ uint4 s_dyn[];
+    const uint32_t tid = threadIdx.x, lane = lane_id(), wib = tid >> 6;
+    const uint32_t req = blockIdx.x;
+    SubjTables T = subj_tables(g);
+    uint32_t *const dyn_words = prog_lds ? subj_stage_programs(g, s_dyn, T, tid) : reinterpret_cast<uint32_t *>(s_dyn);
+    const bool row_lds = lds_words != 0u;
+    uint32_t *const row = row_lds ? dyn_words : rows + (size_t)req * row_words;
+    uint2 *const log = logs + (size_t)req * cap;
+    for (uint32_t i = tid; i < lds_words; i += kSubjThreads) row[i] = 0u;
+    if (tid == 0) {
+        w.end = 1;
+        w.stop = 0;
+        s_wild = 0;
+        log[0] = make_uint2(rids[req], target_slot | (1u << 16));
+    }
+    __syncthreads();
+    SubjectsPolicy pol{row, row_lds, row_words * 32u, &s_wild, SubjEmit{}};
+    subj_block_walk(pol, g, T, key, log, cap, visited_all + (size_t)req * g.visited_words, w, tid, lane, wib);
     __syncthreads();
     if (tid == 0) {
-        if (s_stop) *status = s_stop;
+        if (w.stop) *status = w.stop;
         flags_out[req] = s_wild;
     }
     if (row_lds) {
@@ -3107,12 +3226,15 @@ __global__ __launch_bounds__(kSubjThreads) void k_subj_local(DevSubjects g, cons
     }
 }
 
+// bytes of [programs | ops | side table]; staged in the walking block's LDS when they fit kSubjLdsProgBytes
+static size_t subj_prog_bytes(const DevSubjects &g) { return (size_t)g.nslots * sizeof(SlotProg) + (size_t)g.nops * (sizeof(FwdOp) + sizeof(SubjOp)); }
+
 void launch_subj_local(hipStream_t s, const DevSubjects &g, const uint32_t *rids, uint32_t n, uint32_t target_slot, uint32_t key, void *logs, uint32_t cap,
                        uint32_t *visited, uint32_t *rows, uint32_t row_words, uint32_t *flags_out, uint32_t *status) {
     if (!n) return;
     static const bool big_lds =
         hipFuncSetAttribute(reinterpret_cast<const void *>(k_subj_local), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kRevLdsRowBytes + kSubjLdsProgBytes)) == hipSuccess;
-    const size_t prog_bytes = (size_t)g.nslots * sizeof(SlotProg) + (size_t)g.nops * (sizeof(FwdOp) + sizeof(SubjOp));
+    const size_t prog_bytes = subj_prog_bytes(g);
     const uint32_t prog_lds = prog_bytes <= kSubjLdsProgBytes ? 1u : 0u;
     const uint32_t lds_words = (size_t)row_words * 4u <= (big_lds ? kRevLdsRowBytes : 16384u) ? row_words : 0u;
     const size_t dyn = (prog_lds ? prog_bytes : 0u) + (size_t)lds_words * 4u;
@@ -3120,226 +3242,46 @@ void launch_subj_local(hipStream_t s, const DevSubjects &g, const uint32_t *rids
                        flags_out, status);
 }
 
-// ---- Explain: k_explain_local (engine_explain.cpp).  k_subj_local's walk with a memory and an early exit: one block walks ONE item -- from the item's resource
-// down the forward programs -- and where k_subj_local emits the ids of a row, this kernel TESTS the row for the item's one subject, with the device functions
-// k_check_local's interpreter uses (subject_row_contains, row_contains): a hit here is a hit of Check's.  Log entries are 16 bytes and carry how the state was
-// reached: {id, slot | level << 16 | marks, log index of the parent, index of the op that produced it}.  The log discipline and the depth arithmetic are
-// k_subj_local's (levels one at a time, a child one level down marked at append, later levels moved behind the current one), so a state counts at the least level
-// it can be reached at and a witness exists exactly where Check answers HAS.  A hit does an LDS atomicMin of (log index << 32 | op index); the walk ends behind
-// the first level that produced one and one lane follows the parent indices back to entry 0, writing {op, parent id, child id, flags} records in path order.
-namespace {
-struct ExplainTaskLds {
-    uint32_t start[kSubjThreads];
-    uint32_t prefix[kSubjThreads + 1];
-    uint32_t tag[kSubjThreads];     // child level << 16 | child slot
-    uint32_t parent[kSubjThreads];  // log index of the state the row belongs to
-    uint32_t opi[kSubjThreads];     // index of the enumerating op
-};
-}  // namespace
-
+// ---- Explain: k_explain_local (engine_explain.cpp).  One block walks ONE item -- from the item's resource down the forward programs, subj_block_walk with
+// ExplainPolicy -- and where LookupSubjects emits the ids of a row, this walk TESTS the row for the item's one subject, with the device functions k_check_local's
+// interpreter uses (subject_row_contains, row_contains): a hit here is a hit of Check's.  Log entries are 16 bytes and carry how the state was reached:
+// {id, slot | level << 16 | marks, log index of the parent, index of the op that produced it}.  The log discipline and the depth arithmetic are the shared
+// walk's, so a state counts at the least level it can be reached at and a witness exists exactly where Check answers HAS.  A hit does an LDS atomicMin of
+// (log index << 32 | op index); the walk ends behind the first level that produced one and one lane follows the parent indices back to entry 0, writing
+// {op, parent id, child id, flags} records in path order.
 __global__ __launch_bounds__(kSubjThreads) void k_explain_local(DevSubjects g, const uint32_t *__restrict__ buckets, const uint4 *__restrict__ items, uint4 *logs,
                                                                 uint32_t cap, uint32_t *visited_all, uint32_t prog_lds, uint4 *__restrict__ traces,
                                                                 uint32_t *__restrict__ counts, uint32_t *status) {
-    __shared__ ExplainTaskLds t;
-    __shared__ uint32_t s_end, s_stop, s_wave_tot[kSubjThreads / 64];
+    __shared__ alignas(16) SubjWalkLds<ExplainTaskLds> w;
     __shared__ unsigned long long s_hit;
     extern __shared__ uint4 s_dyn[];  // [programs | ops | side table] when prog_lds
     const uint32_t tid = threadIdx.x, lane = lane_id(), wib = tid >> 6;
     const uint32_t req = blockIdx.x;
-    const SlotProg *progs = g.progs;
-    const FwdOp *ops = g.ops;
-    const SubjOp *sops = g.sops;
-    if (prog_lds) {
-        SlotProg *lp = reinterpret_cast<SlotProg *>(s_dyn);
-        FwdOp *lo = reinterpret_cast<FwdOp *>(lp + g.nslots);
-        SubjOp *ls = reinterpret_cast<SubjOp *>(lo + g.nops);
-        for (uint32_t i = tid; i < g.nslots; i += kSubjThreads) lp[i] = g.progs[i];
-        for (uint32_t i = tid; i < g.nops; i += kSubjThreads) {
-            lo[i] = g.ops[i];
-            ls[i] = g.sops[i];
-        }
-        progs = lp;
-        ops = lo;
-        sops = ls;
-    }
+    SubjTables T = subj_tables(g);
+    if (prog_lds) (void)subj_stage_programs(g, s_dyn, T, tid);
     const uint4 item = items[req];  // {resource id, target slot, subject key, subject id}
-    const uint32_t key = item.z, sid = item.w;
+    const uint32_t sid = item.w;
     uint32_t *__restrict__ visited = visited_all + (size_t)req * g.visited_words;
     uint4 *const log = logs + (size_t)req * cap;
     if (tid == 0) {
-        s_end = 1;
-        s_stop = 0;
+        w.end = 1;
+        w.stop = 0;
         s_hit = ~0ull;
         log[0] = make_uint4(item.x, item.y | (1u << 16) | kSubjMarked, 0u, 0u);  // (the root is walked whatever its id: an object no relationship names can still be its own subject)
     }
     __syncthreads();
-    const bool rel_key = key < g.nslots;  // the subject carries a relation: REFLEX ops count
-    const uint32_t W = rel_key ? g.max_ops_rel : g.max_ops;
-    const uint2 *__restrict__ meta2 = reinterpret_cast<const uint2 *>(g.meta);
     DevGraph dg{};  // (what subject_row_contains reads: the forward row descriptors and the hashed buckets)
     dg.meta = g.meta;
     dg.edges = g.edges;
     dg.buckets = buckets;
-
-    auto append = [&](bool push, uint32_t id, uint32_t y, uint32_t par, uint32_t opi) {
-        const uint64_t b = __ballot(push);
-        if (!b) return;
-        uint32_t base = 0;
-        if (lane == 0) base = atomicAdd(&s_end, (uint32_t)__popcll(b));
-        base = uniform(base);
-        if (base + (uint32_t)__popcll(b) > cap) {
-            if (lane == 0) s_stop = 1u;
-            return;
-        }
-        if (push) log[base + lanes_below(b)] = make_uint4(id, y, par, opi);
-    };
-    auto first_visit = [&](uint32_t slot, uint32_t id) -> bool {
-        const uint32_t vb = g.slot_vbase[slot];
-        if (vb == kSubjNoBits) return true;
-        if (id >= g.slot_vn[slot]) return false;
-        const uint32_t m = 1u << (id & 31u);
-        return !(__hip_atomic_fetch_or(visited + vb + (id >> 5), m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) & m);
-    };
-    auto child = [&](uint32_t id, uint32_t slot, uint32_t lvl, uint32_t cur, bool valid, uint32_t par, uint32_t opi) {
-        bool push = false;
-        uint32_t y = slot | (lvl << 16);
-        if (valid) {
-            if (lvl == cur + 1u) {
-                push = first_visit(slot, id);
-                y |= kSubjMarked;
-            } else {
-                push = true;
-            }
-        }
-        append(push, id, y, par, opi);
-    };
-
-    if (tid == 0) (void)first_visit(item.y, item.x);  // (ordered before every other visit by the first level's barriers)
-    uint32_t lo = 0, level = 1;
-    int stop = 0;
-    bool found = false;
-    for (; level <= kMaxLevels; level++) {
-        const uint32_t hi = s_end;
-        __syncthreads();
-        if (hi == lo || hi > cap) break;
-        // ---- stage A: entries of later levels move behind this one (with their parents); unmarked entries of this level decide their visit now
-        for (uint32_t b0 = lo; b0 < hi; b0 += kSubjThreads) {
-            const uint32_t i = b0 + tid;
-            bool later = false;
-            uint4 en = make_uint4(0u, 0u, 0u, 0u);
-            if (i < hi) {
-                en = log[i];
-                const uint32_t lv = (en.y >> 16) & 63u;
-                if (lv > level) {
-                    later = true;
-                    log[i].y = en.y | kSubjDead;
-                } else if (!(en.y & kSubjMarked) && !first_visit(en.y & 0xFFFFu, en.x)) {
-                    log[i].y = en.y | kSubjDead;
-                }
-            }
-            append(later, en.x, en.y & ~(kSubjMarked | kSubjDead), en.z, en.w);
-        }
-        __syncthreads();
-        // ---- stage B: (state, op) pairs, one per thread and round
-        const uint32_t npairs = (hi - lo) * W;
-        for (uint32_t pb = 0; pb < npairs; pb += kSubjThreads) {
-            const uint32_t q = pb + tid;
-            uint32_t deg = 0, start = 0, tag = 0, id = 0, one_slot = 0, one_lvl = 0, me = 0, opi = 0;
-            bool one_child = false, hit = false;
-            if (q < npairs) {
-                const uint32_t e = q / W, j = q - e * W;
-                me = lo + e;
-                const uint4 en = log[me];
-                if (!(en.y & kSubjDead)) {
-                    const SlotProg p = progs[en.y & 0xFFFFu];
-                    const uint32_t nops = rel_key ? p.n_total : p.n_main;
-                    id = en.x;
-                    opi = p.first + j;
-                    if (j < nops && !(sops[opi].flags & kSubjSkip)) {
-                        const FwdOp op = ops[opi];
-                        const uint32_t L = level + op.dlevel;
-                        if (L <= kMaxLevels) {
-                            if (op.flags & OP_REFLEX) {
-                                hit = op.key == key && id == sid;
-                            } else if (op.flags & OP_PUSH_SAME) {
-                                if (L + 1u <= kMaxLevels) {
-                                    one_child = true;
-                                    one_slot = op.key;
-                                    one_lvl = L + 1u;
-                                }
-                            } else if (op.flags & OP_PROBE_HASH) {
-                                if (op.key == key) hit = subject_row_contains(dg, op, id, sid);
-                            } else if (id < op.nrows) {
-                                const uint2 md = meta2[op.base + id * op.K + op.k];
-                                if (md.y > md.x) {
-                                    if ((op.flags & OP_PROBE) && op.key == key) hit = row_contains(g.edges, md.x, md.y, sid);
-                                    if ((op.flags & OP_ENUM) && L + 1u <= kMaxLevels) {
-                                        if (md.y - md.x > kSubjMaxRow) {
-                                            s_stop = 2u;
-                                        } else {
-                                            start = md.x;
-                                            deg = md.y - md.x;
-                                            tag = ((L + 1u) << 16) | op.key;
-                                        }
-                                    }
-                                }
-                            }
-                        }
-                    }
-                }
-            }
-            if (hit) atomicMin(&s_hit, ((unsigned long long)me << 32) | opi);
-            child(id, one_slot, one_lvl, level, one_child, me, opi);
-            // ---- block-wide exclusive prefix of the degrees
-            const uint32_t incl = wave_incl_scan(deg, lane);
-            if (lane == 63) s_wave_tot[wib] = incl;
-            __syncthreads();
-            uint32_t before = 0, total = 0;
-#pragma unroll
-            for (uint32_t w = 0; w < kSubjThreads / 64; w++) {
-                const uint32_t wt = s_wave_tot[w];
-                before += w < wib ? wt : 0u;
-                total += wt;
-            }
-            if (total) {  // (block-uniform)
-                t.prefix[tid] = before + incl - deg;
-                t.start[tid] = start;
-                t.tag[tid] = tag;
-                t.parent[tid] = me;
-                t.opi[tid] = opi;
-                __syncthreads();
-                for (uint32_t wb = 0; wb < total; wb += kSubjThreads) {
-                    const uint32_t w = wb + tid;
-                    const bool valid = w < total;
-                    const uint32_t wv = valid ? w : total - 1u;
-                    uint32_t jt = 0;
-#pragma unroll
-                    for (uint32_t step = kSubjThreads / 2; step >= 1; step >>= 1)
-                        if (t.prefix[jt + step] <= wv) jt += step;
-                    const uint32_t tg = t.tag[jt];
-                    const uint32_t v = gld(g.edges, t.start[jt] + (wv - t.prefix[jt])) & kIdMask;
-                    child(v, tg & 0xFFFFu, (tg >> 16) & 63u, level, valid, t.parent[jt], t.opi[jt]);
-                }
-            }
-            // (also the barrier behind the task list: every lane is done with it before the next round overwrites it)
-            stop = __syncthreads_or(s_stop != 0u);
-            if (stop) break;
-        }
-        // (behind a barrier either way: block-uniform)  A log that overflowed on children of the level that found the subject does not matter: the hit state
-        // and its ancestors were appended before this level began, and nothing below them is needed.  An enumerated row beyond the limit (2) still fails.
-        // (s_stop is last-writer-wins: an append's 1 may overwrite a 2 of the same round.  That only decides whether a witness already found is returned; it is valid either way.)
-        if (s_hit != ~0ull && s_stop != 2u) {
-            found = true;
-            break;
-        }
-        if (stop) break;
-        lo = hi;
-    }
+    if (tid == 0) (void)subj_first_visit<__HIP_MEMORY_SCOPE_WORKGROUP>(g, visited, item.y, item.x);  // (the root's MARKED entry: ordered before every other visit by the first level's barriers)
+    ExplainPolicy pol{SubjTest{&dg, sid}, &s_hit};
+    const bool found = subj_block_walk(pol, g, T, item.z, log, cap, visited, w, tid, lane, wib);
     __syncthreads();
     if (tid != 0) return;
     // ---- back-trace (one lane): at most kMaxLevels states lie on a path (their levels ascend), every index is checked before it is followed
-    if (s_stop && !found) {
-        *status = s_stop;
+    if (w.stop && !found) {
+        *status = w.stop;
         counts[req] = 1u << 16;
         return;
     }
@@ -3347,7 +3289,7 @@ __global__ __launch_bounds__(kSubjThreads) void k_explain_local(DevSubjects g, c
         counts[req] = 1u << 16;  // not found
         return;
     }
-    const uint32_t end = min(s_end, cap);
+    const uint32_t end = min(w.end, cap);
     const uint32_t h = (uint32_t)(s_hit >> 32), ho = (uint32_t)s_hit;
     uint32_t depth = 0, i = h;
     bool bad = h >= end || ho >= g.nops;
@@ -3363,7 +3305,7 @@ __global__ __launch_bounds__(kSubjThreads) void k_explain_local(DevSubjects g, c
     }
     uint4 *const rec = traces + (size_t)req * (kMaxLevels + 1u);
     uint32_t n = depth;
-    const FwdOp fo = ops[ho];
+    const FwdOp fo = T.ops[ho];
     if (!(fo.flags & OP_REFLEX)) {
         const bool wild = (fo.flags & OP_WILD) != 0u;
         rec[n++] = make_uint4(ho, log[h].x, wild ? fo.K : sid, wild ? 1u : 0u);
@@ -3381,7 +3323,7 @@ __global__ __launch_bounds__(kSubjThreads) void k_explain_local(DevSubjects g, c
 void launch_explain_local(hipStream_t s, const DevSubjects &g, const uint32_t *buckets, const uint4 *items, uint32_t n, void *logs, uint32_t cap, uint32_t *visited,
                           uint4 *traces, uint32_t *counts, uint32_t *status) {
     if (!n) return;
-    const size_t prog_bytes = (size_t)g.nslots * sizeof(SlotProg) + (size_t)g.nops * (sizeof(FwdOp) + sizeof(SubjOp));
+    const size_t prog_bytes = subj_prog_bytes(g);
     const uint32_t prog_lds = prog_bytes <= kSubjLdsProgBytes ? 1u : 0u;
     hipLaunchKernelGGL(k_explain_local, dim3(n), dim3(kSubjThreads), prog_lds ? prog_bytes : 0u, s, g, buckets, items, (uint4 *)logs, cap, visited, prog_lds, traces,
                        counts, status);
@@ -3389,7 +3331,7 @@ void launch_explain_local(hipStream_t s, const DevSubjects &g, const uint32_t *b
 
 // ---- LookupSubjects, level-synchronous: k_subj_expand (the sharded graph's native loop, engine_shard_subjects.cpp).  One launch = one dispatch level of ALL
 // lookups of a chunk on all CUs, over the chunked frontier of k_expand / k_rev_expand.  Entry: x = object id, y = lookup index, z = slot | level << 16 |
-// kSubjMarked, w = 0.  The emission rules and the depth arithmetic per op are k_subj_local's; what differs is WHEN a visit is decided.  There, unmarked
+// kSubjMarked, w = 0.  What an op does is subj_decode's, as in the one-block walk (subj_block_walk); what differs is WHEN a visit is decided.  There, unmarked
 // entries of level L decide behind a block barrier that follows every append of level L - 1.  Here other blocks (and other shards) are still appending, so
 // every decision for a level-L state is taken while iteration L - 1 runs: where an L - 1 state's direct child is appended, where an entry that becomes due
 // next is carried over, and where an exchanged entry is imported.  Entries of later levels travel unmarked.  Every visited bit set during iteration L - 1
@@ -3397,12 +3339,7 @@ void launch_explain_local(hipStream_t s, const DevSubjects &g, const uint32_t *b
 // that owns the slot's type, and only there).  Iteration L reads: marked entries of level L (expanded), unmarked entries of levels > L (carried).
 namespace {
 __device__ __forceinline__ bool subj_first_visit(const DevSubjLevel &s, uint32_t req, uint32_t slot, uint32_t id) {
-    const uint32_t vb = s.g.slot_vbase[slot];
-    if (vb == kSubjNoBits) return true;  // (nothing produces this slot's states: a lookup's own root)
-    if (id >= s.g.slot_vn[slot]) return false;
-    const uint32_t m = 1u << (id & 31u);
-    // agent scope: the blocks of a launch sit on different XCDs, whose L2s are not coherent for anything less
-    return !(__hip_atomic_fetch_or(s.visited + (size_t)req * s.g.visited_words + vb + (id >> 5), m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & m);
+    return subj_first_visit<__HIP_MEMORY_SCOPE_AGENT>(s.g, s.visited + (size_t)req * s.g.visited_words, slot, id);
 }
 // wave-cooperative append of the flagged lanes' entries to the frontier iteration `iter` produces (wave-uniform control flow)
 __device__ __forceinline__ void subj_append(WaveOut &wo, uint32_t lane, bool push, uint32_t id, uint32_t req, uint32_t z) {
@@ -3442,7 +3379,7 @@ __global__ __launch_bounds__(256) void k_subj_seed(DevSubjLevel s, DevFrontier f
     if (i >= n) return;
     const uint32_t id = rids[i];
     bool mine = sh.world <= 1u || s.g.progs[target_slot].owner == sh.rank;
-    if (mine) mine = subj_first_visit(s, i, target_slot, id);  // (an id beyond the visited bits: no walk, as k_subj_local)
+    if (mine) mine = subj_first_visit(s, i, target_slot, id);  // (an id beyond the visited bits: no walk, as in the one-block walk)
     f.buf[0][i] = make_uint4(id, i, mine ? (target_slot | (1u << 16) | kSubjMarked) : kDeadMeta, 0u);
 }
 
@@ -3463,8 +3400,7 @@ __global__ __launch_bounds__(kBlock) void k_subj_expand(DevSubjLevel s, DevFront
     const DevSubjects &g = s.g;
     const bool rel_key = s.key < g.nslots;  // the subject carries a relation: REFLEX ops count
     const uint32_t nbits = s.row_words * 32u;
-    const uint2 *__restrict__ meta2 = reinterpret_cast<const uint2 *>(g.meta);
-    const uint2 *__restrict__ smeta2 = reinterpret_cast<const uint2 *>(g.smeta);
+    const SubjTables T = subj_tables(g);
     // segment-major work order: k_expand's ChunkWalk (the fill counts of the wave's next 64 segment slots in one gather)
     const uint32_t nslot = C * kSegsPerChunk;
     for (uint32_t x0 = wave; x0 < nslot; x0 += 64 * nwaves) {
@@ -3507,65 +3443,20 @@ __global__ __launch_bounds__(kBlock) void k_subj_expand(DevSubjLevel s, DevFront
             const uint32_t nops = expand ? (rel_key ? p.n_total : p.n_main) : 0u;
             const uint32_t maxops = wave_max(nops);
             for (uint32_t j = 0; j < maxops; j++) {
-                uint32_t deg = 0, start = 0, tag = 0, one_slot = 0, one_lvl = 0;
-                bool one_child = false, one_emit = false;
-                if (j < nops && !(g.sops[p.first + j].flags & kSubjSkip)) {
-                    const FwdOp op = g.ops[p.first + j];
-                    const uint32_t L = level + op.dlevel;
-                    if (L <= kMaxLevels) {
-                        if (op.flags & OP_REFLEX) {
-                            one_emit = op.key == s.key;
-                        } else if (op.flags & OP_PUSH_SAME) {
-                            if (L + 1u <= kMaxLevels) {
-                                one_child = true;
-                                one_slot = op.key;
-                                one_lvl = L + 1u;
-                            }
-                        } else if (op.flags & OP_PROBE_HASH) {
-                            const SubjOp so = g.sops[p.first + j];
-                            if (op.key == s.key && id < so.nrows) {
-                                const uint2 rd = smeta2[so.base + id];
-                                if (rd.y > rd.x) {
-                                    if (op.flags & OP_WILD) s.flags[req] = 1;
-                                    else if (rd.y - rd.x > kSubjMaxRow) *f.overflow = 2u;
-                                    else {
-                                        start = rd.x;
-                                        deg = rd.y - rd.x;
-                                        tag = kSubjEmitIds;
-                                    }
-                                }
-                            }
-                        } else if (id < op.nrows) {
-                            const uint2 md = meta2[op.base + id * op.K + op.k];
-                            if (md.y > md.x) {
-                                const bool probe = (op.flags & OP_PROBE) && op.key == s.key;
-                                const bool enm = (op.flags & OP_ENUM) && L + 1u <= kMaxLevels;
-                                if (md.y - md.x > kSubjMaxRow) {
-                                    if (probe || enm) *f.overflow = 2u;
-                                } else if (enm) {
-                                    start = md.x;
-                                    deg = md.y - md.x;
-                                    tag = kSubjChild | ((L + 1u) << 16) | op.key;
-                                } else if (probe) {
-                                    start = md.x;
-                                    deg = md.y - md.x;
-                                    tag = kSubjEmitEdges;
-                                }
-                            }
-                        }
-                    }
-                }
+                const SubjStep d = subj_decode(T, p, nops, s.key, id, level, j, SubjEmit{});
+                if (d.wild()) s.flags[req] = 1;
+                if (d.too_long()) *f.overflow = 2u;
                 // the state itself is the subject (REFLEX): the lanes hold different lookups, so each ORs its own bit
-                if (one_emit && id < nbits)
+                if (d.one_emit() && id < nbits)
                     __hip_atomic_fetch_or(s.rows + (size_t)req * s.row_words + (id >> 5), 1u << (id & 31u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                subj_child<SHARDED>(s, wo, sh, iter, lane, one_child, id, req, one_slot, one_lvl);
+                subj_child<SHARDED>(s, wo, sh, iter, lane, d.one_child(), id, req, d.one_slot, d.one_lvl);
                 // rows: the wave walks one lane's row at a time, consecutive lanes on consecutive ids (coalesced; ascending ids fold in subj_mark)
-                uint64_t todo = __ballot(deg != 0);
+                uint64_t todo = __ballot(d.deg != 0);
                 while (todo) {
                     const int src = __ffsll((unsigned long long)todo) - 1;
                     todo &= todo - 1;
-                    const uint32_t tstart = (uint32_t)__builtin_amdgcn_readlane((int)start, src), tdeg = (uint32_t)__builtin_amdgcn_readlane((int)deg, src);
-                    const uint32_t ttag = (uint32_t)__builtin_amdgcn_readlane((int)tag, src), treq = (uint32_t)__builtin_amdgcn_readlane((int)req, src);
+                    const uint32_t tstart = (uint32_t)__builtin_amdgcn_readlane((int)d.start, src), tdeg = (uint32_t)__builtin_amdgcn_readlane((int)d.deg, src);
+                    const uint32_t ttag = (uint32_t)__builtin_amdgcn_readlane((int)d.tag, src), treq = (uint32_t)__builtin_amdgcn_readlane((int)req, src);
                     const uint32_t kind = ttag & (3u << 30);
                     uint32_t *row = s.rows + (size_t)treq * s.row_words;
                     for (uint32_t o = 0; o < tdeg; o += 64) {

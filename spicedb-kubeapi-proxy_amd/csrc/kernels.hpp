@@ -191,7 +191,7 @@ struct DevSubjects {
 constexpr uint32_t kSubjLdsProgBytes = 16u << 10;  // programs + ops + side table staged in LDS up to this size
 void launch_subj_local(hipStream_t s, const DevSubjects &g, const uint32_t *rids, uint32_t n, uint32_t target_slot, uint32_t key, void *logs, uint32_t cap,
                        uint32_t *visited, uint32_t *rows, uint32_t row_words, uint32_t *flags_out, uint32_t *status);
-// single-launch Explain (kernels.hip k_explain_local): block b walks the forward programs from item b's resource, as k_subj_local does, until the level at
+// single-launch Explain (kernels.hip k_explain_local): block b walks the forward programs from item b's resource, by the walk k_subj_local uses, until the level at
 // which the item's ONE subject is found, and writes the path that led there.  items: [n] {resource id, target slot, subject key, subject id}; buckets: the forward
 // snapshot's hashed rows (DevGraph::buckets); logs: [n][cap] 16-byte entries; visited: [n][g.visited_words] zeroed by the caller.
 //   counts[b] = records written | state << 16 (kExplainFound: a path; kExplainNotFound: no level produced a hit, or the walk stopped; kExplainBadTrace: the

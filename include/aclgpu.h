@@ -447,6 +447,24 @@ typedef struct acl_watch_set acl_watch_set_t;
 typedef struct { uint32_t watcher, resource_id, gained /* 1 gained, 0 lost */, reserved; } acl_watch_change_t;
 #define ACL_WATCHER_FROM_NOW 1u   /* baseline = what the subject holds at the first poll after the add: nothing is reported for it */
 int acl_watch_set_open(acl_engine_t *h, int rtype, int permission, int stype, int srel /* -1 none */, acl_watch_set_t **out);
+/* ---- subject-direction watch sets: who gained or lost `permission` on each watched RESOURCE (the audit question) ----
+ * A set opened this way turns the question round: its watchers are resources of `rtype`, its rows their LookupSubjects answers for subjects `stype[#srel]`.
+ * Every other call is the one above, read with the two sides swapped:
+ *  - acl_watch_set_add takes the id of a RESOURCE of rtype (validated, interned pinned, as the subject is above); ACL_WATCHER_FROM_NOW as above;
+ *  - in the records acl_watch_change_t.resource_id carries a SUBJECT id of stype (resolve it with acl_object_name_copy for stype, within the recycling
+ *    quarantine); records are ordered by (watcher, that id); acl_watch_set_row needs the words of stype's ids;
+ *  - rows: after a successful poll bit s of watcher r's row is set iff acl_lookup_subjects_batch would report s for r on that snapshot.  Where that answer
+ *    carries ACL_SUBJECTS_WILDCARD the bit of the subject type's wildcard object (the name `*`) is set as well, and the record that reports that bit carries
+ *    ACL_WATCH_CHANGE_WILDCARD in `reserved`; the walk never sets that bit as a concrete subject.  On a permission with `&` / `-` / `.all()` that a wildcard
+ *    grants, the row holds every existing subject of the type that holds the permission (the complement of acl_lookup_subjects' excluded row, without the
+ *    wildcard's own id): unbanning a user under `viewer: user:*` is that user's gain.  On a permission WITHOUT them that a wildcard grants the row keeps only
+ *    the named subjects and the wildcard bit -- everybody holds it, a subject behind the wildcard is not reported individually;
+ *  - candidates of a permission with `&` / `-` / `.all()` are confirmed by a Check on the device; one whose Check errs fails the poll (ACL_ERR_DEPTH; the
+ *    baseline stays) unless ACL_FLAG_LENIENT_LOOKUP, which leaves it out;
+ *  - refusals, atomic failure, lifetime, replicas: as above.  One poller per set.  Sets from acl_watch_set_open are untouched: `reserved` is 0 in all their
+ *    records. */
+int acl_watch_set_open_subjects(acl_engine_t *h, int rtype, int permission, int stype, int srel /* -1 none */, acl_watch_set_t **out);
+#define ACL_WATCH_CHANGE_WILDCARD 1u   /* acl_watch_change_t.reserved, subject-direction sets only: the record reports the wildcard, not a concrete subject */
 int acl_watch_set_add(acl_engine_t *h, acl_watch_set_t *s, const char *subject_id, uint32_t flags, uint32_t *watcher_out);
 int acl_watch_set_remove(acl_engine_t *h, acl_watch_set_t *s, uint32_t watcher);
 int acl_watch_set_poll(acl_engine_t *h, acl_watch_set_t *s, const acl_call_opts_t *opts,
@@ -459,6 +477,10 @@ int acl_watch_set_close(acl_engine_t *h, acl_watch_set_t *s);
 /* test hook (GPU): runs the diff kernels alone on caller rows (host arrays [n_rows][words], packed); old rows may be narrower than new ones */
 int acl_selfcheck_rows_diff(acl_engine_t *h, const uint32_t *old_rows, size_t old_words, const uint32_t *new_rows, size_t new_words,
                             size_t n_rows, acl_watch_change_t **changes_out, size_t *n_out);
+/* test hook (GPU): the rows a subject-direction set would hold for these resources (n rows of `words` words, host memory), computed by the set's device
+ * path -- walk, confirmation on the device, wildcard bits -- with no set state */
+int acl_selfcheck_subject_rows(acl_engine_t *h, int rtype, int permission, int stype, int srel, const uint32_t *resource_ids, size_t n,
+                               uint32_t *bitmaps_out, size_t words);
 /* Micro-batching front-end for the proxy's call shape -- many concurrent 1-item checks (check.go:76-94 one goroutine
  * per check expression, watch.go:50 one per update).  acl_check_one blocks its caller; while a batcher runs,
  * concurrent callers share ONE device pass (drained after at most max_wait_us or when max_items are waiting). */
@@ -655,6 +677,8 @@ typedef struct {
     uint64_t keep_route_calls;     /* acl_check_bulk_keep_v / _packed calls answered by ONE reverse walk and bit tests (since open) */
     uint64_t depth_sweeps;         /* forward sweeps over a whole type that established "no Check of this permission ends at the depth limit" for the snapshot (since open) */
     uint64_t hop2_rows;            /* two-hop rows of nested groups in the current snapshot (0: none qualify, or a nesting write dropped them until the next build) */
+    double subj_local_ms;          /* HIP-event time of the single-launch LookupSubjects kernel (k_subj_local) */
+    double refine_ms;              /* HIP-event time of a subject-direction watch set's confirmation kernels other than the Check itself (candidate records, items, apply) */
 } acl_stats_t;
 int acl_stats(acl_engine_t *h, acl_stats_t *out);
 int acl_stats_reset(acl_engine_t *h);

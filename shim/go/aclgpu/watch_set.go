@@ -43,6 +43,7 @@ type WatchChange struct {
 	Watcher  uint32
 	ObjectID string
 	Allowed  bool // true: gained, false: lost -- resultChange.allowed of watch.go:21-24
+	Wildcard bool // subject-direction sets: the record reports `subjectType:*` (ACL_WATCH_CHANGE_WILDCARD), not a concrete subject; ObjectID is "*"
 }
 
 // OpenWatchSet opens a set for subjects subjectType[#subjectRelation] against resourceType#permission.  Needs Config.WatchSets.
@@ -63,6 +64,33 @@ func (e *Engine) OpenWatchSet(resourceType, permission, subjectType, subjectRela
 	}
 	w := &WatchSet{e: e, typeID: rt, sinks: map[uint32]WatchSink{}, wake: make(chan struct{}, 1)}
 	if rc := C.acl_watch_set_open(e.h, rt, pm, st, sr, &w.s); rc != 0 {
+		return nil, lastError(rc)
+	}
+	return w, nil
+}
+
+// OpenSubjectWatchSet opens a SUBJECT-direction set (acl_watch_set_open_subjects): the audit question.  Its watchers are resources of resourceType --
+// Watch takes a resource id -- and its changes name the subjects of subjectType[#subjectRelation] that gained or lost permission on them: a
+// WatchChange's ObjectID is a subject id, Wildcard marks the record of `subjectType:*`.  On a permission without `&` / `-` / `.all()` that a wildcard
+// grants, the subjects behind the wildcard are not reported one by one.  Everything else -- one Run loop, Watch, Stats, Close -- is WatchSet's.
+// Needs Config.WatchSets, as OpenWatchSet does: the reference has no counterpart.
+func (e *Engine) OpenSubjectWatchSet(resourceType, permission, subjectType, subjectRelation string) (*WatchSet, error) {
+	if !e.watchSets {
+		return nil, status.Error(codes.FailedPrecondition, "watch sets are switched off (Config.WatchSets): they report changes the reference's watch does not")
+	}
+	var cs cstrings
+	defer cs.free()
+	rt := C.acl_type_id(e.h, cs.add(resourceType))
+	st := C.acl_type_id(e.h, cs.add(subjectType))
+	pm := C.acl_relation_id(e.h, rt, cs.add(permission))
+	sr := C.int(-1)
+	if subjectRelation != "" && subjectRelation != "..." {
+		if sr = C.acl_relation_id(e.h, st, cs.add(subjectRelation)); sr < 0 {
+			sr = -2
+		}
+	}
+	w := &WatchSet{e: e, typeID: st, sinks: map[uint32]WatchSink{}, wake: make(chan struct{}, 1)} // (the records' ids are of the subject type)
+	if rc := C.acl_watch_set_open_subjects(e.h, rt, pm, st, sr, &w.s); rc != 0 {
 		return nil, lastError(rc)
 	}
 	return w, nil
@@ -125,7 +153,7 @@ func (w *WatchSet) poll(ctx context.Context) ([]WatchChange, uint64, C.int, erro
 		if ln < 0 {
 			continue // an anonymous (bulk-loaded) id: nothing the proxy could name
 		}
-		out = append(out, WatchChange{Watcher: uint32(r.watcher), ObjectID: C.GoStringN(&buf[0], C.int(ln)), Allowed: r.gained != 0})
+		out = append(out, WatchChange{Watcher: uint32(r.watcher), ObjectID: C.GoStringN(&buf[0], C.int(ln)), Allowed: r.gained != 0, Wildcard: r.reserved&C.ACL_WATCH_CHANGE_WILDCARD != 0})
 	}
 	return out, uint64(rev), 0, nil
 }

@@ -31,7 +31,7 @@ SYMBOLS = [
     "acl_check_bulk_v_opts", "acl_object_name_copy", "acl_resolve_bulk_v", "acl_check_bulk_packed", "acl_check_bulk_keep_v", "acl_check_bulk_keep_packed", "acl_selfcheck_json_array", "acl_bitmap_names",
     "acl_lookup_subjects_batch", "acl_lookup_subjects", "acl_shard_subjects_bulk", "acl_shard_subjects_bulk_rccl",
     "acl_watch_set_open", "acl_watch_set_add", "acl_watch_set_remove", "acl_watch_set_poll", "acl_watch_set_row", "acl_watch_set_stats", "acl_watch_set_close",
-    "acl_selfcheck_rows_diff",
+    "acl_watch_set_open_subjects", "acl_selfcheck_rows_diff", "acl_selfcheck_subject_rows",
     "acl_explain_bulk_ids", "acl_explain", "acl_selfcheck_explain_ops",
 ]
 
@@ -104,7 +104,8 @@ class Stats(C.Structure):
                 ("frontier_entries", C.c_uint64), ("kernel_ms", C.c_double), ("expand_ms", C.c_double), ("snapshot_edges", C.c_uint64),
                 ("snapshot_bytes", C.c_uint64), ("snapshot_builds", C.c_uint64), ("overflow_retries", C.c_uint64), ("snapshot_edges_local", C.c_uint64), ("snapshot_patches", C.c_uint64),
                 ("local_ms", C.c_double), ("local_passes", C.c_uint64), ("snapshot_compactions", C.c_uint64),
-                ("rev_local_ms", C.c_double), ("rev_local_passes", C.c_uint64), ("lookup_requests", C.c_uint64), ("ids_recycled", C.c_uint64), ("keep_route_calls", C.c_uint64), ("depth_sweeps", C.c_uint64), ("hop2_rows", C.c_uint64)]
+                ("rev_local_ms", C.c_double), ("rev_local_passes", C.c_uint64), ("lookup_requests", C.c_uint64), ("ids_recycled", C.c_uint64), ("keep_route_calls", C.c_uint64), ("depth_sweeps", C.c_uint64), ("hop2_rows", C.c_uint64),
+                ("subj_local_ms", C.c_double), ("refine_ms", C.c_double)]
 
 
 ALL_GATHER_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
@@ -243,6 +244,7 @@ def load():
     L.acl_explain.argtypes = [H, C.POINTER(CheckItem), C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_void_p), C.POINTER(CallOpts)]
     L.acl_selfcheck_explain_ops.argtypes = [H, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.acl_watch_set_open.argtypes = [H, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    L.acl_watch_set_open_subjects.argtypes = [H, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     L.acl_watch_set_add.argtypes = [H, C.c_void_p, C.c_char_p, C.c_uint32, C.POINTER(C.c_uint32)]
     L.acl_watch_set_remove.argtypes = [H, C.c_void_p, C.c_uint32]
     L.acl_watch_set_poll.argtypes = [H, C.c_void_p, C.POINTER(CallOpts), C.POINTER(C.POINTER(WatchChange)), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]
@@ -250,6 +252,7 @@ def load():
     L.acl_watch_set_stats.argtypes = [H, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.acl_watch_set_close.argtypes = [H, C.c_void_p]
     L.acl_selfcheck_rows_diff.argtypes = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.POINTER(WatchChange)), C.POINTER(C.c_size_t)]
+    L.acl_selfcheck_subject_rows.argtypes = [H, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
     L.acl_check_one_opts.argtypes = [H, C.POINTER(CheckItem), C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(CallOpts)]
     L.acl_check_one_submit.argtypes = [H, C.POINTER(CheckItem), C.c_uint64]
     L.acl_check_completions.argtypes = [H, C.POINTER(Completion), C.c_size_t, C.c_int64, C.POINTER(C.c_size_t)]

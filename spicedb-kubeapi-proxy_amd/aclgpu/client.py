@@ -339,6 +339,8 @@ def run_watch_set(engine: Engine, watch_set, sinks: Optional[dict] = None, polls
     A poll consumes the changes of EVERY watcher of the set (it moves all baselines), so a set has one loop: every record is handed on, none is
     filtered away, and a second run_watch_set on a set whose loop is still open raises FAILED_PRECONDITION.  `sinks` may be changed by the caller
     while the loop runs (a watch opens: WatchSet.add, then its sink; a watch closes: its sink goes, then WatchSet.remove).
+    A subject-direction set (Engine.subject_watch_set) runs here unchanged: its watchers are resources, object_id is a SUBJECT's name (`*` for the
+    record of the wildcard).
     polls: stop after that many polls (None: for ever); timeout_s: how long one wait may block before it polls anyway (expirations arrive
     without a write)."""
     if getattr(watch_set, "_poller", False):

@@ -27,6 +27,7 @@ ITEM_DTYPE = np.dtype([("resource_type", "<u2"), ("permission", "<u2"), ("resour
                        ("subject_relation", "<u2"), ("subject_id", "<u4")])
 assert ITEM_DTYPE.itemsize == 16
 WATCHER_FROM_NOW = 1  # ACL_WATCHER_FROM_NOW
+WATCH_CHANGE_WILDCARD = 1  # ACL_WATCH_CHANGE_WILDCARD (a record's `reserved`, subject-direction sets)
 WATCH_CHANGE_DTYPE = np.dtype([("watcher", "<u4"), ("resource_id", "<u4"), ("gained", "<u4"), ("reserved", "<u4")])  # acl_watch_change_t
 assert WATCH_CHANGE_DTYPE.itemsize == C.sizeof(WatchChange) == 16
 HOP_DTYPE = np.dtype([("rtype", "<u2"), ("relation", "<u2"), ("rid", "<u4"), ("stype", "<u2"), ("srel", "<u2"), ("sid", "<u4"), ("flags", "<u4")])  # acl_explain_hop_t
@@ -559,6 +560,25 @@ class Engine:
         self._check(self._L.acl_watch_set_open(self._h, self.type_id(rt), self.relation_id(rt, perm), self.type_id(st), sr, C.byref(out)))
         return WatchSet(self, out, rt)
 
+    def subject_watch_set(self, rt, perm, st, srel="") -> "WatchSet":
+        """Opens a SUBJECT-direction watch set: the watchers are resources of `rt` (WatchSet.add takes a resource id), the records' `resource_id` carries a
+        subject id of `st`, and a record whose `reserved` is WATCH_CHANGE_WILDCARD reports the wildcard `st:*` instead of a concrete subject."""
+        sr = self.relation_id(st, srel)
+        if srel and sr < 0:
+            sr = -2
+        out = C.c_void_p()
+        self._check(self._L.acl_watch_set_open_subjects(self._h, self.type_id(rt), self.relation_id(rt, perm), self.type_id(st), sr, C.byref(out)))
+        return WatchSet(self, out, st)  # (the ids of its rows and records are of the subject type)
+
+    def selfcheck_subject_rows(self, rt, perm, st, srel, resource_ids) -> np.ndarray:
+        """Test hook: the rows a subject-direction set would hold for these resource ids, by the set's device path -> [n, words] uint32."""
+        rids = np.ascontiguousarray(resource_ids, dtype=np.uint32)
+        words = max(1, (self.object_count(st) + 31) // 32)
+        out = np.zeros((rids.size, words), dtype=np.uint32)
+        self._check(self._L.acl_selfcheck_subject_rows(self._h, self.type_id(rt), self.relation_id(rt, perm), self.type_id(st), self.relation_id(st, srel) if srel else -1,
+                                                       rids.ctypes.data, rids.size, out.ctypes.data, words))
+        return out
+
     def _changes(self, recs, n):
         try:
             if not n:
@@ -813,7 +833,8 @@ class Engine:
 
 
 class WatchSet:
-    """One acl_watch_set_t: the LookupResources rows of many watchers of one (type, permission), kept on the device between polls."""
+    """One acl_watch_set_t: the LookupResources rows of many watchers of one (type, permission), kept on the device between polls -- or, opened by
+    Engine.subject_watch_set, the LookupSubjects rows of many watched resources.  `rtype` is the type of the ids in the rows and records."""
 
     def __init__(self, engine: Engine, handle, rtype: str):
         self._e, self._s, self._rt = engine, handle, rtype

@@ -267,7 +267,7 @@ struct PassCtx {
     bool timing = false;
     std::vector<hipEvent_t> ev;  // pairs
     size_t ev_used = 0;
-    std::vector<int> ev_kind;  // per pair: 0 other, 1 expand
+    std::vector<int> ev_kind;  // per pair: 0 other, 1 expand, 2 k_check_local, 3 k_rev_local, 4 k_subj_local, 5 a subject-direction watch set's confirmation
 
     ~PassCtx();
 };
@@ -516,6 +516,15 @@ int ensure_subjects(acl_engine *h);     // engine_subjects.cpp; the snapshot is 
 bool subjects_current(acl_engine *h);   // caller holds state_mu at least shared
 constexpr uint32_t kFreshSubject = 0xFFFFFFFCu;  // LookupSubjects: an id of the subject type that no relationship names (intern_check_item's unknown subject) -- the wildcard's stand-in
 int subjects_error(int32_t code, uint32_t rid, uint32_t sid);  // fails a LookupSubjects call with a reached subject's Check error (engine_subjects.cpp)
+// subject-direction watch sets: the LookupSubjects walk of n resources with the rows left on the device (engine_subjects.cpp subjects_walk): row i at
+// rows + i * stride (stride >= the words of the subject type's ids; the words behind them zeroed), flags[i] != 0 and wild[i] (host) where a `T:*` row was
+// reached.  The rows are the walk's own: CANDIDATES on a permission with `&` / `-` / `.all()`.  Caller holds an Eval with the subject rows current.
+struct SubjDevDst {
+    uint32_t *rows;
+    size_t stride;
+    uint32_t *flags;
+};
+int subjects_walk_device(acl_engine *h, PassCtx *c, int rt, int pm, int st, int srel, const uint32_t *rids, size_t n, const SubjDevDst &dst, uint8_t *wild);
 // true when the device snapshot answers for the store as it is now (caller holds state_mu at least shared)
 bool snapshot_current(acl_engine *h, bool need_reverse);
 void compaction_join(acl_engine *h);  // acl_close / schema reload: waits for a build in flight and drops its result

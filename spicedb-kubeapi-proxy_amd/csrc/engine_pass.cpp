@@ -87,6 +87,8 @@ void ev_collect(PassCtx *c) {  // stream must be synchronized
             if (c->ev_kind[i / 2] == 1) c->stats.expand_ms += ms;
             else if (c->ev_kind[i / 2] == 2) c->stats.local_ms += ms;
             else if (c->ev_kind[i / 2] == 3) c->stats.rev_local_ms += ms;
+            else if (c->ev_kind[i / 2] == 4) c->stats.subj_local_ms += ms;
+            else if (c->ev_kind[i / 2] == 5) c->stats.refine_ms += ms;
         }
     }
     c->ev_used = 0;
@@ -106,6 +108,8 @@ void merge_stats(acl_engine *h, PassCtx *c) {
     a.local_passes += b.local_passes;
     a.rev_local_ms += b.rev_local_ms;
     a.rev_local_passes += b.rev_local_passes;
+    a.subj_local_ms += b.subj_local_ms;
+    a.refine_ms += b.refine_ms;
     a.lookup_requests += b.lookup_requests;
     a.overflow_retries += b.overflow_retries;
     b = acl_stats_t{};

@@ -26,9 +26,11 @@ int subjects_error(int32_t code, uint32_t rid, uint32_t sid) {
 
 namespace {
 
-// one launch per group of resources: rows of `row_words` words into bitmaps (stride `words`), wildcard reached into wild[]
+// one launch per group of resources: rows of `row_words` words into bitmaps (stride `words`), wildcard reached into wild[].  With `dev` (subject-direction
+// watch sets) the rows stay on the device instead: a chunk whose status is good is copied from d_subj_rows to dev->rows + (b + i) * dev->stride, the words
+// behind row_words zeroed, and its flag words to dev->flags + b -- a chunk that is walked again with a larger log has written nothing there yet
 int subjects_walk(acl_engine *h, PassCtx *c, uint32_t target, uint32_t key, const uint32_t *rids, size_t n, uint32_t *bitmaps, size_t words, size_t row_words,
-                  uint8_t *wild) {
+                  uint8_t *wild, const SubjDevDst *dev = nullptr) {
     const DevSubjects g = dev_subjects(h, c);
     const BlockWalk w{"LookupSubjects", "resource", 2 /* (8-byte log entries) */, row_words, kSubjCapFirst, kSubjCapMax};
     uint32_t *h_rows = nullptr, *h_flags = nullptr;
@@ -39,25 +41,35 @@ int subjects_walk(acl_engine *h, PassCtx *c, uint32_t target, uint32_t key, cons
             HIP_TRY(c->d_subj_rows.ensure(std::max<size_t>(m * row_words, 1)));
             HIP_TRY(c->d_subj_flags.ensure(m));
             HIP_TRY(c->h_in.ensure(m * sizeof(uint32_t)));
-            HIP_TRY(c->h_out.ensure(std::max<size_t>(m * row_words, 1) * 4 + m * 4));
+            HIP_TRY(c->h_out.ensure(std::max<size_t>(dev ? 0 : m * row_words, 1) * 4 + m * 4));
             std::memcpy(c->h_in.p, rids + b, m * sizeof(uint32_t));
             HIP_TRY(hipMemcpyAsync(c->d_sids.p, c->h_in.p, m * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
             if (row_words) HIP_TRY(hipMemsetAsync(c->d_subj_rows.p, 0, m * row_words * 4, c->stream));
             return (int)ACL_OK;
         },
         [&](size_t m, uint32_t cap) {
-            ev_begin(c, 0);
+            ev_begin(c, 4);
             launch_subj_local(c->stream, g, c->d_sids.p, (uint32_t)m, target, key, c->d_fbuf[0].p, cap, c->d_subj_visited.p, c->d_subj_rows.p, (uint32_t)row_words,
                               c->d_subj_flags.p, c->d_status.p);
             ev_end(c);
             HIP_TRY(hipGetLastError());
             h_rows = (uint32_t *)c->h_out.p;
-            h_flags = h_rows + m * row_words;
-            if (row_words) HIP_TRY(hipMemcpyAsync(h_rows, c->d_subj_rows.p, m * row_words * 4, hipMemcpyDeviceToHost, c->stream));
+            h_flags = h_rows + (dev ? 0 : m * row_words);
+            if (row_words && !dev) HIP_TRY(hipMemcpyAsync(h_rows, c->d_subj_rows.p, m * row_words * 4, hipMemcpyDeviceToHost, c->stream));
             HIP_TRY(hipMemcpyAsync(h_flags, c->d_subj_flags.p, m * 4, hipMemcpyDeviceToHost, c->stream));
             return (int)ACL_OK;
         },
         [&](size_t b, size_t m) {
+            if (dev) {
+                // (one strided copy kernel: a 2-D runtime copy of narrow rows costs a launch per row)
+                ev_begin(c, 4);
+                launch_subj_rows_store(c->stream, c->d_subj_rows.p, (uint32_t)row_words, c->d_subj_flags.p, (uint32_t)m, dev->rows + b * dev->stride, (uint32_t)dev->stride,
+                                       dev->flags + b);
+                ev_end(c);
+                HIP_TRY(hipGetLastError());
+                for (size_t i = 0; i < m; i++) wild[b + i] = h_flags[i] ? 1 : 0;
+                return (int)ACL_OK;
+            }
             for (size_t i = 0; i < m; i++) {
                 uint32_t *dst = bitmaps + (b + i) * words;
                 if (row_words) std::memcpy(dst, h_rows + i * row_words, row_words * 4);
@@ -211,6 +223,21 @@ int subjects_batch_call(acl_engine_t *h, int rt, int pm, int st, int srel, const
 }
 
 }  // namespace
+
+int subjects_walk_device(acl_engine *h, PassCtx *c, int rt, int pm, int st, int srel, const uint32_t *rids, size_t n, const SubjDevDst &dst, uint8_t *wild) {
+    int rc = not_sharded(h);
+    if (rc) return rc;
+    const Schema &sc = h->store.schema();
+    const uint32_t nres = h->store.objects(rt).count();
+    for (size_t i = 0; i < n; i++)
+        if (rids[i] >= nres) return fail(ACL_ERR_INVALID_ARGUMENT, "lookup_subjects: resource id " + std::to_string(rids[i]) + " beyond the type's objects");
+    const size_t need = ((size_t)h->store.objects(st).count() + 31) / 32;
+    if (dst.stride < need) return fail(ACL_ERR_INTERNAL, "subject rows: the destination's rows are narrower than the type's ids");
+    rc = subjects_walk(h, c, (uint32_t)sc.slot(rt, pm), sc.subject_key(st, srel < 0 ? kNoRelation : srel), rids, n, nullptr, 0, need, wild, &dst);
+    if (rc) return rc;
+    c->stats.lookup_requests += n;
+    return ACL_OK;
+}
 
 bool subjects_current(acl_engine *h) {
     const SubjectRows &s = h->subj;

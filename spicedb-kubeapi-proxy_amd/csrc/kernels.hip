@@ -3666,4 +3666,102 @@ void launch_rows_diff_emit(hipStream_t st, const DevRowsDiff &d, const uint64_t 
     });
 }
 
+// ---- subject-direction watch sets: the candidates of a non-monotone permission confirmed where the rows are (kernels.hpp DevRefine) ----
+// The candidate records are the diff's own (rows against an empty old array: one {row, bit, 1, 0} per set bit, ordered by (row, bit)); the stand-ins
+// of the flagged rows follow them.  Item k answers record k, so k_refine_apply needs no search: lanes of a wave hold consecutive records, the ones
+// that share a row word are neighbours and fold their bits before the one atomic (subj_mark's fold, with AND NOT in the place of OR).
+
+// the rows in `wrows`: bits [0, nobj) set, the wildcard's own bit (wid < nobj) cleared; one word per thread
+__global__ __launch_bounds__(256) void k_refine_fill(DevRefine r, uint32_t nflag, uint32_t need, uint32_t nobj, uint32_t wid) {
+    const uint64_t total = (uint64_t)nflag * need;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < total; i += (uint64_t)gridDim.x * 256u) {
+        const uint32_t f = (uint32_t)(i / need), w = (uint32_t)(i - (uint64_t)f * need);
+        uint32_t v = w * 32u + 32u <= nobj ? 0xFFFFFFFFu : (1u << (nobj & 31u)) - 1u;  // (need = ceil(nobj / 32): only the last word is partial)
+        if (wid < nobj && (wid >> 5) == w) v &= ~(1u << (wid & 31u));
+        r.rows[(size_t)r.wrows[f] * r.row_words + w] = v;
+    }
+}
+
+// rows whose flag word is raised: the wildcard's bit set (every row has one thread: a plain read-modify-write)
+__global__ __launch_bounds__(256) void k_refine_wild(uint32_t *rows, uint32_t row_words, const uint32_t *__restrict__ flags, uint32_t n_rows, uint32_t wid) {
+    const uint32_t row = blockIdx.x * 256u + threadIdx.x;
+    if (row < n_rows && flags[row]) rows[(size_t)row * row_words + (wid >> 5)] |= 1u << (wid & 31u);
+}
+
+__global__ __launch_bounds__(256) void k_refine_items(DevRefine r, uint4 *__restrict__ items) {
+    const uint32_t n = r.nrec + r.nstand;
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
+        uint32_t row, sid;
+        if (i < r.nrec) {
+            const uint4 rec = r.recs[i];  // {row of the slice, bit, 1, 0}
+            row = r.row0 + rec.x;
+            sid = rec.y;
+        } else {
+            row = r.wrows[r.wrow0 + (i - r.nrec)];
+            sid = r.fresh_sid;
+        }
+        items[i] = make_uint4(r.head, r.rids[row], r.tail, sid);  // acl_item_t: {type | permission << 16, resource, subject type | relation << 16, subject}
+    }
+}
+
+__global__ __launch_bounds__(256) void k_refine_apply(DevRefine r, const uint8_t *__restrict__ perm, const int32_t *__restrict__ err, uint32_t has_value, uint32_t *status) {
+    const uint32_t lane = lane_id(), n = r.nrec + r.nstand;
+    for (uint32_t base = (blockIdx.x * 4u + uniform(threadIdx.x >> 6)) * 64u; base < n; base += gridDim.x * 256u) {  // (wave-uniform trips: the fold shuffles)
+        const uint32_t i = base + lane;
+        const bool in = i < n, is_rec = i < r.nrec;
+        const bool bad = in && err[i] != 0;
+        const bool holds = in && !bad && perm[i] == has_value;
+        uint32_t w = 0xFFFFFFFFu, b = 0u;
+        if (is_rec) {
+            const uint4 rec = r.recs[i];
+            w = (r.row0 + rec.x) * r.row_words + (rec.y >> 5);  // (a set's rows are below 2^28 words)
+            b = holds ? 0u : 1u << (rec.y & 31u);
+        } else if (in) {
+            r.flags[r.wrows[r.wrow0 + (i - r.nrec)]] = holds ? 1u : 0u;  // the stand-in decides the row's wildcard
+        }
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t ow = (uint32_t)__shfl_down((int)w, d), ob = (uint32_t)__shfl_down((int)b, d);
+            if (lane + (uint32_t)d < 64u && ow == w) b |= ob;
+        }
+        const uint32_t pw = (uint32_t)__shfl_up((int)w, 1);
+        if (is_rec && b && (lane == 0u || pw != w)) __hip_atomic_fetch_and(r.rows + w, ~b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned long long errs = __ballot(bad);
+        if (errs && lane == (uint32_t)__ffsll((long long)errs) - 1u) __hip_atomic_fetch_min(status, i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // the wave's first erring item
+    }
+}
+
+// dst[row][0 .. dst_words) = src[row][0 .. src_words) followed by zeros, dst_flags[row] = src_flags[row]: the walk's packed rows into a set's row array
+__global__ __launch_bounds__(256) void k_subj_rows_store(const uint32_t *__restrict__ src, uint32_t src_words, const uint32_t *__restrict__ src_flags, uint32_t m, uint32_t *__restrict__ dst,
+                                                         uint32_t dst_words, uint32_t *__restrict__ dst_flags) {
+    const uint64_t total = (uint64_t)m * dst_words;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < total; i += (uint64_t)gridDim.x * 256u) {
+        const uint32_t row = (uint32_t)(i / dst_words), w = (uint32_t)(i - (uint64_t)row * dst_words);
+        dst[i] = w < src_words ? src[(size_t)row * src_words + w] : 0u;
+        if (w == 0u) dst_flags[row] = src_flags[row];
+    }
+}
+
+static uint32_t refine_blocks(uint64_t threads) { return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((threads + 255) / 256, 4096)); }
+void launch_subj_rows_store(hipStream_t st, const uint32_t *src, uint32_t src_words, const uint32_t *src_flags, uint32_t m, uint32_t *dst, uint32_t dst_words, uint32_t *dst_flags) {
+    if (!m || !dst_words) return;
+    hipLaunchKernelGGL(k_subj_rows_store, dim3(refine_blocks((uint64_t)m * dst_words)), dim3(256), 0, st, src, src_words, src_flags, m, dst, dst_words, dst_flags);
+}
+void launch_refine_fill(hipStream_t st, const DevRefine &r, uint32_t nflag, uint32_t need, uint32_t nobj, uint32_t wid) {
+    if (!nflag || !need) return;
+    hipLaunchKernelGGL(k_refine_fill, dim3(refine_blocks((uint64_t)nflag * need)), dim3(256), 0, st, r, nflag, need, nobj, wid);
+}
+void launch_refine_wild(hipStream_t st, uint32_t *rows, uint32_t row_words, const uint32_t *flags, uint32_t n_rows, uint32_t wid) {
+    if (!n_rows || (wid >> 5) >= row_words) return;
+    hipLaunchKernelGGL(k_refine_wild, dim3((n_rows + 255) / 256), dim3(256), 0, st, rows, row_words, flags, n_rows, wid);
+}
+void launch_refine_items(hipStream_t st, const DevRefine &r, uint4 *items) {
+    if (!(r.nrec + r.nstand)) return;
+    hipLaunchKernelGGL(k_refine_items, dim3(refine_blocks(r.nrec + r.nstand)), dim3(256), 0, st, r, items);
+}
+void launch_refine_apply(hipStream_t st, const DevRefine &r, const uint8_t *perm, const int32_t *err, uint32_t has_value, uint32_t *status) {
+    if (!(r.nrec + r.nstand)) return;
+    hipLaunchKernelGGL(k_refine_apply, dim3(refine_blocks(r.nrec + r.nstand)), dim3(256), 0, st, r, perm, err, has_value, status);
+}
+
 }  // namespace acl

@@ -243,6 +243,32 @@ struct DevRowsDiff {
 inline uint32_t rows_diff_tiles(const DevRowsDiff &d) { return (std::max(d.old_words, d.new_words) + kDiffTileWords - 1) / kDiffTileWords; }  // per row
 void launch_rows_diff_count(hipStream_t s, const DevRowsDiff &d, uint32_t *tile_counts, uint64_t *offs);  // count + scan
 void launch_rows_diff_emit(hipStream_t s, const DevRowsDiff &d, const uint64_t *offs, uint4 *out, uint64_t out_cap);
+// Subject-direction watch sets (engine_watchset.cpp subject_rows): the candidates of a permission with `&` / `-` / `.all()` confirmed on the device.  One slice of
+// whole rows [row0, row0 + rows of the slice) of a packed row array at a time:
+//   fill  : rows wrows[0 .. nflag) (the walk reached `T:*` there) become "every id of the type": bits [0, nobj) set, the wildcard's own bit cleared
+//   items : record k of the slice's diff against an empty old array ({row of the slice, bit, 1, 0}: k_rows_diff_emit without row ids) -> the 16-byte item
+//           {head, rids[row0 + row], tail, bit}; behind the nrec records one stand-in per flagged row of the slice, wrows[wrow0 .. wrow0 + nstand), whose
+//           subject is fresh_sid (an id nobody names: the wildcard as a Check sees it)
+//   apply : answer k of a Check over those items: not `has_value`, or an error -> the record's bit is cleared (lanes that share a word fold first, one
+//           agent-scope atomic AND per word and wave); a stand-in's answer becomes its row's flag word; the least index of an erring item is left in
+//           *status by atomic minimum (the caller stores 0xFFFFFFFF first)
+//   wild  : rows whose flag word is set get the wildcard's bit
+struct DevRefine {
+    uint32_t *rows;          // [n_rows][row_words]
+    uint32_t *flags;         // [n_rows]
+    const uint32_t *rids;    // [n_rows] the rows' resources
+    const uint32_t *wrows;   // ascending indices of the rows the walk flagged
+    const uint4 *recs;       // the slice's candidate records
+    uint32_t row_words, row0, nrec, wrow0, nstand;
+    uint32_t head, tail;     // an item's first and third word: resource type | permission << 16, subject type | subject relation << 16
+    uint32_t fresh_sid;
+};
+// the walk's packed rows (k_subj_local: [m][src_words]) into rows of dst_words >= src_words words, the words behind src_words zeroed, and their flag words
+void launch_subj_rows_store(hipStream_t s, const uint32_t *src, uint32_t src_words, const uint32_t *src_flags, uint32_t m, uint32_t *dst, uint32_t dst_words, uint32_t *dst_flags);
+void launch_refine_fill(hipStream_t s, const DevRefine &r, uint32_t nflag, uint32_t need /* words that hold the type's ids */, uint32_t nobj, uint32_t wid);
+void launch_refine_items(hipStream_t s, const DevRefine &r, uint4 *items);
+void launch_refine_apply(hipStream_t s, const DevRefine &r, const uint8_t *perm, const int32_t *err, uint32_t has_value, uint32_t *status);
+void launch_refine_wild(hipStream_t s, uint32_t *rows, uint32_t row_words, const uint32_t *flags, uint32_t n_rows, uint32_t wid);
 // blocks per expand launch for this device (all co-resident); nwaves = blocks * kWavesPerBlock
 int expand_grid_blocks(int device);
 

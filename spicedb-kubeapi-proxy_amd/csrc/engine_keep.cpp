@@ -32,7 +32,8 @@ constexpr size_t kMultiMinTemplates = 2, kMultiMaxTemplates = 4, kMultiMinItems 
 // -- only a tag hit goes on to the type's name table for the id and the bit, and a name the user may not see never pays the table's miss.  With MANY allowed
 // every name is resolved in the table -- by the host's pass over the pairs, while the device still walks.  Every deviation -- fields that differ, a userset subject, an item the API's validation
 // would refuse, a non-monotone permission, a sharded or store-only engine -- returns kRouteNotTaken BEFORE anything is written, and the caller takes the
-// forward path: keep mask and error behaviour are the forward path's by construction (an unknown or unreachable resource is NO_PERMISSION there, a depth
+// forward path -- as does a subject no table knows while the store holds a `T:*` relationship of its type (without one it is answered "nothing is allowed"
+// with no walk at all; with one, the wildcard's rows grant it what they grant everybody): keep mask and error behaviour are the forward path's by construction (an unknown or unreachable resource is NO_PERMISSION there, a depth
 // error is a pair error there: both drop the item, postfilter.go:162-172, as the missing bit does here).
 // "No Check of (rt, pm) for a subject of type st ends at the dispatch-depth limit on this snapshot" -- what lets the PAIR form below answer a RECURSIVE permission
 // (nested groups: the schema alone allows a chain of any length) from the reverse walk's row.  A Check that does not find its subject explores every path below
@@ -316,7 +317,7 @@ struct KeepCall {
         static thread_local std::vector<uint32_t> idv_buf;
         if (idv_buf.size() < n) idv_buf.resize(n);
         idv = idv_buf.data();
-        hint.look(h, rt, pm, st, sub);
+        if (sub_known) hint.look(h, rt, pm, st, sub);  // (a subject no table knows has no id to remember a reach under: no hint, nothing guessed)
         guess_few = hint.known && (hint.count == 0 || is_few(hint.count));
         // A SHORT list for a subject who reaches thousands of objects: the walk (60-90 us: it marks all of them) costs more than the forward path's pass over
         // the few pairs (1 024 pairs: 0.10 against 0.06 ms).  Not taken then -- except every sixteenth time, so that the hint follows a user whose reach shrinks.
@@ -326,19 +327,37 @@ struct KeepCall {
     // may the row answer this call, and what else it needs: the deep objects' bitmap (pair form), a zeroed row.  false: forward.  c: the evaluation's context
     bool prepare_row(PassCtx *c) {
         const uint32_t target = (uint32_t)h->store.schema().slot(rt, pm);
+        // a permission some `&` / `-` can change: forward, whoever asks (a subject no table knows too: what `a - b` gives it is the Check's to say)
+        if (h->snap.slot_nonmono.size() > target && h->snap.slot_nonmono[target]) return false;
+        // a subject no table knows is answered without a walk -- unless a `st:*` relationship covers it, as it covers every plain subject of the type: forward
+        if (!sub_known && store_holds_wildcard_of(st)) return false;
         // (the pair form also for a subject no table knows: a walk through a cycle of groups ends at the depth limit whoever is looked for)
         if (pair_form && (h->snap.slot_deep.size() <= target || (h->snap.slot_deep[target] && !no_object_is_deep(h, c, rt, pm, st, n, &deep)))) return false;
         dbits = deep ? deep->data() : nullptr;
         dwords = deep ? deep->size() : 0;
         if (sub_known) {
-            if (!h->snap.slot_nonmono.empty() && h->snap.slot_nonmono[target]) return false;
             const size_t words = ((size_t)h->store.objects(rt).count() + 31) / 32;
             row.assign(std::max<size_t>(words, 1), 0u);
         }
         return true;
     }
 
-    // the reverse walk (none for a subject no table knows: it has no relationships, and without a subject relation it is nobody's member)
+    // "Some relationship of the STORE names `st:*`" (caller holds state_mu shared).  The table's "*" object proves nothing: it is interned with the schema and
+    // stays when its last relationship goes.  An expired relationship not collected yet still counts: forward is always right.
+    bool store_holds_wildcard_of(int stype) const {
+        if (h->store.wildcard_id(stype) == 0xFFFFFFFFu) return false;  // (no relation of the schema allows `stype:*`)
+        const Schema &sc = h->store.schema();
+        const auto &tables = h->store.tables();
+        for (int slot = 0; slot < sc.nslots; slot++) {
+            const auto &cls = sc.defs[sc.slot_owner[slot].first].members[sc.slot_owner[slot].second].classes;
+            for (size_t k = 0; k < cls.size(); k++)
+                if (cls[k].wildcard && cls[k].stype == stype && (!tables[slot][k].keys.empty() || !tables[slot][k].pending.empty())) return true;
+        }
+        return false;
+    }
+
+    // the reverse walk.  None for a subject no table knows: it has no relationships, and without a subject relation it is nobody's member -- so nothing is
+    // allowed, PROVIDED no `st:*` relationship covers it: prepare_row has sent such a call forward (the wildcard's row grants whoever is of the type)
     void walk(PassCtx *c) {
         const auto t_w = KeepTrace::Clock::now();
         if (sub_known) walk_rc = lookup_batch(h, c, rt, pm, st, -1, &sub, 1, row.data(), row.size(), &count);

@@ -84,7 +84,8 @@ def test_postfilter_one_subject_reverse_route(aclgpu):
     and acl_check_bulk_keep_packed answer such a call by one reverse walk + bit tests.  Compared here, on named objects: both entry points (route taken: the stats
     say so), the forward path (acl_check_bulk_v + the AND of postfilter.go:144-178) and the oracle -- for a power user, an ordinary user, a user nobody knows; with
     unknown pod names in the list, ragged pair ranges, and the calls the route must NOT take (two subjects, a userset subject) or must fail exactly as the forward
-    path fails (an id the API refuses: the message names the field).  acl_check_bulk_packed answers as acl_check_bulk_v."""
+    path fails (an id the API refuses: the message names the field).  acl_check_bulk_packed answers as acl_check_bulk_v.  For `ghost-user` "all denied" holds because
+    C3's schema has no wildcard: under `user:*` a subject no table knows is granted what the wildcard grants (tests/test_keep_route_wildcards_gpu.py)."""
     from aclgpu import workloads
     w = workloads.c3(scale=0.05, batch=256, power_users=4)
     o = orc.Oracle(w.schema)

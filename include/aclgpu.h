@@ -337,6 +337,33 @@ int acl_explain_bulk_ids(acl_engine_t *h, const acl_item_t *items, size_t n, uin
 int acl_explain(acl_engine_t *h, const acl_check_item_t *item, uint8_t *perm_out, int32_t *err_out, uint32_t *flags_out, char **text_out,
                 const acl_call_opts_t *opts);
 
+/* ---- Explain with proofs: the same question for permissions with `-`, `&` or `.all()` beneath (Snapshot::slot_nonmono) ----
+ * perm_out / err_out are acl_check_bulk_ids' answers, as above.  A granted item on a monotone permission gets ACL_EXPLAIN_WITNESS and exactly the hops
+ * acl_explain_bulk_ids returns (no absences).  A granted item on any other permission gets ACL_EXPLAIN_PROOF: hops [hop_off_out[i], hop_off_out[i + 1])
+ * and absences [absent_off_out[i], absent_off_out[i + 1]); ACL_EXPLAIN_UNSUPPORTED is never returned here.
+ *   - hops are stored relationships, live at the call's revision and `now`, laid out as one or more chains in the sense above; the first hop of every
+ *     chain after the first carries ACL_HOP_SEGMENT.  The order is for readers: the proof reads the hops as a set;
+ *   - absences are ordinary Check items (object, relation or permission, the item's subject) that answer NO_PERMISSION without error on the same
+ *     snapshot: the "not banned" facts the grant rests on.  Why an absent goal is absent is not explained.  An absence reached through a tupleset
+ *     (`- parent->banned`, `.all()`) has that tupleset relationship among the hops;
+ *   - the item is derivable from the hops (positive steps) and the absences (every subtracted operand is refuted by them) within the 50 dispatches of
+ *     a Check (DESIGN.md 15 has the rules).  The hops alone, replayed into an empty store, need NOT grant such an item: an absent goal may be absent
+ *     because of a ban that the hops do not repeat.
+ * Items that are not granted get no flag, no hops and no absences.  A proof of more than ACL_PROOF_MAX_RECORDS hops plus absences for one item, or a
+ * search that outgrows its bound of goals, fails the call with ACL_ERR_RESOURCE_EXHAUSTED naming the item -- a proof is never truncated; a granted item
+ * for which no proof is found fails it with ACL_ERR_INTERNAL.  Refusals, err_out / flags_out and the call options are acl_explain_bulk_ids'.
+ * *hops_out and *absent_out are one allocation each (acl_free; NULL when the call fails or n == 0); both offset arrays hold n + 1 entries. */
+#define ACL_HOP_SEGMENT 2u        /* this hop starts a new chain: its resource is not the previous hop's subject object */
+#define ACL_EXPLAIN_PROOF 4u      /* per item: hops + absences prove it (a permission with -, & or .all() beneath) */
+#define ACL_PROOF_MAX_RECORDS 65536u /* hops plus absences of one item's proof, at most */
+int acl_explain_proof_bulk_ids(acl_engine_t *h, const acl_item_t *items, size_t n, uint8_t *perm_out, int32_t *err_out, uint8_t *flags_out,
+                               uint32_t *hop_off_out, acl_explain_hop_t **hops_out, uint32_t *absent_off_out, acl_item_t **absent_out,
+                               const acl_call_opts_t *opts);
+/* string form, one item, names handled as acl_explain handles them: the hops one per line in the tuple grammar (the text of acl_explain for a monotone
+ * item), then every absence as `not type:id#relation@type:id[#relation]`. */
+int acl_explain_proof(acl_engine_t *h, const acl_check_item_t *item, uint8_t *perm_out, int32_t *err_out, uint32_t *flags_out, char **text_out,
+                      const acl_call_opts_t *opts);
+
 /* ---- the callers either side of the kernels ----
  * PostFilter: filterItemsWithBulkPermissions (postfilter.go:58-182).  The K list items' resolved pairs are ONE bulk
  * check; pairs [item_off[i], item_off[i+1]) belong to list item i (itemToRequestMap, postfilter.go:65,117-119);

@@ -33,6 +33,7 @@ SYMBOLS = [
     "acl_watch_set_open", "acl_watch_set_add", "acl_watch_set_remove", "acl_watch_set_poll", "acl_watch_set_row", "acl_watch_set_stats", "acl_watch_set_close",
     "acl_watch_set_open_subjects", "acl_selfcheck_rows_diff", "acl_selfcheck_subject_rows",
     "acl_explain_bulk_ids", "acl_explain", "acl_selfcheck_explain_ops",
+    "acl_explain_proof_bulk_ids", "acl_explain_proof",
 ]
 
 
@@ -243,6 +244,9 @@ def load():
     L.acl_explain_bulk_ids.argtypes = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.POINTER(ExplainHop)), C.POINTER(CallOpts)]
     L.acl_explain.argtypes = [H, C.POINTER(CheckItem), C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_void_p), C.POINTER(CallOpts)]
     L.acl_selfcheck_explain_ops.argtypes = [H, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.acl_explain_proof_bulk_ids.argtypes = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.POINTER(ExplainHop)), C.c_void_p,
+                                             C.POINTER(C.c_void_p), C.POINTER(CallOpts)]
+    L.acl_explain_proof.argtypes = [H, C.POINTER(CheckItem), C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_void_p), C.POINTER(CallOpts)]
     L.acl_watch_set_open.argtypes = [H, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     L.acl_watch_set_open_subjects.argtypes = [H, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     L.acl_watch_set_add.argtypes = [H, C.c_void_p, C.c_char_p, C.c_uint32, C.POINTER(C.c_uint32)]

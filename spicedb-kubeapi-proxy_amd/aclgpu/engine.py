@@ -36,6 +36,9 @@ EXPLAIN_OP_DTYPE = np.dtype([("rtype", "<u2"), ("relation", "<u2"), ("stype", "<
 assert EXPLAIN_OP_DTYPE.itemsize == C.sizeof(ExplainOpRec) == 20
 HOP_WILDCARD = 1                                # ACL_HOP_WILDCARD
 EXPLAIN_WITNESS, EXPLAIN_UNSUPPORTED = 1, 2     # per-item flags of Explain
+HOP_SEGMENT = 2                                 # ACL_HOP_SEGMENT: the hop starts a new chain of a proof
+EXPLAIN_PROOF = 4                               # ACL_EXPLAIN_PROOF: hops + absences prove the item
+PROOF_MAX_RECORDS = 65536                       # ACL_PROOF_MAX_RECORDS
 
 
 class AclError(Exception):
@@ -774,6 +777,41 @@ class Engine:
         it = CheckItem(*[_b(x if x is not None else "") for x in (rt, rid, perm, st, sid, srel)])
         p, e, f, txt = C.c_uint8(), C.c_int32(), C.c_uint32(), C.c_void_p()
         self._check(self._L.acl_explain(self._h, C.byref(it), C.byref(p), C.byref(e), C.byref(f), C.byref(txt), None))
+        try:
+            lines = C.string_at(txt).decode().splitlines() if txt.value else []
+        finally:
+            self._L.acl_free(txt)
+        return p.value, e.value, f.value, lines
+
+    def explain_proof_ids(self, items: np.ndarray, cancel=None, timeout_s=None):
+        """acl_explain_proof_bulk_ids: Check + a proof per granted item, permissions with `-`, `&` and `.all()` included ->
+        (perm u8[n], err i32[n], flags u8[n], hop_off u32[n + 1], hops HOP_DTYPE[], absent_off u32[n + 1], absent ITEM_DTYPE[]); item i rests on the stored
+        relationships hops[hop_off[i]:hop_off[i + 1]] and on the Check items absent[absent_off[i]:absent_off[i + 1]], each of which answers NO."""
+        items = np.ascontiguousarray(items, dtype=ITEM_DTYPE)
+        n = items.size
+        perm = np.zeros(max(1, n), dtype=np.uint8)
+        err = np.zeros(max(1, n), dtype=np.int32)
+        flags = np.zeros(max(1, n), dtype=np.uint8)
+        off = np.zeros(n + 1, dtype=np.uint32)
+        aoff = np.zeros(n + 1, dtype=np.uint32)
+        hp, ap = C.POINTER(ExplainHop)(), C.c_void_p()
+        o = self._opts(cancel, timeout_s)
+        self._check(self._L.acl_explain_proof_bulk_ids(self._h, items.ctypes.data, n, perm.ctypes.data, err.ctypes.data, flags.ctypes.data, off.ctypes.data, C.byref(hp),
+                                                       aoff.ctypes.data, C.byref(ap), C.byref(o) if o else None))
+        try:
+            nh, na = int(off[n]), int(aoff[n])
+            hops = np.frombuffer(C.string_at(hp, nh * HOP_DTYPE.itemsize), dtype=HOP_DTYPE).copy() if nh else np.zeros(0, dtype=HOP_DTYPE)
+            absent = np.frombuffer(C.string_at(ap, na * ITEM_DTYPE.itemsize), dtype=ITEM_DTYPE).copy() if na else np.zeros(0, dtype=ITEM_DTYPE)
+        finally:
+            self._L.acl_free(hp)
+            self._L.acl_free(ap)
+        return perm[:n], err[:n], flags[:n], off, hops, aoff, absent
+
+    def explain_proof(self, rt, rid, perm, st, sid, srel=""):
+        """acl_explain_proof: (permissionship, error code, flags, [lines]): the hops in the tuple grammar of aclgpu/text.py, then `not <goal>` per absence."""
+        it = CheckItem(*[_b(x if x is not None else "") for x in (rt, rid, perm, st, sid, srel)])
+        p, e, f, txt = C.c_uint8(), C.c_int32(), C.c_uint32(), C.c_void_p()
+        self._check(self._L.acl_explain_proof(self._h, C.byref(it), C.byref(p), C.byref(e), C.byref(f), C.byref(txt), None))
         try:
             lines = C.string_at(txt).decode().splitlines() if txt.value else []
         finally:

@@ -15,12 +15,15 @@ namespace {
 constexpr uint32_t kExplainCapFirst = 1u << 14;  // log entries (16 B) per block of the first attempt
 constexpr uint32_t kExplainCapMax = 1u << 24;    // ... and at most: beyond, ACL_ERR_RESOURCE_EXHAUSTED
 
-std::string item_text(const acl_item_t &it, size_t i) {
+}  // namespace
+
+std::string explain_item_text(const acl_item_t &it, size_t i) {
     return "item " + std::to_string(i) + " (type " + std::to_string(it.resource_type) + " id " + std::to_string(it.resource_id) + " permission " +
            std::to_string(it.permission) + " @ type " + std::to_string(it.subject_type) + " id " + std::to_string(it.subject_id) + ")";
 }
 
 // walks the items listed in `pick` (indices into items; all HAS on a monotone slot) and appends their hops; count[k] = hops of pick[k]
+// (engine_proof.cpp walks its monotone items through it too)
 int explain_walk(acl_engine *h, PassCtx *c, const acl_item_t *items, const std::vector<uint32_t> &pick, std::vector<acl_explain_hop_t> *hops, std::vector<uint32_t> *count) {
     const Schema &sc = h->store.schema();
     const SubjectRows &sr = h->subj;
@@ -68,16 +71,16 @@ int explain_walk(acl_engine *h, PassCtx *c, const acl_item_t *items, const std::
                 const size_t idx = pick[b + i];
                 const uint32_t state = h_cnt[i] >> 16, nrec = h_cnt[i] & 0xFFFFu;
                 if (state != kExplainFound || nrec > kExplainTraceRecs)
-                    return fail(ACL_ERR_INTERNAL, "Explain: Check grants " + item_text(items[idx], idx) + " but the walk " +
+                    return fail(ACL_ERR_INTERNAL, "Explain: Check grants " + explain_item_text(items[idx], idx) + " but the walk " +
                                                       (state == kExplainNotFound ? "found no chain of relationships" : "could not trace its chain back") + " (the two kernels disagree)");
                 uint32_t nh = 0;
                 for (uint32_t k = 0; k < nrec; k++) {
                     const uint4 r = h_tr[i * kExplainTraceRecs + k];
-                    if (r.x >= sr.xops.size()) return fail(ACL_ERR_INTERNAL, "Explain: a trace record of " + item_text(items[idx], idx) + " names no op");
+                    if (r.x >= sr.xops.size()) return fail(ACL_ERR_INTERNAL, "Explain: a trace record of " + explain_item_text(items[idx], idx) + " names no op");
                     const ExplainOp &x = sr.xops[r.x];
                     if (x.rtype == ExplainOp::kExplainRewrite) {
                         if (h->snap.ops[r.x].flags & OP_PUSH_SAME) continue;  // a rewrite step: same object, no relationship
-                        return fail(ACL_ERR_INTERNAL, "Explain: a trace record of " + item_text(items[idx], idx) + " names an op that reads no relationships");
+                        return fail(ACL_ERR_INTERNAL, "Explain: a trace record of " + explain_item_text(items[idx], idx) + " names an op that reads no relationships");
                     }
                     hops->push_back(acl_explain_hop_t{x.rtype, x.relation, r.y, x.stype, x.srel, r.z, (r.w & kExplainRecWild) ? ACL_HOP_WILDCARD : 0u});
                     nh++;
@@ -87,6 +90,8 @@ int explain_walk(acl_engine *h, PassCtx *c, const acl_item_t *items, const std::
             return (int)ACL_OK;
         });
 }
+
+namespace {
 
 // caller holds an Eval with the subject rows current
 int explain_batch(acl_engine *h, PassCtx *c, const acl_item_t *items, size_t n, uint8_t *perm, int32_t *err, uint8_t *flags, uint32_t *hop_off,
@@ -105,7 +110,7 @@ int explain_batch(acl_engine *h, PassCtx *c, const acl_item_t *items, size_t n, 
         // (a granted item passed the device's validation; the host reads the same fields, so it checks them again before it indexes with them)
         if (it.resource_type >= sc.defs.size() || it.subject_type >= sc.defs.size() || it.permission >= sc.defs[it.resource_type].members.size() ||
             (it.subject_relation != ACL_NO_RELATION && it.subject_relation >= sc.defs[it.subject_type].members.size()))
-            return fail(ACL_ERR_INTERNAL, "Explain: Check grants the ill-formed " + item_text(it, i));
+            return fail(ACL_ERR_INTERNAL, "Explain: Check grants the ill-formed " + explain_item_text(it, i));
         const size_t slot = (size_t)sc.slot(it.resource_type, it.permission);
         if (slot < h->snap.slot_nonmono.size() && h->snap.slot_nonmono[slot]) {
             flags[i] = ACL_EXPLAIN_UNSUPPORTED;
@@ -169,6 +174,28 @@ int explain_call(acl_engine_t *h, const acl_item_t *items, size_t n, uint8_t *pe
 
 }  // namespace
 
+// hops [k0, k1) in the tuple grammar of aclgpu/text.py, one per line, appended to *text.  Names are read under the names lock, as acl_object_name_copy
+// reads them (the hops' objects take part in relationships: their names stay)
+int explain_hops_text(acl_engine *h, const char *fn, const acl_explain_hop_t *hops, uint32_t k0, uint32_t k1, std::string *text) {
+    const std::string who = fn;
+    std::shared_lock<std::shared_mutex> nlk(h->names_mu);
+    const Schema &sc = h->store.schema();
+    for (uint32_t k = k0; k < k1; k++) {
+        const acl_explain_hop_t &hp = hops[k];
+        if (hp.rtype >= sc.defs.size() || hp.stype >= sc.defs.size() || hp.relation >= sc.defs[hp.rtype].members.size() ||
+            (hp.srel != ACL_NO_RELATION && hp.srel >= sc.defs[hp.stype].members.size()))
+            return fail(ACL_ERR_UNAVAILABLE, who + ": the schema changed while the witness was named");
+        const std::string *rn = h->store.objects(hp.rtype).name(hp.rid), *sn = h->store.objects(hp.stype).name(hp.sid);
+        if (!rn || (!sn && !(hp.flags & ACL_HOP_WILDCARD)))  // (the evaluation has ended: a write since may have taken a hop's object away; objects loaded by id never had a name)
+            return fail(ACL_ERR_UNAVAILABLE, who + ": an object of the witness has no name (loaded by id, or renamed by a write since the walk): use " + who + "_bulk_ids, or ask again");
+        *text += sc.defs[hp.rtype].name + ":" + *rn + "#" + sc.defs[hp.rtype].members[hp.relation].name + "@" + sc.defs[hp.stype].name + ":" +
+                 ((hp.flags & ACL_HOP_WILDCARD) ? std::string("*") : *sn);
+        if (hp.srel != ACL_NO_RELATION) *text += "#" + sc.defs[hp.stype].members[hp.srel].name;
+        *text += "\n";
+    }
+    return ACL_OK;
+}
+
 }  // namespace aclint
 
 int acl_explain_bulk_ids(acl_engine_t *h, const acl_item_t *items, size_t n, uint8_t *perm_out, int32_t *err_out, uint8_t *flags_out, uint32_t *hop_off_out,
@@ -203,29 +230,9 @@ int acl_explain(acl_engine_t *h, const acl_check_item_t *item, uint8_t *perm_out
         const int rc = explain_call(h, &it, 1, perm_out, err_out, &fl, off, &hops, opts);
         if (rc) return rc;
         if (flags_out) *flags_out = fl;
-        {
-            // names are read under the names lock, as acl_object_name_copy reads them (the hops' objects take part in relationships: their names stay)
-            std::shared_lock<std::shared_mutex> nlk(h->names_mu);
-            const Schema &sc = h->store.schema();
-            for (uint32_t k = off[0]; k < off[1]; k++) {
-                const acl_explain_hop_t &hp = hops[k];
-                if (hp.rtype >= sc.defs.size() || hp.stype >= sc.defs.size() || hp.relation >= sc.defs[hp.rtype].members.size() ||
-                    (hp.srel != ACL_NO_RELATION && hp.srel >= sc.defs[hp.stype].members.size())) {
-                    std::free(hops);
-                    return fail(ACL_ERR_UNAVAILABLE, "acl_explain: the schema changed while the witness was named");
-                }
-                const std::string *rn = h->store.objects(hp.rtype).name(hp.rid), *sn = h->store.objects(hp.stype).name(hp.sid);
-                if (!rn || (!sn && !(hp.flags & ACL_HOP_WILDCARD))) {  // (the evaluation has ended: a write since may have taken a hop's object away; objects loaded by id never had a name)
-                    std::free(hops);
-                    return fail(ACL_ERR_UNAVAILABLE, "acl_explain: an object of the witness has no name (loaded by id, or renamed by a write since the walk): use acl_explain_bulk_ids, or ask again");
-                }
-                text += sc.defs[hp.rtype].name + ":" + *rn + "#" + sc.defs[hp.rtype].members[hp.relation].name + "@" + sc.defs[hp.stype].name + ":" +
-                        ((hp.flags & ACL_HOP_WILDCARD) ? std::string("*") : *sn);
-                if (hp.srel != ACL_NO_RELATION) text += "#" + sc.defs[hp.stype].members[hp.srel].name;
-                text += "\n";
-            }
-        }
+        const int trc = explain_hops_text(h, "acl_explain", hops, off[0], off[1], &text);
         std::free(hops);
+        if (trc) return trc;
     }
     char *out = (char *)std::malloc(text.size() + 1);
     if (!out) return fail(ACL_ERR_RESOURCE_EXHAUSTED, "out of host memory for the witness");

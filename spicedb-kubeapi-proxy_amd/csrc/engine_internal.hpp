@@ -241,6 +241,9 @@ struct PassCtx {
     DevArray<uint4> d_items;
     DevArray<uint32_t> d_sids, d_visited, d_rows;
     DevArray<uint32_t> d_subj_visited, d_subj_rows, d_subj_flags;  // LookupSubjects (k_subj_local): visited regions, result rows, wildcard flags
+    DevArray<uint32_t> d_proof_obj, d_proof_group, d_proof_rows, d_proof_out;  // Explain proofs (kernels.hpp DevProofPick / DevProofRows): a pass's candidates, their groups, row descriptors, total | first[] | count[] | win[] | gn[]
+    DevArray<uint4> d_proof_groups;
+    uint32_t proof_region = 0;  // ids of the rows one proof pass enumerates on the device: grown 8 x when a pass overflows it (engine_proof.cpp)
     // result rows beyond the block's LDS (kernels.hpp RevBigRows): the lookups' deferred terminal rows, their counts / levels, the id-count accumulators
     DevArray<uint8_t> d_big_bytes;  // the lookups' byte maps, zero between launches (bytes_zeroed: the leading bytes known to be)
     size_t big_bytes_zeroed = 0;
@@ -577,6 +580,11 @@ int device_of(acl_engine *h, const void *p);  // HIP ordinal a device pointer li
 int check_device(acl_engine *h, PassCtx *c, const uint4 *d_items, size_t n, uint8_t *d_perm, int32_t *d_errout, bool try_local = true);  // try_local: the single-launch walk first
 // host items -> answers in host buffers through context c (pinned staging unless the caller's buffers are pinned)
 int check_ids_host(acl_engine *h, PassCtx *c, const acl_item_t *items, size_t n, uint8_t *perm_out, int32_t *err_out, bool items_on_device = false);  // items_on_device: c->d_items already holds them (items is not read)
+// Explain (engine_explain.cpp), shared with the proofs of engine_proof.cpp: the witness walk of the items pick[] (all HAS on a monotone slot; caller holds an
+// Eval with the subject rows current), an item spelled for a message, hops [k0, k1) printed in the tuple grammar under the names lock
+int explain_walk(acl_engine *h, PassCtx *c, const acl_item_t *items, const std::vector<uint32_t> &pick, std::vector<acl_explain_hop_t> *hops, std::vector<uint32_t> *count);
+std::string explain_item_text(const acl_item_t &it, size_t i);
+int explain_hops_text(acl_engine *h, const char *fn, const acl_explain_hop_t *hops, uint32_t k0, uint32_t k1, std::string *text);
 int lookup_candidate_error(acl_engine *h, int32_t code, uint32_t id, uint32_t sid);  // fails a LookupResources call with a candidate's Check error (lookups.go:75-83)
 int lookup_batch(acl_engine *h, PassCtx *c, int rtype, int perm, int stype, int srel, const uint32_t *sids, size_t n, uint32_t *bitmaps, size_t words,
                  uint64_t *counts, uint32_t *d_dst = nullptr /* watch sets: the rows stay on the device (engine_lookup.cpp) */, size_t dstride = 0);

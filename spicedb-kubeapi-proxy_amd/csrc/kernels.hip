@@ -3742,7 +3742,118 @@ __global__ __launch_bounds__(256) void k_subj_rows_store(const uint32_t *__restr
     }
 }
 
+// ---- Explain proofs: a round's candidates become items and their answers are folded per goal on the device (kernels.hpp DevProofPick) ----
+__global__ __launch_bounds__(256) void k_proof_items(DevProofPick p, uint4 *__restrict__ items) {
+    for (uint32_t k = blockIdx.x * 256u + threadIdx.x; k < p.ncand; k += gridDim.x * 256u) {
+        const uint32_t g = p.group[k];
+        // (a group index the host did not hand out names no header: the item is left ill-formed on purpose -- type 0xFFFF -- and answers with an error)
+        const uint4 gr = g < p.ngroups ? p.groups[g] : make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u);
+        items[k] = make_uint4(gr.x, p.obj[k], gr.y, gr.z);  // acl_item_t: {type | permission << 16, resource, subject type | relation << 16, subject}
+    }
+}
+
+__global__ __launch_bounds__(256) void k_proof_rows(DevProofRows r) {
+    __shared__ uint32_t s_at, s_deg, s_first;
+    const uint2 *__restrict__ meta2 = reinterpret_cast<const uint2 *>(r.meta);
+    for (uint32_t g = blockIdx.x; g < r.ngroups; g += gridDim.x) {  // (block-uniform trips: the barriers)
+        if (threadIdx.x == 0) {
+            const uint2 rw = r.rows[g];
+            uint32_t at = 0, deg = 0, first = 0;
+            if (rw.x < r.meta_pairs) {
+                const uint2 md = meta2[rw.x];
+                if (md.y > md.x && md.y <= r.nedges && md.y - md.x > rw.y) {
+                    first = md.x + rw.y;
+                    deg = md.y - first;
+                    const unsigned long long was = __hip_atomic_fetch_add(reinterpret_cast<unsigned long long *>(r.total), (unsigned long long)deg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (was + deg > (unsigned long long)r.cap) {  // the region is full: the caller redoes the pass with a larger one
+                        __hip_atomic_fetch_or(r.total + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        deg = 0;
+                    } else {
+                        at = (uint32_t)was;
+                    }
+                }
+                r.groups[g].w = at;
+                r.gn[g] = deg;
+            }
+            s_at = at;
+            s_deg = deg;
+            s_first = first;
+        }
+        __syncthreads();
+        const uint32_t at = s_at, deg = s_deg, first = s_first;
+        for (uint32_t i = threadIdx.x; i < deg; i += 256u) {  // (at + deg <= cap and first + deg <= nedges were checked by thread 0)
+            r.obj[at + i] = r.edges[first + i] & kIdMask;
+            r.group[at + i] = g;
+        }
+        __syncthreads();  // (before thread 0 overwrites the three words for the block's next group)
+    }
+}
+
+__global__ __launch_bounds__(256) void k_proof_winner(DevProofPick p, uint32_t *__restrict__ win) {
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < 2u * p.ngroups; i += gridDim.x * 256u) {
+        const uint32_t f = p.first[i];
+        const uint64_t at = (uint64_t)p.groups[i >> 1].w + f;
+        win[i] = (f != 0xFFFFFFFFu && at < p.ncand) ? p.obj[at] : 0xFFFFFFFFu;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_proof_pick(DevProofPick p, const uint8_t *__restrict__ perm, const int32_t *__restrict__ err, uint32_t has_value, uint32_t no_value) {
+    const uint32_t lane = lane_id();
+    for (uint32_t base = (blockIdx.x * 4u + uniform(threadIdx.x >> 6)) * 64u; base < p.ncand; base += gridDim.x * 256u) {  // (wave-uniform trips: the ballots)
+        const uint32_t k = base + lane;
+        uint32_t g = 0xFFFFFFFFu;
+        bool has = false, no = false;
+        if (k < p.ncand) {
+            g = p.group[k];
+            if (g < p.ngroups) {
+                const bool clean = err[k] == 0;
+                const uint32_t v = perm[k];
+                has = clean && v == has_value;
+                no = clean && v == no_value;
+            } else {
+                g = 0xFFFFFFFFu;
+            }
+        }
+        const uint32_t g0 = uniform(g);  // lane 0 is in range (base < ncand)
+        if (!__ballot(g != g0 && g != 0xFFFFFFFFu)) {  // one group in the wave (lanes behind the end, if any, carry none): one lane speaks for all
+            if (g0 == 0xFFFFFFFFu) continue;
+            const unsigned long long hb = __ballot(has), nb = __ballot(no);
+            if (lane == 0u) {
+                const uint32_t at = base - p.groups[g0].w;  // lane 0's index inside the group
+                if (hb) {
+                    __hip_atomic_fetch_min(p.first + 2u * g0, at + (uint32_t)__ffsll((long long)hb) - 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_fetch_add(p.count + 2u * g0, (uint32_t)__popcll(hb), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+                if (nb) {
+                    __hip_atomic_fetch_min(p.first + 2u * g0 + 1u, at + (uint32_t)__ffsll((long long)nb) - 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_fetch_add(p.count + 2u * g0 + 1u, (uint32_t)__popcll(nb), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+            }
+        } else if (has || no) {  // a wave that spans groups: every answering lane for itself
+            const uint32_t at = k - p.groups[g].w, w = 2u * g + (no ? 1u : 0u);
+            __hip_atomic_fetch_min(p.first + w, at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_fetch_add(p.count + w, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
 static uint32_t refine_blocks(uint64_t threads) { return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((threads + 255) / 256, 4096)); }
+void launch_proof_items(hipStream_t st, const DevProofPick &p, uint4 *items) {
+    if (!p.ncand || !p.ngroups) return;
+    hipLaunchKernelGGL(k_proof_items, dim3(refine_blocks(p.ncand)), dim3(256), 0, st, p, items);
+}
+void launch_proof_rows(hipStream_t st, const DevProofRows &r) {
+    if (!r.ngroups) return;
+    hipLaunchKernelGGL(k_proof_rows, dim3(std::min<uint32_t>(r.ngroups, 4096u)), dim3(256), 0, st, r);
+}
+void launch_proof_winner(hipStream_t st, const DevProofPick &p, uint32_t *win) {
+    if (!p.ngroups) return;
+    hipLaunchKernelGGL(k_proof_winner, dim3(refine_blocks(2ull * p.ngroups)), dim3(256), 0, st, p, win);
+}
+void launch_proof_pick(hipStream_t st, const DevProofPick &p, const uint8_t *perm, const int32_t *err, uint32_t has_value, uint32_t no_value) {
+    if (!p.ncand || !p.ngroups) return;
+    hipLaunchKernelGGL(k_proof_pick, dim3(refine_blocks(p.ncand)), dim3(256), 0, st, p, perm, err, has_value, no_value);
+}
 void launch_subj_rows_store(hipStream_t st, const uint32_t *src, uint32_t src_words, const uint32_t *src_flags, uint32_t m, uint32_t *dst, uint32_t dst_words, uint32_t *dst_flags) {
     if (!m || !dst_words) return;
     hipLaunchKernelGGL(k_subj_rows_store, dim3(refine_blocks((uint64_t)m * dst_words)), dim3(256), 0, st, src, src_words, src_flags, m, dst, dst_words, dst_flags);

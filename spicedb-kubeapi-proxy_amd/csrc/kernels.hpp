@@ -269,6 +269,39 @@ void launch_refine_fill(hipStream_t s, const DevRefine &r, uint32_t nflag, uint3
 void launch_refine_items(hipStream_t s, const DevRefine &r, uint4 *items);
 void launch_refine_apply(hipStream_t s, const DevRefine &r, const uint8_t *perm, const int32_t *err, uint32_t has_value, uint32_t *status);
 void launch_refine_wild(hipStream_t s, uint32_t *rows, uint32_t row_words, const uint32_t *flags, uint32_t n_rows, uint32_t wid);
+// Explain proofs (engine_proof.cpp): one round of the search asks, for each of `ngroups` goals, about a run of candidate objects -- the members of a row the
+// goal may step to -- that share the goal's {resource type | permission << 16, subject type | relation << 16, subject id}.  Candidates of a group are
+// neighbours, group g's start at groups[g].w.
+//   items : candidate k -> the 16-byte item {head, obj[k], tail, subject} of its group, one store per lane
+//   pick  : the answers of a Check over those items, folded per group where they are: first[2 g] / first[2 g + 1] = the least index INSIDE the group of a
+//           candidate that answered HAS / NO without error (the caller stores 0xFFFFFFFF first), count[2 g] / count[2 g + 1] = how many did (the caller
+//           stores 0 first).  A wave whose lanes share one group folds by ballot and issues one set of agent-scope atomics; 16 bytes per group reach the host
+struct DevProofPick {
+    const uint32_t *obj;    // [ncand] candidate object ids
+    const uint32_t *group;  // [ncand] the candidate's group
+    const uint4 *groups;    // [ngroups] {head, tail, subject id, index of the group's first candidate}
+    uint32_t ncand, ngroups;
+    uint32_t *first, *count;  // [2 ngroups] each
+};
+//   winner: win[2 g] / win[2 g + 1] = the object ids of those two candidates (0xFFFFFFFF: none), so a row the device enumerated never has to reach the host
+//   rows  : groups whose candidates are a whole sorted sub-row of the forward graph from its `floor`-th id on (rows[g] = {descriptor index, floor}; a
+//           descriptor index >= meta_pairs: not such a group, left alone) are enumerated where the row is -- one block per group reserves the row's length
+//           in the candidate region by one agent-scope add to total[0 .. 1] (64 bits, the caller stores the host-made candidates' count), writes its
+//           start into groups[g].w and its length into gn[g], and copies the ids; a row that does not fit into `cap` raises total[2] and copies nothing
+struct DevProofRows {
+    const uint32_t *meta, *edges;  // DevGraph's
+    uint32_t meta_pairs, nedges;   // their valid lengths (uint2 descriptors, ids)
+    const uint2 *rows;             // [ngroups]
+    uint4 *groups;                 // [ngroups]
+    uint32_t *gn;                  // [ngroups]
+    uint32_t *obj, *group;         // [cap]
+    uint32_t cap, ngroups;
+    uint32_t *total;               // [3]
+};
+void launch_proof_rows(hipStream_t s, const DevProofRows &r);
+void launch_proof_winner(hipStream_t s, const DevProofPick &p, uint32_t *win);
+void launch_proof_items(hipStream_t s, const DevProofPick &p, uint4 *items);
+void launch_proof_pick(hipStream_t s, const DevProofPick &p, const uint8_t *perm, const int32_t *err, uint32_t has_value, uint32_t no_value);
 // blocks per expand launch for this device (all co-resident); nwaves = blocks * kWavesPerBlock
 int expand_grid_blocks(int device);
 

@@ -314,7 +314,8 @@ int acl_lookup_subjects(acl_engine_t *h, const char *resource_type, const char *
  *     shortest chain by more than the schema's deepest inlined computed userset.  Which chain wins among equals is unspecified.
  * flags_out per item: ACL_EXPLAIN_WITNESS -- the hops prove it (possibly zero of them); ACL_EXPLAIN_UNSUPPORTED -- the item is granted by a permission
  * that holds `-`, `&` or `.all()` anywhere beneath: answered, not explained (that needs a tree of proofs and absences, not a chain), no hops; 0 -- not
- * granted (NO_PERMISSION or a per-item error such as ACL_ERR_DEPTH): no hops.  Items may mix resource types, permissions and subject classes.
+ * granted (NO_PERMISSION or a per-item error such as ACL_ERR_DEPTH): no hops (what to write for a denied item: acl_explain_denial_bulk_ids).  Items may
+ * mix resource types, permissions and subject classes.
  * A granted item for which no chain is found fails the call with ACL_ERR_INTERNAL (the message names the item); a walk that outgrows 2^24 states:
  * ACL_ERR_RESOURCE_EXHAUSTED.  Sharded engines answer ACL_ERR_FAILED_PRECONDITION, store-only engines ACL_ERR_UNAVAILABLE.  err_out and flags_out may be
  * NULL.  *hops_out is the engine's (one allocation, release with acl_free; NULL when the call fails or n == 0); hop_off_out holds n + 1 offsets. */
@@ -363,6 +364,40 @@ int acl_explain_proof_bulk_ids(acl_engine_t *h, const acl_item_t *items, size_t 
  * item), then every absence as `not type:id#relation@type:id[#relation]`. */
 int acl_explain_proof(acl_engine_t *h, const acl_check_item_t *item, uint8_t *perm_out, int32_t *err_out, uint32_t *flags_out, char **text_out,
                       const acl_call_opts_t *opts);
+
+/* ---- Explain for denials: the single writes that would grant a Check ----
+ * perm_out / err_out per item are exactly what acl_check_bulk_ids answers for the same items on the same snapshot (one evaluation holds the Check and the
+ * walk).  An item that answers NO_PERMISSION without error on a permission built from `+`, `->` and references alone gets ACL_EXPLAIN_DENIAL and the
+ * grants [grant_off_out[i], grant_off_out[i + 1]) of *grants_out, possibly none: ALL relationships `rtype:rid#relation@subject` -- the subject is the
+ * item's own object, with its relation if it has one -- whose write, alone, turns the item's answer into HAS_PERMISSION.
+ *   - sound: writing any one of them (TOUCH, no expiry, nothing else changed) makes the item's Check answer HAS_PERMISSION;
+ *   - complete: no other relationship with this subject does.  An empty list says "no single relationship with this subject grants it";
+ *   - a relation that accepts the subject's type only as `T:*` is not a grant for a named subject, and `T:*` itself is never suggested;
+ *   - level: the dispatch at which a Check finds the new relationship, counted from the item's resource (a relation of the resource asked directly: 1;
+ *     `view = viewer + ...` puts `viewer` of the same object at 2; every userset hop, arrow and reference adds one); never above 50;
+ *   - a relation reachable on several paths is listed once, at its least level; the grants of one item are sorted by (level, rtype, relation, rid), and
+ *     two calls on the same snapshot return the same bytes;
+ *   - a resource nobody has written (an id beyond the type's objects) still has grants on the resource itself: the records carry the id the item gave.
+ * Every other item gets no grants: a NO on a permission that holds `-`, `&` or `.all()` anywhere beneath gets ACL_EXPLAIN_UNSUPPORTED (a grant there may
+ * need a ban deleted, or two writes); a granted item gets flag 0 (acl_explain's business), and so does an item with a per-item error (ACL_ERR_DEPTH, an
+ * unknown type or permission: what such a Check has looked at is not known to be complete).  Items may mix resource types, permissions and subject
+ * classes; items about the same resource and permission share one walk.
+ * The answer is never truncated: a walk that outgrows 2^24 states, or a call whose states outgrow 2^27 records, fails with ACL_ERR_RESOURCE_EXHAUSTED.
+ * Sharded engines answer ACL_ERR_FAILED_PRECONDITION, store-only engines ACL_ERR_UNAVAILABLE.  err_out and flags_out may be NULL; n == 0 succeeds.
+ * *grants_out is the engine's (one allocation, release with acl_free; NULL when the call fails or n == 0); grant_off_out holds n + 1 offsets. */
+typedef struct {
+    uint16_t rtype, relation; /* the relation to write (type, member index as acl_relation_id gives it) */
+    uint32_t rid;             /* ... of this object; the subject is the item's own */
+    uint32_t level;           /* dispatches from the item's resource at which a Check finds the new relationship (1..50) */
+} acl_grant_t;
+#define ACL_EXPLAIN_DENIAL 8u /* per item: grants [grant_off[i], grant_off[i+1]) are ALL single relationships whose write grants it */
+int acl_explain_denial_bulk_ids(acl_engine_t *h, const acl_item_t *items, size_t n, uint8_t *perm_out, int32_t *err_out, uint8_t *flags_out,
+                                uint32_t *grant_off_out, acl_grant_t **grants_out, const acl_call_opts_t *opts);
+/* string form, one item: *text_out = one relationship to write per line, in the tuple grammar and in the order above (the engine's: acl_free; an empty
+ * string when there are none).  Names, validation and refusals are acl_explain's; an unknown resource name yields grants on the resource itself, spelled
+ * as the item spelled it. */
+int acl_explain_denial(acl_engine_t *h, const acl_check_item_t *item, uint8_t *perm_out, int32_t *err_out, uint32_t *flags_out, char **text_out,
+                       const acl_call_opts_t *opts);
 
 /* ---- the callers either side of the kernels ----
  * PostFilter: filterItemsWithBulkPermissions (postfilter.go:58-182).  The K list items' resolved pairs are ONE bulk
@@ -679,6 +714,12 @@ typedef struct {
     uint32_t kind;            /* the op's kind bits (csrc/plan.hpp OP_*) */
 } acl_explain_op_t;
 int acl_selfcheck_explain_ops(acl_engine_t *h, acl_explain_op_t *out, size_t cap, size_t *n_out);
+/* The host half of acl_explain_denial_bulk_ids alone, on a caller-supplied list of states: states holds n records {object id, slot | level << 16} (two
+ * words each; slot = the type's first slot + member index) as the device's walk of rtype's `member` returns them, (stype, srel: -1 none) is the subject's
+ * class.  *grants_out: the grants those states hold for such a subject, deduplicated and sorted as above (malloc'd: acl_free), *n_out of them.  A pure
+ * function of the schema: works on a store-only engine. */
+int acl_selfcheck_denial_grants(acl_engine_t *h, int rtype, int member, int stype, int srel, const uint32_t *states, size_t n, acl_grant_t **grants_out,
+                                size_t *n_out);
 /* ---- measurement ---- */
 typedef struct {
     uint64_t check_items;      /* items answered since open / last reset */

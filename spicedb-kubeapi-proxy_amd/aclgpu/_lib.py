@@ -34,6 +34,7 @@ SYMBOLS = [
     "acl_watch_set_open_subjects", "acl_selfcheck_rows_diff", "acl_selfcheck_subject_rows",
     "acl_explain_bulk_ids", "acl_explain", "acl_selfcheck_explain_ops",
     "acl_explain_proof_bulk_ids", "acl_explain_proof",
+    "acl_explain_denial_bulk_ids", "acl_explain_denial", "acl_selfcheck_denial_grants",
 ]
 
 
@@ -82,6 +83,11 @@ class ExplainHop(C.Structure):
     """acl_explain_hop_t: one stored relationship of a witness (ids; flags bit 0: sid is the id of `stype:*`)."""
     _fields_ = [("rtype", C.c_uint16), ("relation", C.c_uint16), ("rid", C.c_uint32), ("stype", C.c_uint16), ("srel", C.c_uint16), ("sid", C.c_uint32),
                 ("flags", C.c_uint32)]
+
+
+class Grant(C.Structure):
+    """acl_grant_t: one relationship whose write grants a denied item (the subject is the item's own)."""
+    _fields_ = [("rtype", C.c_uint16), ("relation", C.c_uint16), ("rid", C.c_uint32), ("level", C.c_uint32)]
 
 
 class ExplainOpRec(C.Structure):
@@ -247,6 +253,9 @@ def load():
     L.acl_explain_proof_bulk_ids.argtypes = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.POINTER(ExplainHop)), C.c_void_p,
                                              C.POINTER(C.c_void_p), C.POINTER(CallOpts)]
     L.acl_explain_proof.argtypes = [H, C.POINTER(CheckItem), C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_void_p), C.POINTER(CallOpts)]
+    L.acl_explain_denial_bulk_ids.argtypes = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.POINTER(Grant)), C.POINTER(CallOpts)]
+    L.acl_explain_denial.argtypes = [H, C.POINTER(CheckItem), C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_void_p), C.POINTER(CallOpts)]
+    L.acl_selfcheck_denial_grants.argtypes = [H, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.POINTER(Grant)), C.POINTER(C.c_size_t)]
     L.acl_watch_set_open.argtypes = [H, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     L.acl_watch_set_open_subjects.argtypes = [H, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     L.acl_watch_set_add.argtypes = [H, C.c_void_p, C.c_char_p, C.c_uint32, C.POINTER(C.c_uint32)]

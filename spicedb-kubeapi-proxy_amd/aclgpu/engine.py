@@ -7,11 +7,12 @@ pkg/authz/lookups.go:49-62.
 from __future__ import annotations
 
 import ctypes as C
+import weakref
 
 import numpy as np
 
 from . import _lib
-from ._lib import CallOpts, CheckItem, Completion, Config, ExplainHop, ExplainOpRec, Filter, READ_CB, Relationship, Stats, Update, WATCH_CB, WATCH_CHECK_CB, WatchChange
+from ._lib import CallOpts, CheckItem, Completion, Config, ExplainHop, ExplainOpRec, Filter, Grant, READ_CB, Relationship, Stats, Update, WATCH_CB, WATCH_CHECK_CB, WatchChange
 
 PERM_UNSPECIFIED, PERM_NO, PERM_HAS, PERM_CONDITIONAL = 0, 1, 2, 3
 OP_CREATE, OP_TOUCH, OP_DELETE = 1, 2, 3
@@ -34,6 +35,9 @@ HOP_DTYPE = np.dtype([("rtype", "<u2"), ("relation", "<u2"), ("rid", "<u4"), ("s
 assert HOP_DTYPE.itemsize == C.sizeof(ExplainHop) == 20
 EXPLAIN_OP_DTYPE = np.dtype([("rtype", "<u2"), ("relation", "<u2"), ("stype", "<u2"), ("srel", "<u2"), ("slot", "<u4"), ("dlevel", "<u4"), ("kind", "<u4")])  # acl_explain_op_t
 assert EXPLAIN_OP_DTYPE.itemsize == C.sizeof(ExplainOpRec) == 20
+GRANT_DTYPE = np.dtype([("rtype", "<u2"), ("relation", "<u2"), ("rid", "<u4"), ("level", "<u4")])  # acl_grant_t
+assert GRANT_DTYPE.itemsize == C.sizeof(Grant) == 12
+EXPLAIN_DENIAL = 8                              # ACL_EXPLAIN_DENIAL: the item's grants are ALL single relationships whose write grants it
 HOP_WILDCARD = 1                                # ACL_HOP_WILDCARD
 EXPLAIN_WITNESS, EXPLAIN_UNSUPPORTED = 1, 2     # per-item flags of Explain
 HOP_SEGMENT = 2                                 # ACL_HOP_SEGMENT: the hop starts a new chain of a proof
@@ -817,6 +821,51 @@ class Engine:
         finally:
             self._L.acl_free(txt)
         return p.value, e.value, f.value, lines
+
+    def explain_denial_ids(self, items: np.ndarray, cancel=None, timeout_s=None):
+        """acl_explain_denial_bulk_ids: Check + the single writes that would grant each denied item -> (perm u8[n], err i32[n], flags u8[n],
+        grant_off u32[n + 1], grants GRANT_DTYPE[]); writing grants[k] for k in grant_off[i]:grant_off[i + 1] with item i's subject grants item i."""
+        items = np.ascontiguousarray(items, dtype=ITEM_DTYPE)
+        n = items.size
+        perm = np.zeros(max(1, n), dtype=np.uint8)
+        err = np.zeros(max(1, n), dtype=np.int32)
+        flags = np.zeros(max(1, n), dtype=np.uint8)
+        off = np.zeros(n + 1, dtype=np.uint32)
+        gp = C.POINTER(Grant)()
+        o = self._opts(cancel, timeout_s)
+        self._check(self._L.acl_explain_denial_bulk_ids(self._h, items.ctypes.data, n, perm.ctypes.data, err.ctypes.data, flags.ctypes.data, off.ctypes.data,
+                                                        C.byref(gp), C.byref(o) if o else None))
+        total = int(off[n])
+        if not total:
+            self._L.acl_free(gp)
+            return perm[:n], err[:n], flags[:n], off, np.zeros(0, dtype=GRANT_DTYPE)
+        # No copy: the array reads the engine's allocation, which is released (acl_free) when the last array over it goes away -- 4 096 items about one
+        # resource return 4 096 lists, tens of megabytes.
+        buf = (C.c_char * (total * GRANT_DTYPE.itemsize)).from_address(C.addressof(gp.contents))
+        weakref.finalize(buf, self._L.acl_free, C.c_void_p(C.addressof(gp.contents)))
+        return perm[:n], err[:n], flags[:n], off, np.frombuffer(buf, dtype=GRANT_DTYPE)
+
+    def explain_denial(self, rt, rid, perm, st, sid, srel=""):
+        """acl_explain_denial: (permissionship, error code, flags, [relationships to write, in the tuple grammar of aclgpu/text.py])."""
+        it = CheckItem(*[_b(x if x is not None else "") for x in (rt, rid, perm, st, sid, srel)])
+        p, e, f, txt = C.c_uint8(), C.c_int32(), C.c_uint32(), C.c_void_p()
+        self._check(self._L.acl_explain_denial(self._h, C.byref(it), C.byref(p), C.byref(e), C.byref(f), C.byref(txt), None))
+        try:
+            lines = C.string_at(txt).decode().splitlines() if txt.value else []
+        finally:
+            self._L.acl_free(txt)
+        return p.value, e.value, f.value, lines
+
+    def selfcheck_denial_grants(self, rtype: str, member: str, stype: str, srel: str, states) -> np.ndarray:
+        """Test hook (any engine): the host half of Explain denial on states [(object id, slot | level << 16)] -> GRANT_DTYPE records."""
+        st = np.ascontiguousarray(states, dtype=np.uint32).reshape(-1, 2)
+        gp, n = C.POINTER(Grant)(), C.c_size_t()
+        self._check(self._L.acl_selfcheck_denial_grants(self._h, self.type_id(rtype), self.relation_id(rtype, member), self.type_id(stype), self.relation_id(stype, srel),
+                                                        st.ctypes.data, st.shape[0], C.byref(gp), C.byref(n)))
+        try:
+            return np.frombuffer(C.string_at(gp, n.value * GRANT_DTYPE.itemsize), dtype=GRANT_DTYPE).copy() if n.value else np.zeros(0, dtype=GRANT_DTYPE)
+        finally:
+            self._L.acl_free(gp)
 
     def selfcheck_explain_ops(self) -> np.ndarray:
         """Test hook (store-only engines): Explain's per-op side table, one EXPLAIN_OP_DTYPE record (acl_explain_op_t) per program op."""

@@ -174,6 +174,12 @@ int explain_call(acl_engine_t *h, const acl_item_t *items, size_t n, uint8_t *pe
 
 }  // namespace
 
+void relationship_line(const Schema &sc, uint16_t rtype, const std::string &rid, uint16_t relation, uint16_t stype, const std::string &sid, uint16_t srel, std::string *text) {
+    *text += sc.defs[rtype].name + ":" + rid + "#" + sc.defs[rtype].members[relation].name + "@" + sc.defs[stype].name + ":" + sid;
+    if (srel != ACL_NO_RELATION) *text += "#" + sc.defs[stype].members[srel].name;
+    *text += "\n";
+}
+
 // hops [k0, k1) in the tuple grammar of aclgpu/text.py, one per line, appended to *text.  Names are read under the names lock, as acl_object_name_copy
 // reads them (the hops' objects take part in relationships: their names stay)
 int explain_hops_text(acl_engine *h, const char *fn, const acl_explain_hop_t *hops, uint32_t k0, uint32_t k1, std::string *text) {
@@ -188,10 +194,7 @@ int explain_hops_text(acl_engine *h, const char *fn, const acl_explain_hop_t *ho
         const std::string *rn = h->store.objects(hp.rtype).name(hp.rid), *sn = h->store.objects(hp.stype).name(hp.sid);
         if (!rn || (!sn && !(hp.flags & ACL_HOP_WILDCARD)))  // (the evaluation has ended: a write since may have taken a hop's object away; objects loaded by id never had a name)
             return fail(ACL_ERR_UNAVAILABLE, who + ": an object of the witness has no name (loaded by id, or renamed by a write since the walk): use " + who + "_bulk_ids, or ask again");
-        *text += sc.defs[hp.rtype].name + ":" + *rn + "#" + sc.defs[hp.rtype].members[hp.relation].name + "@" + sc.defs[hp.stype].name + ":" +
-                 ((hp.flags & ACL_HOP_WILDCARD) ? std::string("*") : *sn);
-        if (hp.srel != ACL_NO_RELATION) *text += "#" + sc.defs[hp.stype].members[hp.srel].name;
-        *text += "\n";
+        relationship_line(sc, hp.rtype, *rn, hp.relation, hp.stype, (hp.flags & ACL_HOP_WILDCARD) ? std::string("*") : *sn, hp.srel, text);
     }
     return ACL_OK;
 }

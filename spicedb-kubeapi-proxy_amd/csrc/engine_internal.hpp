@@ -243,6 +243,8 @@ struct PassCtx {
     DevArray<uint32_t> d_subj_visited, d_subj_rows, d_subj_flags;  // LookupSubjects (k_subj_local): visited regions, result rows, wildcard flags
     DevArray<uint32_t> d_proof_obj, d_proof_group, d_proof_rows, d_proof_out;  // Explain proofs (kernels.hpp DevProofPick / DevProofRows): a pass's candidates, their groups, row descriptors, total | first[] | count[] | win[] | gn[]
     DevArray<uint4> d_proof_groups;
+    DevArray<uint2> d_reach_recs;  // Explain denial (kernels.hpp DevReachOut): the call-wide region the blocks of k_reach_local copy their states into
+    uint32_t reach_region = 0;     // ... its records: grown 8 x when a pass overflows it (engine_denial.cpp), kept across calls
     uint32_t proof_region = 0;  // ids of the rows one proof pass enumerates on the device: grown 8 x when a pass overflows it (engine_proof.cpp)
     // result rows beyond the block's LDS (kernels.hpp RevBigRows): the lookups' deferred terminal rows, their counts / levels, the id-count accumulators
     DevArray<uint8_t> d_big_bytes;  // the lookups' byte maps, zero between launches (bytes_zeroed: the leading bytes known to be)
@@ -585,6 +587,11 @@ int check_ids_host(acl_engine *h, PassCtx *c, const acl_item_t *items, size_t n,
 int explain_walk(acl_engine *h, PassCtx *c, const acl_item_t *items, const std::vector<uint32_t> &pick, std::vector<acl_explain_hop_t> *hops, std::vector<uint32_t> *count);
 std::string explain_item_text(const acl_item_t &it, size_t i);
 int explain_hops_text(acl_engine *h, const char *fn, const acl_explain_hop_t *hops, uint32_t k0, uint32_t k1, std::string *text);
+// one relationship in the tuple grammar of aclgpu/text.py + a newline, appended to *text (srel: ACL_NO_RELATION = none; the indices are the caller's to check)
+void relationship_line(const Schema &sc, uint16_t rtype, const std::string &rid, uint16_t relation, uint16_t stype, const std::string &sid, uint16_t srel, std::string *text);
+// Explain denial (engine_denial.cpp): the host half, a pure function of the schema -- the grants that the states recs[0, n) = {object id, slot | level << 16}
+// hold for a subject of class (stype, srel: kNoRelation = none), deduplicated at their least level and sorted by (level, rtype, relation, rid)
+void denial_grants(const Schema &sc, const uint2 *recs, size_t n, int stype, int srel, std::vector<acl_grant_t> *out);
 int lookup_candidate_error(acl_engine *h, int32_t code, uint32_t id, uint32_t sid);  // fails a LookupResources call with a candidate's Check error (lookups.go:75-83)
 int lookup_batch(acl_engine *h, PassCtx *c, int rtype, int perm, int stype, int srel, const uint32_t *sids, size_t n, uint32_t *bitmaps, size_t words,
                  uint64_t *counts, uint32_t *d_dst = nullptr /* watch sets: the rows stay on the device (engine_lookup.cpp) */, size_t dstride = 0);
@@ -680,7 +687,9 @@ struct BlockWalk {
     uint32_t cap_first, cap_max;
 };
 // prepare(b, m): buffers, uploads and memsets of chunk [b, b + m) other than the visited bits and the status word; run(m, cap): the launch (between
-// ev_begin / ev_end) and the copies back, all on c->stream; collect(b, m): the chunk's results, after the stream was synchronised with status 0.
+// ev_begin / ev_end) and the copies back, all on c->stream; collect(b, m): the chunk's results, after the stream was synchronised with status 0 --
+// kRedoChunk from it walks the same chunk again (Explain denial: its output region was too small and has been grown).
+constexpr int kRedoChunk = -1001;  // internal: never leaves the library
 template <typename Prepare, typename Run, typename Collect>
 int block_walk_chunks(acl_engine *h, PassCtx *c, const BlockWalk &w, size_t n, Prepare prepare, Run run, Collect collect) {
     const std::string op = w.op;
@@ -715,6 +724,7 @@ int block_walk_chunks(acl_engine *h, PassCtx *c, const BlockWalk &w, size_t n, P
             continue;
         }
         rc = collect(b, m);
+        if (rc == kRedoChunk) continue;
         if (rc) return rc;
         b += m;
     }

@@ -2066,7 +2066,7 @@ constexpr uint32_t kRevLocalBudget = 1u << 22;      // children of one round a s
 constexpr uint32_t kRevTerminal = 0x80000000u;      // task target flag: children are only marked, never expanded
 constexpr uint32_t kRevNoMark = 0x40000000u;        // task target flag (OP_NOMARK seed ops): every child is a first visit by construction -- no visited bit
 
-// ---- block primitives of the one-block walks (k_rev_local here; k_subj_local and k_explain_local through subj_block_walk)
+// ---- block primitives of the one-block walks (k_rev_local here; k_subj_local, k_explain_local and k_reach_local through subj_block_walk)
 // Block-wide exclusive scan of one degree per thread: before = the sum over the threads below this one, total = the block's sum (block-uniform).
 // One barrier, between the store of the wave totals and their read; a caller that scans again puts a barrier of its own between the two.
 template <int THREADS>
@@ -2859,10 +2859,12 @@ void launch_rev_import(hipStream_t s, const DevReverse &r, const DevFrontier &f,
 
 // ---- the forward walk of LookupSubjects and Explain (plan.hpp SubjectRows).  A walk starts at one resource's state and follows the FORWARD programs: the
 // positive relaxation of the Check they encode -- ops inside the subtracted operand of an exclusion are skipped (SubjOp kSubjSkip), both sides of `&` and the
-// tupleset of `.all()` are walked.  Three kernels share it:
+// tupleset of `.all()` are walked.  Four kernels share it:
 //   k_subj_local     one block per lookup, every level in one launch: subj_block_walk with SubjectsPolicy -- reached rows of the subject class are EMITTED
 //   k_explain_local  one block per item, the same walk with ExplainPolicy -- reached rows are TESTED for the item's one subject, every state remembers its parent
 //   k_subj_expand    one launch per level over the chunked frontier (the sharded graph): its own loop, the same decode
+//   k_reach_local    one block per (resource, permission) of an Explain-denial call, the same walk with ReachPolicy -- children only, no row is emitted or
+//                    tested: the log IS the result, the states a denied Check has looked at
 // subj_decode is the one place that says what an op does, at dispatch level L = the state's level + op.dlevel <= kMaxLevels (k_check_local's rule: a Check
 // answers HAS there):
 //   OP_PROBE_HASH of key T      -> every id of the class's subject row for the state's object (OP_WILD: the row is the wildcard's -> the flag)
@@ -2870,7 +2872,8 @@ void launch_rev_import(hipStream_t s, const DevReverse &r, const DevFrontier &f,
 //   OP_REFLEX of key T#r        -> the state's own id
 //   OP_ENUM / OP_PUSH_SAME      -> child states at L + 1 (when L + 1 <= kMaxLevels); a userset row of key T#r is emitted through its children's REFLEX
 //                                  ops, or, when the children would lie beyond the limit, by the probe itself
-// (TEST, Explain: "every id of the row" becomes "does the row hold the subject", answered by the device functions of k_check_local's interpreter.)
+// (TEST, Explain: "every id of the row" becomes "does the row hold the subject", answered by the device functions of k_check_local's interpreter.
+//  REACH, Explain denial: probes and reflex ops yield nothing; only the last line is left, and the walk does not depend on the subject.)
 // Depth: a state counts at the LEAST level it can be reached at.  subj_block_walk processes its log level by level; a child one level below the current one
 // gets its visited bit when it is appended (nothing of a lower level is still to come), a child further down (an inlined computed userset's offset) is appended
 // unmarked and decides its visit when its own level comes round -- after every state of the levels before it has been marked.
@@ -2936,15 +2939,22 @@ struct SubjStep {  // what one (state, op) pair asks of the walk
     __device__ __forceinline__ bool wild() const { return (flags & kWild) != 0u; }
     __device__ __forceinline__ bool too_long() const { return (flags & kTooLong) != 0u; }
 };
-// what a probe does (subj_decode's mode): LookupSubjects hands the probed row back to be emitted, Explain tests it for the item's one subject
+// what a probe does (subj_decode's mode): LookupSubjects hands the probed row back to be emitted, Explain tests it for the item's one subject, Explain
+// denial ignores it (the closure of a resource's states is the same for every subject)
 struct SubjEmit {
-    static constexpr bool kTest = false;
+    static constexpr bool kTest = false, kReach = false;
     __device__ __forceinline__ bool is(uint32_t) const { return true; }
     __device__ __forceinline__ bool hashed_has(const FwdOp &, uint32_t) const { return false; }
     __device__ __forceinline__ bool sorted_has(const uint2 &) const { return false; }
 };
+struct SubjReach {
+    static constexpr bool kTest = false, kReach = true;
+    __device__ __forceinline__ bool is(uint32_t) const { return false; }
+    __device__ __forceinline__ bool hashed_has(const FwdOp &, uint32_t) const { return false; }
+    __device__ __forceinline__ bool sorted_has(const uint2 &) const { return false; }
+};
 struct SubjTest {
-    static constexpr bool kTest = true;
+    static constexpr bool kTest = true, kReach = false;
     const DevGraph *dg;  // what subject_row_contains reads: the forward row descriptors and the hashed buckets
     uint32_t sid;
     __device__ __forceinline__ bool is(uint32_t id) const { return id == sid; }
@@ -2954,18 +2964,18 @@ struct SubjTest {
 // Op j of the `nops` ops of program p that count for the state (p's slot, id) at `level`, looking for subjects of `key` (nops: n_total when the subject
 // carries a relation -- REFLEX ops count -- else n_main; 0 for a lane without a state).  Side effects are the caller's: it turns `wild` and `too_long` into
 // its own flag and stop code.  SubjTest: a probed row is tested, which also guards the id, and only ENUMERATED rows can be too long; SubjEmit: the probed
-// row is handed back as a task, guarded by the side table's row count.
+// row is handed back as a task, guarded by the side table's row count.  SubjReach: only OP_PUSH_SAME and OP_ENUM do anything (`key` is not read).
 template <typename Mode>
 __device__ __forceinline__ SubjStep subj_decode(const SubjTables &T, const SlotProg &p, uint32_t nops, uint32_t key, uint32_t id, uint32_t level, uint32_t j,
                                                 const Mode &mode) {
-    constexpr bool TEST = Mode::kTest;
+    constexpr bool TEST = Mode::kTest, REACH = Mode::kReach;
     SubjStep d;
     if (j >= nops || (T.sops[p.first + j].flags & kSubjSkip)) return d;
     const FwdOp op = T.ops[p.first + j];
     const uint32_t L = level + op.dlevel;
     if (L > kMaxLevels) return d;
     if (op.flags & OP_REFLEX) {
-        if (op.key == key && mode.is(id)) d.flags = SubjStep::kOneEmit;
+        if (!REACH && op.key == key && mode.is(id)) d.flags = SubjStep::kOneEmit;
     } else if (op.flags & OP_PUSH_SAME) {
         if (L + 1u <= kMaxLevels) {
             d.flags = SubjStep::kOneChild;
@@ -2973,7 +2983,7 @@ __device__ __forceinline__ SubjStep subj_decode(const SubjTables &T, const SlotP
             d.one_lvl = L + 1u;
         }
     } else if (op.flags & OP_PROBE_HASH) {
-        if (op.key != key) return d;
+        if (REACH || op.key != key) return d;
         if (TEST) {
             if (mode.hashed_has(op, id)) d.flags = SubjStep::kOneEmit;
             return d;
@@ -2994,7 +3004,7 @@ __device__ __forceinline__ SubjStep subj_decode(const SubjTables &T, const SlotP
     } else if (id < op.nrows) {
         const uint2 md = T.meta2[op.base + id * op.K + op.k];
         if (md.y > md.x) {
-            const bool probe = (op.flags & OP_PROBE) && op.key == key;
+            const bool probe = !REACH && (op.flags & OP_PROBE) && op.key == key;
             const bool enm = (op.flags & OP_ENUM) && L + 1u <= kMaxLevels;
             if (TEST && probe && mode.sorted_has(md)) d.flags = SubjStep::kOneEmit;
             if (md.y - md.x > kSubjMaxRow) {
@@ -3058,6 +3068,7 @@ __device__ __forceinline__ bool subj_block_walk(P &pol, const DevSubjects &g, co
     using Entry = typename P::Entry;
     const bool rel_key = key < g.nslots;  // the subject carries a relation: REFLEX ops count
     const uint32_t W = rel_key ? g.max_ops_rel : g.max_ops;
+    constexpr bool only_children = decltype(pol.probe)::kTest || decltype(pol.probe)::kReach;
     // child (slot, id) at level lvl, produced while level `cur` is expanded
     auto child = [&](uint32_t id, uint32_t slot, uint32_t lvl, uint32_t cur, bool valid, uint32_t par, uint32_t opi) {
         bool push = false;
@@ -3130,7 +3141,7 @@ __device__ __forceinline__ bool subj_block_walk(P &pol, const DevSubjects &g, co
                     const bool valid = x < total;
                     const uint32_t xv = valid ? x : total - 1u;  // (inactive lanes shadow the last id: every load stays in range)
                     const uint32_t jt = task_owner<kSubjThreads>(w.t.prefix, xv);
-                    const uint32_t tg = w.t.tag[jt], kind = decltype(pol.probe)::kTest ? kSubjChild : tg & (3u << 30);  // (TEST: rows are only ever enumerated)
+                    const uint32_t tg = w.t.tag[jt], kind = only_children ? kSubjChild : tg & (3u << 30);  // (TEST, REACH: rows are only ever enumerated)
                     const uint32_t pos = w.t.start[jt] + (xv - w.t.prefix[jt]);
                     const uint32_t v = kind == kSubjEmitIds ? gld(g.sids, pos) : (gld(g.edges, pos) & kIdMask);
                     pol.element(v, valid && kind != kSubjChild, lane);
@@ -3186,6 +3197,17 @@ struct ExplainPolicy {  // Explain: 16-byte entries that also carry {log index o
     // began, and nothing below them is needed.  An enumerated row beyond the limit (2) still fails.  (The stop word is last-writer-wins: an append's 1 may
     // overwrite a 2 of the same round.  That only decides whether a witness already found is returned; it is valid either way.)
     __device__ __forceinline__ bool level_done(uint32_t stop) const { return *s_hit != ~0ull && stop != 2u; }
+};
+struct ReachPolicy {  // Explain denial: 8-byte entries as LookupSubjects'; nothing is emitted or tested and no level ends the walk -- the log is the result
+    using Entry = uint2;
+    using Tasks = SubjTaskLds;
+    SubjReach probe;
+    __device__ __forceinline__ Entry entry(uint32_t id, uint32_t y, uint32_t, uint32_t) const { return make_uint2(id, y); }
+    __device__ __forceinline__ void keep_producer(Tasks &, uint32_t, uint32_t, uint32_t) const {}
+    __device__ __forceinline__ uint2 producer(const Tasks &, uint32_t) const { return make_uint2(0u, 0u); }
+    __device__ __forceinline__ void state(const SubjStep &, uint32_t, uint32_t, uint32_t, uint32_t) const {}
+    __device__ __forceinline__ void element(uint32_t, bool, uint32_t) const {}
+    __device__ __forceinline__ bool level_done(uint32_t) const { return false; }
 };
 }  // namespace
 
@@ -3327,6 +3349,81 @@ void launch_explain_local(hipStream_t s, const DevSubjects &g, const uint32_t *b
     const uint32_t prog_lds = prog_bytes <= kSubjLdsProgBytes ? 1u : 0u;
     hipLaunchKernelGGL(k_explain_local, dim3(n), dim3(kSubjThreads), prog_lds ? prog_bytes : 0u, s, g, buckets, items, (uint4 *)logs, cap, visited, prog_lds, traces,
                        counts, status);
+}
+
+// ---- Explain denial: k_reach_local (engine_denial.cpp).  One block walks ONE distinct (resource, permission) of the call with ReachPolicy: the forward closure
+// of the resource's state over userset and arrow relationships, which is the set of states a Check of that permission on that resource looks at whoever the
+// subject is.  When the walk is over, the log's entries without kSubjDead are the distinct states, each at its least level (a second visit and an entry that was
+// moved behind its level are dead; every other entry decided its first visit).  The block counts them, reserves that many records of the call-wide output region
+// with one agent-scope add (the blocks sit on different XCDs) and copies them there in tiles of kSubjThreads behind a block-wide scan of the keep flags.  A block
+// whose records do not fit raises *out.overflow and copies nothing: the host redoes the pass with a larger region.
+__global__ __launch_bounds__(kSubjThreads) void k_reach_local(DevSubjects g, const uint2 *__restrict__ roots, uint2 *logs, uint32_t cap, uint32_t *visited_all,
+                                                              uint32_t prog_lds, DevReachOut out, uint32_t *status) {
+    __shared__ alignas(16) SubjWalkLds<SubjTaskLds> w;
+    __shared__ uint32_t s_base;
+    extern __shared__ uint4 s_dyn[];  // [programs | ops | side table] when prog_lds
+    const uint32_t tid = threadIdx.x, lane = lane_id(), wib = tid >> 6;
+    const uint32_t req = blockIdx.x;
+    SubjTables T = subj_tables(g);
+    if (prog_lds) (void)subj_stage_programs(g, s_dyn, T, tid);
+    const uint2 root = roots[req];  // {resource id, target slot}
+    uint32_t *__restrict__ visited = visited_all + (size_t)req * g.visited_words;
+    uint2 *const log = logs + (size_t)req * cap;
+    if (tid == 0) {
+        w.end = 1;
+        w.stop = 0;
+        log[0] = make_uint2(root.x, root.y | (1u << 16) | kSubjMarked);  // (walked whatever its id, as Explain's root: a resource nobody has written is still a state)
+        (void)subj_first_visit<__HIP_MEMORY_SCOPE_WORKGROUP>(g, visited, root.y, root.x);
+    }
+    __syncthreads();
+    ReachPolicy pol{};
+    (void)subj_block_walk(pol, g, T, 0xFFFFFFFFu /* no subject key: REFLEX ops do not count */, log, cap, visited, w, tid, lane, wib);
+    __syncthreads();
+    if (w.stop) {  // (block-uniform: read behind the barrier, written by nobody from here on)
+        if (tid == 0) {
+            *status = w.stop;
+            out.spans[req] = make_uint2(0u, 0u);
+        }
+        return;
+    }
+    const uint32_t end = min(w.end, cap);
+    uint32_t mine = 0;
+    for (uint32_t i = tid; i < end; i += kSubjThreads) mine += (log[i].y & kSubjDead) ? 0u : 1u;
+    uint32_t before, total;
+    block_excl_scan<kSubjThreads>(mine, lane, wib, w.wave_tot, before, total);
+    if (tid == 0) {
+        const unsigned long long at = __hip_atomic_fetch_add(out.total, (unsigned long long)total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const bool fits = at + total <= (unsigned long long)out.cap;
+        if (!fits) *out.overflow = 1u;
+        s_base = fits ? (uint32_t)at : 0xFFFFFFFFu;
+        out.spans[req] = fits ? make_uint2((uint32_t)at, total) : make_uint2(0u, 0u);
+    }
+    __syncthreads();  // (also between the scan above and the first tile's)
+    const uint32_t base = s_base;
+    if (base == 0xFFFFFFFFu) return;
+    uint32_t done = 0;
+    for (uint32_t t0 = 0; t0 < end; t0 += kSubjThreads) {
+        const uint32_t i = t0 + tid;
+        uint2 en = make_uint2(0u, 0u);
+        bool keep = false;
+        if (i < end) {
+            en = log[i];
+            keep = !(en.y & kSubjDead);
+        }
+        uint32_t bf, tt;
+        block_excl_scan<kSubjThreads>(keep ? 1u : 0u, lane, wib, w.wave_tot, bf, tt);
+        if (keep) out.recs[(size_t)base + done + bf] = make_uint2(en.x, en.y & 0x3FFFFFu);  // (done + bf < total: inside the block's reservation)
+        done += tt;
+        __syncthreads();  // (the wave totals are read before the next tile's scan stores its own)
+    }
+}
+
+void launch_reach_local(hipStream_t s, const DevSubjects &g, const uint2 *roots, uint32_t n, void *logs, uint32_t cap, uint32_t *visited, const DevReachOut &out,
+                        uint32_t *status) {
+    if (!n) return;
+    const size_t prog_bytes = subj_prog_bytes(g);
+    const uint32_t prog_lds = prog_bytes <= kSubjLdsProgBytes ? 1u : 0u;
+    hipLaunchKernelGGL(k_reach_local, dim3(n), dim3(kSubjThreads), prog_lds ? prog_bytes : 0u, s, g, roots, (uint2 *)logs, cap, visited, prog_lds, out, status);
 }
 
 // ---- LookupSubjects, level-synchronous: k_subj_expand (the sharded graph's native loop, engine_shard_subjects.cpp).  One launch = one dispatch level of ALL

@@ -204,6 +204,20 @@ constexpr uint32_t kExplainFound = 0, kExplainNotFound = 1, kExplainBadTrace = 2
 constexpr uint32_t kExplainRecWild = 1u;
 void launch_explain_local(hipStream_t s, const DevSubjects &g, const uint32_t *buckets, const uint4 *items, uint32_t n, void *logs, uint32_t cap, uint32_t *visited,
                           uint4 *traces, uint32_t *counts, uint32_t *status);
+// single-launch Explain denial (kernels.hip k_reach_local): block b walks the forward programs from roots[b] = {resource id, target slot} by the same walk,
+// following children only, and hands back the distinct states it reached, each at its least dispatch level: out.spans[b] = {first record, count} of
+// out.recs, records {object id, slot | level << 16} in no particular order.  out.total (zeroed by the caller) counts the records of ALL blocks, also of
+// those that did not fit out.cap -- they raise *out.overflow (zeroed by the caller) and copy nothing.  logs: [n][cap] 8-byte entries; visited and *status as
+// for launch_subj_local.
+struct DevReachOut {
+    uint2 *recs;
+    uint32_t cap;
+    unsigned long long *total;
+    uint2 *spans;  // [n]
+    uint32_t *overflow;
+};
+void launch_reach_local(hipStream_t s, const DevSubjects &g, const uint2 *roots, uint32_t n, void *logs, uint32_t cap, uint32_t *visited, const DevReachOut &out,
+                        uint32_t *status);
 // level-synchronous LookupSubjects (kernels.hip k_subj_expand; the sharded graph's native loop): one launch per dispatch level over the chunked frontier, all
 // lookups of a chunk at once.  visited: [m][g.visited_words], rows: this shard's PARTIAL rows [m][row_words], flags: [m] bytes (1: a `T:*` row was reached) --
 // all zeroed by the caller.  A row beyond the per-task enumeration limit raises overflow code 2 in the frontier's status block.

@@ -120,6 +120,9 @@ int acl_load_bootstrap_yaml(acl_engine_t *h, const char *yaml_utf8, size_t len);
 /* ---- identifiers (pre-interned fast path) ---- */
 int acl_type_id(acl_engine_t *h, const char *type);                 /* -1 if unknown */
 int acl_relation_id(acl_engine_t *h, int type, const char *name);   /* relation or permission; -1 if unknown */
+/* the other way round (the ids in acl_access_review's rows): the name of definition `type` (member < 0) or of its relation / permission `member`, copied as
+ * acl_object_name_copy copies (NUL-terminated, cut to cap - 1 bytes); returns the name's length, -1 when there is no such definition or member */
+int64_t acl_schema_name_copy(acl_engine_t *h, int type, int member, char *buf, size_t cap);
 int acl_intern(acl_engine_t *h, int type, const char *object_id, uint32_t *id_out); /* creates if missing */
 int acl_find(acl_engine_t *h, int type, const char *object_id, uint32_t *id_out);   /* ACL_ERR_NOT_FOUND if missing */
 const char *acl_object_name(acl_engine_t *h, int type, uint32_t id); /* NULL for anonymous/unknown ids.  The pointer is only good while the id keeps its
@@ -281,6 +284,24 @@ void acl_free(void *p);
 /* batched form: n subjects of one (stype, srel) against one (rtype, permission); bitmaps_out is n * bitmap_words */
 int acl_lookup_resources_batch(acl_engine_t *h, int rtype, int permission, int stype, int srel, const uint32_t *subject_ids, size_t n,
                                uint32_t *bitmaps_out, size_t bitmap_words, uint64_t *counts_out);
+/* ---- many targets, ONE reverse walk per subject (a rule's several pre-filters for one user; an audit: "what does this user hold?") ---- */
+typedef struct { int32_t rtype; int32_t permission; } acl_target_t;   /* permission: a relation or a permission of rtype */
+/* n subjects of one (stype, srel) against n_targets targets.  Row of (subject i, target j): bitmaps_out + i * stride + off[j], row_words[j] words, stride = the
+ * sum of row_words, off = its exclusive prefix; counts_out[i * n_targets + j] = ids in that row (may be NULL).  Every row is bit for bit what
+ * acl_lookup_resources_batch answers for target j alone on the same snapshot (words behind the type's ids zeroed; candidates of a target with `-`, `&` or
+ * `.all()` confirmed by a forward Check, whose error fails the call unless ACL_FLAG_LENIENT_LOOKUP).  Duplicate targets are allowed, each gets its row.
+ * Arguments are validated before the engine's mode is looked at: a NULL pointer where one is needed: ACL_ERR_INVALID_ARGUMENT; an unknown type or member in
+ * a target: ACL_ERR_FAILED_PRECONDITION (the message names the target's index); a row_words[j] too small: ACL_ERR_INVALID_ARGUMENT; n_targets == 0 or
+ * n == 0: ACL_OK, nothing written.  Then: a store-only engine: ACL_ERR_UNAVAILABLE; a sharded engine: ACL_ERR_FAILED_PRECONDITION. */
+int acl_lookup_resources_multi(acl_engine_t *h, const acl_target_t *targets, size_t n_targets, int stype, int srel /* -1 none */,
+                               const uint32_t *subject_ids, size_t n, uint32_t *bitmaps_out, const size_t *row_words,
+                               uint64_t *counts_out, const acl_call_opts_t *opts);
+/* String form, engine-owned result (acl_free both *rows_out and *bitmaps_out).  targets == NULL: every relation and permission of every definition, in slot
+ * order.  Row k: (*bitmaps_out) + rows[k].row_off, rows[k].row_words words.  The subject's name is handled as acl_lookup_resources_alloc handles it. */
+typedef struct { int32_t rtype, permission; uint64_t count; size_t row_off, row_words; } acl_review_row_t;
+int acl_access_review(acl_engine_t *h, const char *subject_type, const char *subject_id, const char *subject_relation,
+                      const acl_target_t *targets, size_t n_targets, const acl_call_opts_t *opts,
+                      acl_review_row_t **rows_out, size_t *n_rows_out, uint32_t **bitmaps_out);
 
 /* ---- LookupSubjects (PermissionsService.LookupSubjects): who holds `permission` on ONE resource ----
  * Result = dense bitmap over the subject type's local ids: bit s set <=> Check(resource#permission @ stype:s[#srel]) is HAS_PERMISSION and s is
@@ -747,6 +768,8 @@ typedef struct {
     uint64_t hop2_rows;            /* two-hop rows of nested groups in the current snapshot (0: none qualify, or a nesting write dropped them until the next build) */
     double subj_local_ms;          /* HIP-event time of the single-launch LookupSubjects kernel (k_subj_local) */
     double refine_ms;              /* HIP-event time of a subject-direction watch set's confirmation kernels other than the Check itself (candidate records, items, apply) */
+    uint64_t rev_multi_passes;     /* acl_lookup_resources_multi groups answered by the many-target kernel (k_rev_multi: one walk, every target's row) */
+    double rev_multi_ms;           /* HIP-event time of that kernel */
 } acl_stats_t;
 int acl_stats(acl_engine_t *h, acl_stats_t *out);
 int acl_stats_reset(acl_engine_t *h);

@@ -35,6 +35,7 @@ SYMBOLS = [
     "acl_explain_bulk_ids", "acl_explain", "acl_selfcheck_explain_ops",
     "acl_explain_proof_bulk_ids", "acl_explain_proof",
     "acl_explain_denial_bulk_ids", "acl_explain_denial", "acl_selfcheck_denial_grants",
+    "acl_lookup_resources_multi", "acl_access_review", "acl_schema_name_copy",
 ]
 
 
@@ -112,7 +113,17 @@ class Stats(C.Structure):
                 ("snapshot_bytes", C.c_uint64), ("snapshot_builds", C.c_uint64), ("overflow_retries", C.c_uint64), ("snapshot_edges_local", C.c_uint64), ("snapshot_patches", C.c_uint64),
                 ("local_ms", C.c_double), ("local_passes", C.c_uint64), ("snapshot_compactions", C.c_uint64),
                 ("rev_local_ms", C.c_double), ("rev_local_passes", C.c_uint64), ("lookup_requests", C.c_uint64), ("ids_recycled", C.c_uint64), ("keep_route_calls", C.c_uint64), ("depth_sweeps", C.c_uint64), ("hop2_rows", C.c_uint64),
-                ("subj_local_ms", C.c_double), ("refine_ms", C.c_double)]
+                ("subj_local_ms", C.c_double), ("refine_ms", C.c_double), ("rev_multi_passes", C.c_uint64), ("rev_multi_ms", C.c_double)]
+
+
+class Target(C.Structure):
+    """acl_target_t: one (type, relation or permission) of acl_lookup_resources_multi / acl_access_review."""
+    _fields_ = [("rtype", C.c_int32), ("permission", C.c_int32)]
+
+
+class ReviewRow(C.Structure):
+    """acl_review_row_t: one row of acl_access_review -- row_words words at row_off of the call's bitmaps."""
+    _fields_ = [("rtype", C.c_int32), ("permission", C.c_int32), ("count", C.c_uint64), ("row_off", C.c_size_t), ("row_words", C.c_size_t)]
 
 
 ALL_GATHER_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
@@ -191,6 +202,8 @@ def load():
     L.acl_add_edges.argtypes = [H, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p]
     L.acl_revision.argtypes = [H]
     L.acl_revision.restype = C.c_uint64
+    L.acl_schema_name_copy.argtypes = [H, C.c_int, C.c_int, C.c_char_p, C.c_size_t]
+    L.acl_schema_name_copy.restype = C.c_int64
     L.acl_set_now.argtypes = [H, C.c_int64]
     L.acl_snapshot.argtypes = [H]
     L.acl_check_bulk.argtypes = [H, C.POINTER(CheckItem), C.c_size_t, C.c_void_p, C.c_void_p]
@@ -233,6 +246,9 @@ def load():
     L.acl_ticket_wait.argtypes = [H, C.c_void_p]
     L.acl_host_alloc.argtypes = [H, C.c_size_t, C.POINTER(C.c_void_p)]
     L.acl_host_free.argtypes = [H, C.c_void_p]
+    L.acl_lookup_resources_multi.argtypes = [H, C.POINTER(Target), C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CallOpts)]
+    L.acl_access_review.argtypes = [H, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(Target), C.c_size_t, C.POINTER(CallOpts), C.POINTER(C.POINTER(ReviewRow)),
+                                    C.POINTER(C.c_size_t), C.POINTER(C.POINTER(C.c_uint32))]
     L.acl_lookup_resources_alloc.argtypes = [H, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(CallOpts),
                                              C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]
     L.acl_filter_list_response_req.argtypes = [H, C.c_char_p, C.c_size_t, C.POINTER(C.c_char_p), C.c_size_t, C.c_char_p, C.POINTER(ListRequest), C.POINTER(C.c_void_p),

@@ -119,6 +119,12 @@ class Engine:
     def relation_id(self, t: str, r: str | None) -> int:
         return -1 if not r else self._L.acl_relation_id(self._h, self.type_id(t), _b(r))
 
+    def schema_name(self, type_id: int, member: int = -1):
+        """acl_schema_name_copy: the name of definition `type_id`, or of its relation / permission `member`; None when there is none."""
+        buf = C.create_string_buffer(256)
+        n = self._L.acl_schema_name_copy(self._h, int(type_id), int(member), buf, len(buf))
+        return None if n < 0 else buf.value.decode()
+
     def intern(self, t: str, oid: str) -> int:
         out = C.c_uint32()
         self._check(self._L.acl_intern(self._h, self.type_id(t), _b(oid), C.byref(out)))
@@ -717,6 +723,57 @@ class Engine:
     def lookup_ids(self, rtype, perm, stype, srel, subject_id):
         bms, _ = self.lookup_ids_batch(rtype, perm, stype, srel, [subject_id])
         return np.flatnonzero(np.unpackbits(bms[0].view(np.uint8), bitorder="little")).astype(np.uint32)
+
+    def lookup_ids_multi(self, targets, stype, srel, subject_ids, cancel=None, timeout_s=None, out=None):
+        """n subjects of one class against T targets [(rtype, perm), ...] in ONE reverse walk per subject (acl_lookup_resources_multi)
+        -> (list of T arrays [n, words_j] u32, counts [n, T] u64).  Row (i, j) is what lookup_ids_batch answers for target j alone.
+        `out` = the (rows, counts) pair of an earlier call with the same arguments, to write into (as lookup_ids_batch's)."""
+        from ._lib import Target
+        sids = np.ascontiguousarray(subject_ids, dtype=np.uint32)
+        n, T = int(sids.size), len(targets)
+        tg = (Target * max(1, T))()
+        words = np.zeros(max(1, T), dtype=np.uintp)
+        for j, (rt, pm) in enumerate(targets):
+            tg[j].rtype, tg[j].permission = self.type_id(rt), self.relation_id(rt, pm)
+            words[j] = (self.object_count(rt) + 31) // 32
+        off = np.concatenate(([0], np.cumsum(words[:T]))).astype(np.int64)  # row j of a subject: [off[j], off[j + 1]) of its stride
+        stride = int(off[T])
+        flat = out[0][0].base if out is not None and T and stride else None  # (the rows are views of one [n, stride] array)
+        if flat is not None and flat.shape == (n, stride) and flat.dtype == np.uint32 and flat.flags.c_contiguous and out[1].shape == (n, T) and out[1].dtype == np.uint64:
+            counts = out[1]
+        else:
+            flat = np.zeros((n, max(1, stride)), dtype=np.uint32)
+            counts = np.zeros((n, T), dtype=np.uint64)
+        o = self._opts(cancel, timeout_s)
+        self._check(self._L.acl_lookup_resources_multi(self._h, tg, T, self.type_id(stype), self.relation_id(stype, srel), sids.ctypes.data, n, flat.ctypes.data,
+                                                       words.ctypes.data, counts.ctypes.data, C.byref(o) if o else None))
+        return [flat[:, int(off[j]):int(off[j + 1])] for j in range(T)], counts
+
+    def access_review(self, stype, sid, srel="", targets=None, cancel=None, timeout_s=None):
+        """What one subject holds: {(rtype, perm): set of resource names}, every target answered by one reverse walk (acl_access_review).
+        targets = [(rtype, perm), ...]; None: every relation and permission of every definition."""
+        from ._lib import ReviewRow, Target
+        tg, T = None, 0
+        if targets is not None:
+            T = len(targets)
+            tg = (Target * max(1, T))()
+            for j, (rt, pm) in enumerate(targets):
+                tg[j].rtype, tg[j].permission = self.type_id(rt), self.relation_id(rt, pm)
+        rows, nrows, bms = C.POINTER(ReviewRow)(), C.c_size_t(), C.POINTER(C.c_uint32)()
+        o = self._opts(cancel, timeout_s)
+        self._check(self._L.acl_access_review(self._h, _b(stype), _b(sid), _b(srel or ""), tg, T, C.byref(o) if o else None, C.byref(rows), C.byref(nrows), C.byref(bms)))
+        try:
+            out = {}
+            for k in range(nrows.value):
+                r = rows[k]
+                a = np.ctypeslib.as_array(bms, shape=(r.row_off + max(1, r.row_words),))[r.row_off:r.row_off + r.row_words]
+                rt = self.schema_name(r.rtype)
+                ids = np.flatnonzero(np.unpackbits(a.view(np.uint8), bitorder="little"))
+                out[(rt, self.schema_name(r.rtype, r.permission))] = {self.object_name(rt, int(i)) for i in ids}
+        finally:
+            self._L.acl_free(rows)
+            self._L.acl_free(bms)
+        return out
 
     # ---- LookupSubjects (not Workload.lookup_subjects: that is C3's list of LookupResources subjects)
     def lookup_subjects_ids_batch(self, rtype, perm, stype, srel, resource_ids, want_excluded=False, cancel=None, timeout_s=None):

@@ -31,6 +31,8 @@ static void read_env_knobs(acl_engine *h) {
     if (const char *ev = getenv("ACL_SPIN_MAX")) h->spin_max = (uint32_t)std::max(0, atoi(ev));  // A/B knob
     if (const char *ev = getenv("ACL_LOCAL_WIDE_MIN")) h->local_wide_min = (uint32_t)std::max(0, atoi(ev));  // A/B knob
     if (const char *ev = getenv("ACL_REV_LOCAL")) h->rev_local = atoi(ev) != 0;
+    if (const char *ev = getenv("ACL_REV_MULTI_MIN_T")) h->rev_multi_min_targets = (size_t)std::max(2, atoi(ev));      // A/B knobs (tools/lookup_multi_bench.py): where the
+    if (const char *ev = getenv("ACL_REV_MULTI_MAX_WORDS")) h->rev_multi_max_words = (size_t)std::max(0, atoi(ev));    // many-target lookup takes its one walk
     if (const char *ev = getenv("ACL_REV_ROWS")) h->rev_rows_device = !std::strcmp(ev, "device");
     if (const char *ev = getenv("ACL_REV_LDS_ROWS")) h->rev_lds_rows = atoi(ev) != 0;
     if (const char *ev = getenv("ACL_REV_SINK")) h->rev_sink_on = atoi(ev) != 0;

@@ -272,7 +272,7 @@ struct PassCtx {
     bool timing = false;
     std::vector<hipEvent_t> ev;  // pairs
     size_t ev_used = 0;
-    std::vector<int> ev_kind;  // per pair: 0 other, 1 expand, 2 k_check_local, 3 k_rev_local, 4 k_subj_local, 5 a subject-direction watch set's confirmation
+    std::vector<int> ev_kind;  // per pair: 0 other, 1 expand, 2 k_check_local, 3 k_rev_local, 4 k_subj_local, 5 a subject-direction watch set's confirmation, 6 k_rev_multi
 
     ~PassCtx();
 };
@@ -454,6 +454,9 @@ struct acl_engine {
     bool rev_lds_rows = true;  // k_rev_local keeps the result slot's rows in LDS when they fit (ACL_REV_LDS_ROWS=0: always in HBM; A/B and tests)
     uint32_t rev_defer_min = 0;  // 0 = the kernels' default (4096 children per round); ACL_REV_DEFER_MIN: test knob
     bool rev_big_rows = true;   // result rows beyond the LDS: deferred terminal rows + chip-wide row copy (kernels.hip RevDefer); ACL_REV_BIG_ROWS=0 switches it off (A/B)
+    // acl_lookup_resources_multi takes its one walk (k_rev_multi) from this many targets on and while their rows hold at most this many words per lookup
+    // (engine_lookup_multi.cpp; the values come from profiles/lookup_multi_c4.md -- ACL_REV_MULTI_MIN_T / ACL_REV_MULTI_MAX_WORDS: the tool's sweep)
+    size_t rev_multi_min_targets = 2, rev_multi_max_words = 4096;
     bool rev_local = true;  // LookupResources: the single-launch reverse walk (k_rev_local) first; ACL_REV_LOCAL=0 = always the level loop (A/B)
     uint32_t lk_target = 0;  // sharded lookup in flight: target slot, number of requests
     size_t lk_n = 0;
@@ -595,6 +598,9 @@ void denial_grants(const Schema &sc, const uint2 *recs, size_t n, int stype, int
 int lookup_candidate_error(acl_engine *h, int32_t code, uint32_t id, uint32_t sid);  // fails a LookupResources call with a candidate's Check error (lookups.go:75-83)
 int lookup_batch(acl_engine *h, PassCtx *c, int rtype, int perm, int stype, int srel, const uint32_t *sids, size_t n, uint32_t *bitmaps, size_t words,
                  uint64_t *counts, uint32_t *d_dst = nullptr /* watch sets: the rows stay on the device (engine_lookup.cpp) */, size_t dstride = 0);
+// confirms the candidates of a permission with `&` / `-` / `.all()` by a forward Check (engine_lookup.cpp): n rows of cw words, `words` apart; counts[i] = ids kept
+int lookup_refine(acl_engine *h, PassCtx *c, int rtype, int perm, int stype, int srel, const uint32_t *sids, size_t n, uint32_t *bitmaps, size_t words, size_t cw,
+                  uint64_t *counts);
 void watch_sets_release(acl_engine_t *h);  // engine_watchset.cpp: acl_close frees the sets still open
 bool empty(const char *s);
 FilterText to_filter(const acl_filter_t *f);

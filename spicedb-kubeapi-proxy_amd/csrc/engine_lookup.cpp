@@ -131,8 +131,8 @@ int lookup_candidate_error(acl_engine *h, int32_t code, uint32_t id, uint32_t si
     return fail(code, std::string(code == ACL_ERR_DEPTH ? "LookupResources: max depth exceeded" : "LookupResources: a candidate's check failed") + " while checking candidate id " +
                           std::to_string(id) + " for subject id " + std::to_string(sid) + " (the permission holds an intersection / exclusion: candidates are confirmed by a forward Check)");
 }
-static int lookup_refine(acl_engine *h, PassCtx *c, int rtype, int perm, int stype, int srel, const uint32_t *sids, size_t n, uint32_t *bitmaps, size_t words, size_t cw,
-                         uint64_t *counts) {
+int lookup_refine(acl_engine *h, PassCtx *c, int rtype, int perm, int stype, int srel, const uint32_t *sids, size_t n, uint32_t *bitmaps, size_t words, size_t cw,
+                  uint64_t *counts) {
     std::vector<acl_item_t> items;
     std::vector<uint8_t> answers;
     std::vector<int32_t> errs;

@@ -89,6 +89,7 @@ void ev_collect(PassCtx *c) {  // stream must be synchronized
             else if (c->ev_kind[i / 2] == 3) c->stats.rev_local_ms += ms;
             else if (c->ev_kind[i / 2] == 4) c->stats.subj_local_ms += ms;
             else if (c->ev_kind[i / 2] == 5) c->stats.refine_ms += ms;
+            else if (c->ev_kind[i / 2] == 6) c->stats.rev_multi_ms += ms;
         }
     }
     c->ev_used = 0;
@@ -110,6 +111,8 @@ void merge_stats(acl_engine *h, PassCtx *c) {
     a.rev_local_passes += b.rev_local_passes;
     a.subj_local_ms += b.subj_local_ms;
     a.refine_ms += b.refine_ms;
+    a.rev_multi_ms += b.rev_multi_ms;
+    a.rev_multi_passes += b.rev_multi_passes;
     a.lookup_requests += b.lookup_requests;
     a.overflow_retries += b.overflow_retries;
     b = acl_stats_t{};

@@ -2446,6 +2446,240 @@ __global__ __launch_bounds__(kRevLocalThreads) void k_rev_local(DevReverse r, co
     signal_done(done_ctr, done_flag, done_val);
 }
 
+// ------------------------------------------------------- reverse walk, single launch, MANY result slots
+// acl_lookup_resources_multi: one subject against T (type, permission) targets.  k_rev_local's walk with "the result slot" generalised: the
+// level loop, the task list and the first-visit log are the same, what differs is which ops are dead, which states end the walk and which are marked.
+//   * dead ops: `useful` is the OR of the targets' Snapshot::rev_useful rows -- an op into a slot that leads to NO target is OP_DEAD;
+//   * terminal states: a state is marked and never expanded exactly when its slot has no live op left (s_info's count), or at level 50.  For one sink target
+//     that is k_rev_local's sink flag (every parent op of the slot leads outside `useful`); for namespace#view asked WITH pod#view it is not a sink any more;
+//   * marks: every state of a target slot gets its bit, terminal or not (OP_NOMARK seed children too); terminal states of other slots get none;
+//   * rows: all of them stay in `visited` (workgroup-scope atomics; no LDS row, nothing deferred).  After the walk the block copies each target's word range
+//     to the caller's row, counts it, and then clears the logged first visits and the target ranges: `visited` is handed back all zero.
+// The walk is written out here, not shared with k_rev_local: that kernel's registers and LDS stay exactly what they were.
+constexpr uint32_t kRevIsTarget = 0x20000000u;    // task target flag: the child's slot is one of the launch's targets -- always marked
+constexpr uint32_t kRevTaskFlags = kRevTerminal | kRevNoMark | kRevIsTarget;
+constexpr uint32_t kRevMultiLdsTargets = 256;     // target descriptors staged in LDS (the rest are read where they lie)
+
+__global__ __launch_bounds__(kRevLocalThreads) void k_rev_multi(DevReverse r, const uint32_t *__restrict__ sids, uint32_t key, const uint4 *__restrict__ targets,
+                                                                 uint32_t n_targets, uint2 *logs, uint32_t cap, uint32_t *out_bitmaps, uint32_t out_stride,
+                                                                 unsigned long long *out_counts, uint32_t *status, uint32_t *done_ctr, uint32_t *done_flag,
+                                                                 uint32_t done_val, RevUseful useful, RevUseful is_target) {
+    __shared__ RevTaskLds t;
+    __shared__ RevProgLds pl;
+    __shared__ uint32_t s_info[kRevLdsSlots];  // live ops of the slot's program | bit 31: the slot is a target
+    __shared__ uint4 s_tg[kRevMultiLdsTargets];  // {slot, first word of the caller's row, words to copy, words of the caller's row}
+    __shared__ uint32_t s_end, s_wave_tot[kRevLocalThreads / 64], s_stop, s_maxops, s_cnt;
+    __shared__ uint32_t s_nomark[kRevLdsSlots / 32];  // slots whose states carry no visited bit in this launch (nothing to clear afterwards)
+    const uint32_t tid = threadIdx.x, lane = lane_id(), wib = tid >> 6;
+    const uint32_t req = blockIdx.x;
+    uint32_t *__restrict__ visited = r.visited + (size_t)req * r.visited_words;
+    uint2 *const log = logs + (size_t)req * cap;
+    const uint2 *__restrict__ rmeta2 = reinterpret_cast<const uint2 *>(r.rmeta);
+    const uint32_t *__restrict__ redges = r.redges;
+    if (tid == 0) {
+        s_end = 0;
+        s_stop = 0;
+        s_maxops = 0;
+        s_cnt = 0;
+    }
+    if (tid < kRevLdsSlots / 32) s_nomark[tid] = 0;
+    __syncthreads();
+    for (uint32_t i = tid; i < r.nrops; i += kRevLocalThreads) {
+        RevOp o = r.rops[i];
+        if (o.target < kRevLdsSlots && !((useful.w[o.target >> 5] >> (o.target & 31u)) & 1u)) o.flags |= OP_DEAD;
+        pl.ops[i] = o;
+    }
+    for (uint32_t i = tid; i < r.nslots; i += kRevLocalThreads) {
+        const RevProg p = r.rprogs[i];
+        pl.progs[i] = p;
+        pl.slot[i] = make_uint2(r.slot_bit_base[i], r.slot_nobjects[i]);
+        atomicMax(&s_maxops, p.n & ~kRevRemoteBit);
+    }
+    for (uint32_t i = tid; i < min(n_targets, kRevMultiLdsTargets); i += kRevLocalThreads) s_tg[i] = targets[i];
+    const RevProg seed = r.rseeds[key];
+    const uint32_t sid = sids[req];
+    __syncthreads();
+    for (uint32_t i = tid; i < r.nslots; i += kRevLocalThreads) {
+        const RevProg p = pl.progs[i];
+        uint32_t live = 0;
+        for (uint32_t j = 0; j < (p.n & ~kRevRemoteBit); j++) live += (pl.ops[p.first + j].flags & OP_DEAD) ? 0u : 1u;
+        s_info[i] = live | (((is_target.w[i >> 5] >> (i & 31u)) & 1u) << 31);
+    }
+    for (uint32_t i = tid; i < (seed.n & ~kRevRemoteBit); i += kRevLocalThreads) {
+        const RevOp so = r.rops[seed.first + i];
+        if ((so.flags & OP_NOMARK) && !((is_target.w[so.target >> 5] >> (so.target & 31u)) & 1u)) atomicOr(&s_nomark[so.target >> 5], 1u << (so.target & 31u));
+    }
+    // (`visited` is handed over all zero and handed back all zero, private to this block: workgroup scope everywhere -- see k_rev_local)
+    __syncthreads();
+
+    // marks child (slot, id); returns true when it was a first visit of a state that has live parents of its own
+    auto visit = [&](uint32_t id, uint32_t tgt, bool valid) -> bool {
+        const uint32_t slot = tgt & ~kRevTaskFlags;
+        const uint2 si = pl.slot[slot];
+        const bool ok = valid && id < si.y;
+        if (!(tgt & kRevIsTarget)) {
+            if (tgt & kRevTerminal) return false;  // neither expanded nor part of an answer: no bit
+            if (tgt & kRevNoMark) return ok;       // the only producer of this slot's states, each id once: a first visit without asking
+        }
+        bool push = false;
+        const uint32_t bit = si.x + (ok ? id : 0u);
+        uint32_t *w = visited + (bit >> 5);
+        const uint32_t m = 1u << (bit & 31u);
+        if (ok) {
+            if (tgt & kRevTerminal) (void)__hip_atomic_fetch_or(w, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            else push = !(__hip_atomic_fetch_or(w, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) & m);
+        }
+        return push;
+    };
+    auto append = [&](bool push, uint32_t id, uint32_t slot) { log_append(log, cap, &s_end, &s_stop, lane, push, make_uint2(id, slot)); };
+
+    uint32_t lvl_lo = 0, cnt = 1, level = 1;
+    int stop = 0;
+    for (; level <= kMaxLevels; level++) {
+        const uint2 *__restrict__ fin = log + lvl_lo;
+        const uint32_t lvl_hi = lvl_lo + (level > 1 ? cnt : 0u);
+        const uint32_t term_all = level >= kMaxLevels ? kRevTerminal : 0u;
+        const uint32_t W = level == 1 ? (seed.n & ~kRevRemoteBit) : s_maxops;
+        const uint32_t npairs = cnt * W;
+        for (uint32_t pb = 0; pb < npairs; pb += kRevLocalThreads) {
+            // ---- phase A: this thread's (state, op) pair -> at most one task
+            const uint32_t q = pb + tid;
+            uint32_t deg = 0, start = 0, tgt = 0;
+            bool same = false;
+            uint32_t id = 0;
+            if (q < npairs) {
+                const uint32_t e = q / W, j = q - e * W;
+                RevProg p = seed;
+                id = sid;
+                if (level > 1) {
+                    const uint2 en = fin[e];
+                    id = en.x;
+                    p = pl.progs[en.y];
+                }
+                if (j < (p.n & ~kRevRemoteBit) && !(pl.ops[p.first + j].flags & OP_DEAD)) {
+                    const RevOp op = pl.ops[p.first + j];
+                    const uint32_t inf = s_info[op.target];
+                    const bool is_tg = (inf >> 31) != 0u;
+                    bool skip = false;
+                    tgt = op.target | ((inf & 0x7FFFFFFFu) == 0u ? kRevTerminal : 0u) | term_all | (is_tg ? kRevIsTarget : (op.flags & OP_NOMARK) ? kRevNoMark : 0u);
+                    // mark-through (k_rev_local, round 6): a relation nobody asked for whose one parent op is the computed userset of a permission
+                    // that ends the walk -- its row marks that permission's objects directly, one level further on, while that level is inside the limit
+                    if (!(op.flags & OP_PUSH_SAME) && !is_tg && (pl.progs[op.target].n & ~kRevRemoteBit) == 1u) {
+                        const RevOp via = pl.ops[pl.progs[op.target].first];
+                        if ((via.flags & (OP_PUSH_SAME | OP_DEAD)) == OP_PUSH_SAME && (s_info[via.target] & 0x7FFFFFFFu) == 0u) {
+                            if (level + 1u <= kMaxLevels) tgt = via.target | kRevTerminal | ((s_info[via.target] >> 31) ? kRevIsTarget : 0u);
+                            else skip = true;  // (the permission's level lies beyond the limit, and the relation's own states are nobody's answer)
+                        }
+                    }
+                    if (skip) {
+                        // nothing to enumerate for this op
+                    } else if (op.flags & OP_PUSH_SAME) {
+                        same = true;
+                    } else if ((op.flags & OP_WILD) || id < op.nrows) {
+                        const uint2 rd = rmeta2[op.roff_base + ((op.flags & OP_WILD) ? 0u : id)];
+                        if (rd.y - rd.x > kMaxRow) s_stop = 2u;
+                        else if (rd.y > rd.x) {
+                            start = rd.x;
+                            deg = rd.y - rd.x;
+                        }
+                    }
+                }
+            }
+            {  // same-object parents are visited right here (wave-uniform control flow: the append ballots)
+                const bool push = visit(id, tgt, same);
+                append(push, id, tgt & ~kRevTaskFlags);
+            }
+            uint32_t before, total;
+            block_excl_scan<kRevLocalThreads>(deg, lane, wib, s_wave_tot, before, total);
+            if (total) {  // (block-uniform)
+                t.prefix[tid] = before;
+                t.start[tid] = start;
+                t.target[tid] = tgt;
+                if (tid == 0 && total > kRevLocalBudget) s_stop = 1u;
+                __syncthreads();
+                // ---- phase B: the lanes walk the output index space (k_rev_local)
+                if (total <= kRevLocalBudget) {
+                    constexpr int U = 2;
+                    for (uint32_t wb = 0; wb < total; wb += U * kRevLocalThreads) {
+                        uint32_t edge[U], tj[U];
+                        bool valid[U];
+#pragma unroll
+                        for (int k = 0; k < U; k++) {
+                            const uint32_t w = wb + (uint32_t)k * kRevLocalThreads + tid;
+                            valid[k] = w < total;
+                            const uint32_t wv = valid[k] ? w : total - 1;  // inactive lanes shadow the last child: every load stays in range
+                            const uint32_t jt = task_owner<kRevTaskCap>(t.prefix, wv);
+                            tj[k] = jt;
+                            edge[k] = gld(redges, t.start[jt] + (wv - t.prefix[jt]));
+                        }
+                        issue_fence();
+#pragma unroll
+                        for (int k = 0; k < U; k++) {
+                            if (!__ballot(valid[k])) break;  // (wave-uniform)
+                            const uint32_t tg = t.target[tj[k]];
+                            const bool push = visit(edge[k], tg, valid[k]);
+                            append(push, edge[k], tg & ~kRevTaskFlags);
+                        }
+                    }
+                }
+            }
+            stop = __syncthreads_or(s_stop != 0u);
+            if (stop) break;
+        }
+        if (stop) break;
+        const uint32_t end = s_end;
+        if (end == lvl_hi) break;  // nothing produced
+        lvl_lo = lvl_hi;
+        cnt = end - lvl_hi;
+    }
+    if (stop) {
+        // 1: the host answers the group target by target, 2: a row beyond the per-task enumeration limit (`visited` is left dirty: the host zeroes it)
+        if (tid == 0) *status = s_stop;
+        signal_done(done_ctr, done_flag, done_val);
+        return;
+    }
+    // ---- result rows: each target's words (last written by an L2 atomic, or still the zero they were handed over with -- agent-scope loads, as k_rev_local's)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __syncthreads();
+    uint32_t *orow = out_bitmaps + (size_t)req * out_stride;
+    for (uint32_t j = 0; j < n_targets; j++) {
+        const uint4 tg = j < kRevMultiLdsTargets ? s_tg[j] : targets[j];
+        const uint32_t w0 = pl.slot[tg.x].x >> 5;
+        uint32_t c32 = 0;  // (a row holds < 2^31 ids)
+        for (uint32_t i = tid; i < tg.w; i += kRevLocalThreads) {
+            uint32_t v = 0;
+            if (i < tg.z) v = __hip_atomic_load(visited + w0 + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            orow[tg.y + i] = v;
+            c32 += (uint32_t)__popc(v);
+        }
+        if (out_counts) {
+            c32 = wave_last(wave_incl_scan(c32, lane));
+            if (lane == 0 && c32) atomicAdd(&s_cnt, c32);
+            __syncthreads();
+            if (tid == 0) {
+                out_counts[(size_t)req * n_targets + j] = (unsigned long long)s_cnt | ((unsigned long long)min(level, kMaxLevels) << 56);
+                s_cnt = 0;
+            }
+            __syncthreads();
+        }
+    }
+    // ---- leave `visited` all zero: the logged first visits (whole words: they hold this lookup's bits only) and every target's range
+    __syncthreads();  // (every row is copied out before anything in it is cleared)
+    const uint32_t nlog = min(s_end, cap);
+    for (uint32_t i = tid; i < nlog; i += kRevLocalThreads) {
+        const uint2 en = log[i];
+        if (s_nomark[en.y >> 5] >> (en.y & 31u) & 1u) continue;  // (never marked)
+        visited[(pl.slot[en.y].x + en.x) >> 5] = 0u;
+    }
+    for (uint32_t j = 0; j < n_targets; j++) {
+        const uint32_t slot = j < kRevMultiLdsTargets ? s_tg[j].x : targets[j].x;
+        const uint2 si = pl.slot[slot];
+        const uint32_t rw = (si.y + 31u) >> 5;
+        for (uint32_t i = tid; i < rw; i += kRevLocalThreads) visited[(si.x >> 5) + i] = 0u;
+    }
+    signal_done(done_ctr, done_flag, done_val);
+}
+
 // The deferred rows of k_rev_local (see RevDefer): blockIdx.y = lookup, the launch's waves take its tasks round-robin and a wave's lanes read consecutive ids
 // of a reverse row.  An id's mark is its byte of the lookup's byte map (RevDefer::bytemap): a plain store, whichever block and XCD makes it.
 __global__ __launch_bounds__(256) void k_rev_terminal(DevReverse r, uint32_t target_slot, RevDefer dfr) {
@@ -2830,6 +3064,14 @@ void launch_rev_local(hipStream_t s, const DevReverse &r, const uint32_t *sids, 
     const uint32_t slices = std::max(1u, std::min(per, (out_stride + 1023u) / 1024u));
     hipLaunchKernelGGL(k_rev_rows, dim3(slices, n), dim3(256), 0, s, r, target_slot, n, out_bitmaps, out_stride, copy_words, (unsigned long long *)out_counts,
                        (unsigned long long *)big->counts, dfr, done_ctr, done_flag, done_val);
+}
+void launch_rev_multi(hipStream_t s, const DevReverse &r, const uint32_t *sids, uint32_t n, uint32_t key, const RevMultiTarget *targets, uint32_t n_targets, void *logs,
+                      uint32_t cap, uint32_t *out_bitmaps, uint32_t out_stride, uint64_t *out_counts, uint32_t *status, const RevUseful &useful, const RevUseful &is_target,
+                      uint32_t *done_ctr, uint32_t *done_flag, uint32_t done_val) {
+    if (!n || !n_targets) return;
+    static_assert(sizeof(RevMultiTarget) == sizeof(uint4), "k_rev_multi reads a target as one 16-byte load");
+    hipLaunchKernelGGL(k_rev_multi, dim3(n), dim3(kRevLocalThreads), 0, s, r, sids, key, reinterpret_cast<const uint4 *>(targets), n_targets, (uint2 *)logs, cap, out_bitmaps,
+                       out_stride, (unsigned long long *)out_counts, status, done_ctr, done_flag, done_val, useful, is_target);
 }
 static uint32_t import_blocks(uint32_t n) {  // ~one 1024-entry chunk of input per wave, at most 256 blocks
     const uint32_t b = (n + 4095) / 4096;

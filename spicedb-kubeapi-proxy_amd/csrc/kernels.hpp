@@ -175,6 +175,16 @@ void launch_rev_local(hipStream_t s, const DevReverse &r, const uint32_t *sids, 
                       uint32_t *done_ctr = nullptr, uint32_t *done_flag = nullptr, uint32_t done_val = 0 /* as launch_check_local: the last block stores done_val into the pinned
                       word done_flag behind a system-scope release of every block's rows, counts and status */,
                       const RevBigRows *big = nullptr, const RevUseful *useful = nullptr /* NULL: every slot */);
+// single-launch LookupResources against MANY result slots (kernels.hip k_rev_multi): block b walks lookup b once and hands back one row per target --
+// targets[j].copy_words words of slot targets[j].slot's rows at out_bitmaps + b * out_stride + targets[j].out_off, zero up to out_words; out_counts[b * n_targets + j] =
+// ids in that row | reverse levels walked << 56.  `targets` is read by the device (device or pinned host memory).  useful: the OR of the targets'
+// Snapshot::rev_useful rows; is_target: bit of every target slot.  r.visited all zero before and after; logs, cap, status and the completion word as launch_rev_local.
+struct RevMultiTarget {
+    uint32_t slot, out_off, copy_words, out_words;
+};
+void launch_rev_multi(hipStream_t s, const DevReverse &r, const uint32_t *sids, uint32_t n, uint32_t key, const RevMultiTarget *targets, uint32_t n_targets, void *logs,
+                      uint32_t cap, uint32_t *out_bitmaps, uint32_t out_stride, uint64_t *out_counts, uint32_t *status, const RevUseful &useful, const RevUseful &is_target,
+                      uint32_t *done_ctr = nullptr, uint32_t *done_flag = nullptr, uint32_t done_val = 0);
 // single-launch LookupSubjects (kernels.hip k_subj_local): block b walks the forward programs from resource rids[b] of `target_slot` and marks the ids of the
 // subjects of `key` it reaches in rows + b * row_words (device memory; zeroed by the caller when the row does not fit the block's LDS: row_words * 4 >
 // kRevLdsRowBytes); flags_out[b] = 1 when a `T:*` row was reached.  visited: [n][g.visited_words] zeroed by the caller; logs: [n][cap] 8-byte entries.

@@ -253,7 +253,20 @@ struct PassCtx {
     DevArray<uint32_t> d_big_meta;  // [2 m]: task counts, levels
     size_t big_counts_zeroed = 0;   // leading accumulators known to be zero (k_rev_rows re-arms what it used)
     bool direct_tripped = false;   // this context's last walk gave up on the direct task lists (kOverflowDirect): its redo is not a frontier overflow (walk_outcome)
-    size_t visited_zero_words = 0;  // leading words of d_visited known to be all zero: k_rev_local takes `visited` zeroed and hands it back zeroed (kernels.hip)
+    size_t visited_zero_words = 0;  // leading words of d_visited known to be all zero: k_rev_local and k_rev_multi take `visited` zeroed and hand it back zeroed (kernels.hip)
+    // d_visited holds `words` words, all zero once the stream gets there: one memset per context and size, not one per call.  Whoever leaves marks behind (a
+    // block that gave up, the level loop) sets visited_zero_words = 0.
+    hipError_t visited_zeroed(size_t words) {
+        if (d_visited.n < words || !d_visited.p) {
+            hipError_t e = d_visited.ensure(words);
+            if (e != hipSuccess) return e;
+            visited_zero_words = 0;  // (fresh memory)
+        }
+        if (visited_zero_words >= words) return hipSuccess;
+        hipError_t e = hipMemsetAsync(d_visited.p, 0, words * 4, stream);
+        if (e == hipSuccess) visited_zero_words = words;
+        return e;
+    }
     DevArray<uint4> d_nodes;     // schemas with `&` / `-`: the CombineNode records of a pass (plan.hpp)
     DevArray<uint64_t> d_dedup;  // duplicate-merging passes only (check_pass): open-addressing table over one level's entries
     PinnedBuf h_in, h_out;  // staging for pageable caller buffers
@@ -595,6 +608,23 @@ void relationship_line(const Schema &sc, uint16_t rtype, const std::string &rid,
 // Explain denial (engine_denial.cpp): the host half, a pure function of the schema -- the grants that the states recs[0, n) = {object id, slot | level << 16}
 // hold for a subject of class (stype, srel: kNoRelation = none), deduplicated at their least level and sorted by (level, rtype, relation, rid)
 void denial_grants(const Schema &sc, const uint2 *recs, size_t n, int stype, int srel, std::vector<acl_grant_t> *out);
+// What the two single-launch reverse passes share (engine_lookup.cpp; lookup_pass_local there, multi_pass_local in engine_lookup_multi.cpp): the logs' capacity
+// per lookup, the pinned staging [flag (64 B)] [counts ncounts x 8] [rows row_bytes] in c->h_out, the completion word, the wait and what the status word means.
+struct RevPass {
+    uint32_t cap = 0;                // 8-byte log entries per lookup, carved from the context's frontier buffer 0 (16 B per entry there)
+    bool spin = false;               // the caller polls the completion word: hand the kernel done_flag / done_val and c->d_done
+    uint32_t done_val = 0;
+    size_t ncounts = 0, rows_off = 0;
+    uint32_t *flag = nullptr;        // host views of the staging: the status word (flag[15]: the completion word), ...
+    const uint32_t *h_rows = nullptr;  // ... and the rows
+    uint32_t *d_status = nullptr, *d_done_flag = nullptr, *d_rows = nullptr;  // the device's pointers to the same
+    uint64_t *d_counts = nullptr;
+};
+// rev_pass_begin: kTakeLevelLoop when the logs would be too small; else the staging, zeroed where the kernel reports.  The caller launches between ev_begin and ev_end.
+// rev_pass_end: waits (spin or stream), collects the events, maps the status word -- 2: ACL_ERR_RESOURCE_EXHAUSTED, 1: overflow_retries++ and kTakeLevelLoop --
+// and unpacks count | levels << 56 into counts (may be NULL) and stats.levels_last.
+int rev_pass_begin(acl_engine *h, PassCtx *c, size_t m, size_t ncounts, size_t row_bytes, bool may_spin, RevPass *p);
+int rev_pass_end(PassCtx *c, const RevPass &p, uint64_t *counts);
 int lookup_candidate_error(acl_engine *h, int32_t code, uint32_t id, uint32_t sid);  // fails a LookupResources call with a candidate's Check error (lookups.go:75-83)
 int lookup_batch(acl_engine *h, PassCtx *c, int rtype, int perm, int stype, int srel, const uint32_t *sids, size_t n, uint32_t *bitmaps, size_t words,
                  uint64_t *counts, uint32_t *d_dst = nullptr /* watch sets: the rows stay on the device (engine_lookup.cpp) */, size_t dstride = 0);

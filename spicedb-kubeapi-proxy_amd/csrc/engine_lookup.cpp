@@ -5,40 +5,68 @@
 
 namespace aclint {
 
+// The two halves of a single-launch reverse pass around its launch (RevPass, engine_internal.hpp)
+int rev_pass_begin(acl_engine *h, PassCtx *c, size_t m, size_t ncounts, size_t row_bytes, bool may_spin, RevPass *p) {
+    uint64_t cap64 = std::min<uint64_t>(c->frontier_entries * 2 / std::max<size_t>(m, 1), 1u << 22);
+    if (h->local_cap_limit) cap64 = std::min<uint64_t>(cap64, h->local_cap_limit);
+    if (cap64 < 64 || m > 0x7FFFFFFFull) return kTakeLevelLoop;
+    p->cap = (uint32_t)cap64;
+    p->ncounts = ncounts;
+    p->rows_off = 64 + ncounts * sizeof(uint64_t);
+    HIP_TRY(c->h_out.ensure(p->rows_off + row_bytes));
+    p->flag = (uint32_t *)c->h_out.p;
+    p->h_rows = (const uint32_t *)((const char *)c->h_out.p + p->rows_off);
+    p->flag[0] = 0;
+    p->flag[15] = 0;
+    p->d_status = (uint32_t *)c->h_out.dp;
+    p->d_counts = (uint64_t *)((char *)c->h_out.dp + 64);
+    p->d_rows = (uint32_t *)((char *)c->h_out.dp + p->rows_off);
+    p->spin = may_spin && m <= h->spin_max && !c->timing;
+    p->done_val = p->spin ? next_done_val(c) : 0u;
+    p->d_done_flag = p->spin ? p->d_status + 15 : nullptr;
+    return ACL_OK;
+}
+
+int rev_pass_end(PassCtx *c, const RevPass &p, uint64_t *counts) {
+    // (the proxy's shape is ONE LookupResources per list request, lookups.go:65: the caller spins on the completion word -- spin_for)
+    if (!(p.spin && spin_for(p.flag + 15, p.done_val))) HIP_TRY(hipStreamSynchronize(c->stream));
+    ev_collect(c);
+    if (*p.flag == 2) return fail(ACL_ERR_RESOURCE_EXHAUSTED, "a relationship row exceeds the per-task enumeration limit");
+    if (*p.flag) {
+        c->stats.overflow_retries++;
+        return kTakeLevelLoop;
+    }
+    const uint64_t *h_counts = (const uint64_t *)((const char *)c->h_out.p + 64);
+    uint32_t levels = 0;
+    for (size_t k = 0; k < p.ncounts; k++) {  // count | levels walked << 56
+        levels = std::max<uint32_t>(levels, (uint32_t)(h_counts[k] >> 56));
+        if (counts) counts[k] = h_counts[k] & 0x00FFFFFFFFFFFFFFull;
+    }
+    c->stats.levels_last = levels;
+    return ACL_OK;
+}
+
 // Single-launch LookupResources over m subjects already staged in c->h_in (pinned).  Result rows go to `bitmaps` directly when the
 // caller's buffer is pinned (acl_host_alloc), else through the context's pinned staging.  kTakeLevelLoop: a block outgrew its share.
 // d_dst != NULL (watch sets, engine_watchset.cpp): the rows stay on the device, row i at d_dst + i * dstride (dstride >= cw words, the words behind cw
 // zeroed); `bitmaps` is not touched.
 static int lookup_pass_local(acl_engine *h, PassCtx *c, const DevReverse &r, uint32_t key, uint32_t target, size_t m, uint32_t *bitmaps, size_t words, size_t cw,
                              uint64_t *counts, uint32_t *d_dst = nullptr, size_t dstride = 0) {
-    // private frontier regions: 8-byte entries carved from the context's two frontier buffers (16 B per entry there)
-    uint64_t cap64 = std::min<uint64_t>(c->frontier_entries * 2 / std::max<size_t>(m, 1), 1u << 22);
-    if (h->local_cap_limit) cap64 = std::min<uint64_t>(cap64, h->local_cap_limit);
-    if (cap64 < 64 || words > 0xFFFFFFFFull || m > 0x7FFFFFFFull || r.nslots > kRevLdsSlots || r.nrops > kRevLdsOps) return kTakeLevelLoop;
+    if (words > 0xFFFFFFFFull || r.nslots > kRevLdsSlots || r.nrops > kRevLdsOps) return kTakeLevelLoop;
     const bool direct = !d_dst && words && h->is_pinned(bitmaps, m * words * sizeof(uint32_t));
     const size_t ostride = d_dst ? dstride : direct ? words : cw;
-    // staging: [flag (64 B)] [counts m x 8] [rows m x cw x 4]
-    const size_t rows_off = 64 + m * sizeof(uint64_t);
-    HIP_TRY(c->h_out.ensure(rows_off + ((direct || d_dst) ? 0 : m * std::max<size_t>(cw, 1) * 4)));
-    uint32_t *flag = (uint32_t *)c->h_out.p;
-    uint64_t *h_counts = (uint64_t *)((char *)c->h_out.p + 64);
-    uint32_t *h_rows = (uint32_t *)((char *)c->h_out.p + rows_off);
-    *flag = 0;
-    flag[15] = 0;
-    void *d_sids = nullptr, *d_out = nullptr, *d_rows = nullptr;
-    HIP_TRY(hipHostGetDevicePointer(&d_sids, c->h_in.p, 0));
-    HIP_TRY(hipHostGetDevicePointer(&d_out, c->h_out.p, 0));
     // Result rows: written by the kernel straight into host memory (each block as it finishes), or -- rev_rows_device, A/B knob
     // ACL_REV_ROWS=device -- into a device buffer that one DMA copy brings over afterwards.
     const bool via_device = h->rev_rows_device && ostride && !d_dst;
-    const bool spin = m <= h->spin_max && !c->timing && !via_device && !d_dst;
-    const uint32_t done_val = spin ? next_done_val(c) : 0u;
+    RevPass p;
+    int rc = rev_pass_begin(h, c, m, m, (direct || d_dst) ? 0 : m * std::max<size_t>(cw, 1) * 4, !via_device && !d_dst, &p);
+    if (rc) return rc;
+    void *d_rows = p.d_rows;
     if (d_dst) d_rows = d_dst;
     else if (via_device) {
         HIP_TRY(c->d_rows.ensure(m * ostride));
         d_rows = c->d_rows.p;
     } else if (direct) HIP_TRY(hipHostGetDevicePointer(&d_rows, bitmaps, 0));
-    else d_rows = (char *)d_out + rows_off;
     // Rows that do not fit the block's LDS (a type of more than 1 M objects; reference pkg/authz/lookups.go:49-65 asks for the whole type): the heavy terminal
     // rows are deferred to a chip-wide launch and the rows are copied / counted / cleared by a third one (kernels.hip RevDefer; ACL_REV_BIG_ROWS=0: one block
     // does it all, as in round 5 -- A/B)
@@ -77,14 +105,13 @@ static int lookup_pass_local(acl_engine *h, PassCtx *c, const DevReverse &r, uin
     RevUseful useful;  // (the slots that can lead to the result slot: everything else is dead weight for this lookup)
     const bool pruned = h->rev_sink_on && h->shard.world == 1 && h->snap.rev_useful.size() >= ((size_t)target + 1) * kRevUsefulWords;
     if (pruned) std::memcpy(useful.w, h->snap.rev_useful.data() + (size_t)target * kRevUsefulWords, sizeof(useful.w));
-    launch_rev_local(c->stream, r, (const uint32_t *)d_sids, (uint32_t)m, key, target | (sink ? kRevTargetSink : 0u), c->d_fbuf[0].p, c->d_fbuf[1].p, (uint32_t)cap64, (uint32_t *)d_rows, (uint32_t)ostride,
-                     (uint32_t)cw, (uint64_t *)((char *)d_out + 64), (uint32_t *)d_out, lds_row_words,
-                     (spin || use_big) ? c->d_done.p : nullptr, spin ? (uint32_t *)d_out + 15 : nullptr, done_val, use_big ? &big : nullptr, pruned ? &useful : nullptr);
+    launch_rev_local(c->stream, r, (const uint32_t *)c->h_in.dp, (uint32_t)m, key, target | (sink ? kRevTargetSink : 0u), c->d_fbuf[0].p, p.cap, (uint32_t *)d_rows, (uint32_t)ostride,
+                     (uint32_t)cw, p.d_counts, p.d_status, lds_row_words, (p.spin || use_big) ? c->d_done.p : nullptr, p.d_done_flag, p.done_val, use_big ? &big : nullptr,
+                     pruned ? &useful : nullptr);
     ev_end(c);
-    if (via_device) HIP_TRY(hipMemcpyAsync(direct ? (void *)bitmaps : (void *)h_rows, c->d_rows.p, m * ostride * 4, hipMemcpyDeviceToHost, c->stream));
-    // (the proxy's shape is ONE LookupResources per list request, lookups.go:65: the caller spins on the completion word -- spin_for)
-    if (!(spin && spin_for(flag + 15, done_val))) HIP_TRY(hipStreamSynchronize(c->stream));
-    ev_collect(c);
+    if (via_device) HIP_TRY(hipMemcpyAsync(direct ? (void *)bitmaps : (void *)p.h_rows, c->d_rows.p, m * ostride * 4, hipMemcpyDeviceToHost, c->stream));
+    rc = rev_pass_end(c, p, counts);
+    const uint32_t *flag = p.flag;
     if (*flag && use_big) c->big_bytes_zeroed = 0;  // (a block gave up half-way: marks of rows nobody folded may be left)
     static const bool kDebugRev = getenv("ACL_DEBUG_REV") != nullptr;  // (stderr: what the walk deferred -- tools/lookup_big_probe.py)
     if (kDebugRev && use_big) {
@@ -99,22 +126,12 @@ static int lookup_pass_local(acl_engine *h, PassCtx *c, const DevReverse &r, uin
                     std::min<size_t>(meta[i], tk.size()), meta[m + i], *flag);
         }
     }
-    if (*flag == 2) return fail(ACL_ERR_RESOURCE_EXHAUSTED, "a relationship row exceeds the per-task enumeration limit");
-    if (*flag) {
-        c->stats.overflow_retries++;
-        return kTakeLevelLoop;
+    if (rc) return rc;
+    for (size_t i = 0; i < m && !direct && !d_dst; i++) {
+        uint32_t *dst = bitmaps + i * words;
+        if (cw) std::memcpy(dst, p.h_rows + i * cw, cw * 4);
+        std::fill(dst + cw, dst + words, 0u);
     }
-    uint32_t levels = 0;
-    for (size_t i = 0; i < m; i++) {  // count | levels walked << 56
-        levels = std::max<uint32_t>(levels, (uint32_t)(h_counts[i] >> 56));
-        if (counts) counts[i] = h_counts[i] & 0x00FFFFFFFFFFFFFFull;
-        if (!direct && !d_dst) {
-            uint32_t *dst = bitmaps + i * words;
-            if (cw) std::memcpy(dst, h_rows + i * cw, cw * 4);
-            std::fill(dst + cw, dst + words, 0u);
-        }
-    }
-    c->stats.levels_last = levels;
     c->stats.rev_local_passes++;
     c->stats.lookup_requests += m;
     return ACL_OK;
@@ -202,10 +219,8 @@ int lookup_batch(acl_engine *h, PassCtx *c, int rtype, int perm, int stype, int 
     const size_t group = std::max<size_t>(1, std::min<size_t>(n ? n : 1, ((size_t)1 << 28) / vwords));  // <= 1 GiB of visited bits
     for (size_t b = 0; b < n; b += group) {
         const size_t m = std::min(group, n - b);
-        if (c->d_visited.n < m * vwords || !c->d_visited.p) {
-            HIP_TRY(c->d_visited.ensure(m * vwords));
-            c->visited_zero_words = 0;  // (fresh memory)
-        }
+        // (the single-launch walk takes the visited rows all zero and leaves them all zero -- every block clears what it marked; the level loop zeroes them itself)
+        HIP_TRY(h->rev_local ? c->visited_zeroed(m * vwords) : c->d_visited.ensure(m * vwords));
         HIP_TRY(c->d_sids.ensure(m));
         HIP_TRY(c->h_in.ensure(m * sizeof(uint32_t)));
         std::memcpy(c->h_in.p, sids + b, m * sizeof(uint32_t));
@@ -215,12 +230,6 @@ int lookup_batch(acl_engine *h, PassCtx *c, int rtype, int perm, int stype, int 
         // memset, no D2H copies.  A lookup that outgrows its block (private frontier region, children per level) sends the group to the
         // level loop below, which spreads it over the chip.
         if (h->rev_local) {
-            // the single-launch walk takes the visited rows all zero and leaves them all zero (every block clears what it marked): one memset
-            // per context and size, not one per call
-            if (c->visited_zero_words < m * vwords) {
-                HIP_TRY(hipMemsetAsync(c->d_visited.p, 0, m * vwords * 4, c->stream));
-                c->visited_zero_words = m * vwords;
-            }
             rc = lookup_pass_local(h, c, r, key, target, m, d_dst ? nullptr : bitmaps + b * words, words, cw, counts ? counts + b : nullptr, d_dst ? d_dst + b * dstride : nullptr,
                                    dstride);
             if (rc == ACL_OK) continue;

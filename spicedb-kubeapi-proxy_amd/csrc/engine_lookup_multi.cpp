@@ -18,45 +18,25 @@ struct MultiTargets {
 // The one launch over m subjects already in `sids` (host).  Rows and counts in the caller's layout.  kTakeLevelLoop: a block gave up, or the group does not fit.
 int multi_pass_local(acl_engine *h, PassCtx *c, const DevReverse &r, uint32_t key, const MultiTargets &mt, const uint32_t *sids, size_t m, uint32_t *bitmaps, uint64_t *counts) {
     const size_t T = mt.dev.size();
-    uint64_t cap64 = std::min<uint64_t>(c->frontier_entries * 2 / std::max<size_t>(m, 1), 1u << 22);
-    if (h->local_cap_limit) cap64 = std::min<uint64_t>(cap64, h->local_cap_limit);
-    if (cap64 < 64 || mt.stride > 0xFFFFFFFFull || m > 0x7FFFFFFFull || T > 0xFFFFFFFFull) return kTakeLevelLoop;
+    if (mt.stride > 0xFFFFFFFFull || T > 0xFFFFFFFFull) return kTakeLevelLoop;
     const bool direct = mt.stride && h->is_pinned(bitmaps, m * mt.stride * sizeof(uint32_t));
-    // pinned input: [sids m x 4, padded to 16] [targets T x 16]; pinned staging: [flag (64 B)] [counts m x T x 8] [rows m x stride x 4]
+    RevPass p;  // (rows in the staging: m x stride words)
+    int rc = rev_pass_begin(h, c, m, m * T, direct ? 0 : m * std::max<size_t>(mt.stride, 1) * 4, true, &p);
+    if (rc) return rc;
+    // pinned input: [sids m x 4, padded to 16] [targets T x 16]
     const size_t tg_off = (m * sizeof(uint32_t) + 15) / 16 * 16;
     HIP_TRY(c->h_in.ensure(tg_off + T * sizeof(RevMultiTarget)));
     std::memcpy(c->h_in.p, sids, m * sizeof(uint32_t));
     std::memcpy((char *)c->h_in.p + tg_off, mt.dev.data(), T * sizeof(RevMultiTarget));
-    const size_t rows_off = 64 + m * T * sizeof(uint64_t);
-    HIP_TRY(c->h_out.ensure(rows_off + (direct ? 0 : m * std::max<size_t>(mt.stride, 1) * 4)));
-    uint32_t *flag = (uint32_t *)c->h_out.p;
-    const uint64_t *h_counts = (const uint64_t *)((char *)c->h_out.p + 64);
-    *flag = 0;
-    flag[15] = 0;
-    void *d_rows = nullptr;
+    void *d_rows = p.d_rows;
     if (direct) HIP_TRY(hipHostGetDevicePointer(&d_rows, bitmaps, 0));
-    else d_rows = (char *)c->h_out.dp + rows_off;
-    const bool spin = m <= h->spin_max && !c->timing;
-    const uint32_t done_val = spin ? next_done_val(c) : 0u;
     ev_begin(c, 6);
     launch_rev_multi(c->stream, r, (const uint32_t *)c->h_in.dp, (uint32_t)m, key, (const RevMultiTarget *)((const char *)c->h_in.dp + tg_off), (uint32_t)T, c->d_fbuf[0].p,
-                     (uint32_t)cap64, (uint32_t *)d_rows, (uint32_t)mt.stride, (uint64_t *)((char *)c->h_out.dp + 64), (uint32_t *)c->h_out.dp, mt.useful, mt.is_target,
-                     spin ? c->d_done.p : nullptr, spin ? (uint32_t *)c->h_out.dp + 15 : nullptr, done_val);
+                     p.cap, (uint32_t *)d_rows, (uint32_t)mt.stride, p.d_counts, p.d_status, mt.useful, mt.is_target, p.spin ? c->d_done.p : nullptr, p.d_done_flag, p.done_val);
     ev_end(c);
-    if (!(spin && spin_for(flag + 15, done_val))) HIP_TRY(hipStreamSynchronize(c->stream));
-    ev_collect(c);
-    if (*flag == 2) return fail(ACL_ERR_RESOURCE_EXHAUSTED, "a relationship row exceeds the per-task enumeration limit");
-    if (*flag) {
-        c->stats.overflow_retries++;
-        return kTakeLevelLoop;
-    }
-    uint32_t levels = 0;
-    for (size_t k = 0; k < m * T; k++) {  // count | levels walked << 56
-        levels = std::max<uint32_t>(levels, (uint32_t)(h_counts[k] >> 56));
-        if (counts) counts[k] = h_counts[k] & 0x00FFFFFFFFFFFFFFull;
-    }
-    if (!direct && mt.stride) std::memcpy(bitmaps, (const char *)c->h_out.p + rows_off, m * mt.stride * 4);
-    c->stats.levels_last = levels;
+    rc = rev_pass_end(c, p, counts);
+    if (rc) return rc;
+    if (!direct && mt.stride) std::memcpy(bitmaps, p.h_rows, m * mt.stride * 4);
     c->stats.rev_multi_passes++;
     c->stats.lookup_requests += m * T;
     return ACL_OK;
@@ -145,14 +125,7 @@ int lookup_multi(acl_engine *h, PassCtx *c, const acl_target_t *targets, size_t 
         const size_t m = std::min(group, n - b);
         rc = check_opts(c->opts);
         if (rc) return rc;
-        if (c->d_visited.n < m * vwords || !c->d_visited.p) {
-            HIP_TRY(c->d_visited.ensure(m * vwords));
-            c->visited_zero_words = 0;  // (fresh memory)
-        }
-        if (c->visited_zero_words < m * vwords) {  // (the kernel takes the rows all zero and hands them back all zero: lookup_batch's contract)
-            HIP_TRY(hipMemsetAsync(c->d_visited.p, 0, m * vwords * 4, c->stream));
-            c->visited_zero_words = m * vwords;
-        }
+        HIP_TRY(c->visited_zeroed(m * vwords));  // (the kernel takes the rows all zero and hands them back all zero: lookup_batch's contract)
         const DevReverse r = h->dev_reverse(c, (uint32_t)vwords);
         rc = multi_pass_local(h, c, r, key, mt, sids + b, m, bitmaps + b * mt.stride, counts ? counts + b * T : nullptr);
         if (rc == ACL_OK) {

@@ -146,7 +146,7 @@ void launch_resolve_gathered(hipStream_t s, const DevGraph &g, const uint4 *node
 void launch_rev_expand(hipStream_t s, const DevReverse &r, const DevFrontier &f, uint32_t iter, uint32_t phase = REV_FUSED,
                        const DevShard &sh = DevShard());
 // single-launch LookupResources: block b walks lookup b (subject sids[b] of class `key`) through every reverse level; visited rows r.visited
-// (zeroed by the kernel), private frontier regions of `cap` 8-byte entries per block in buf0 / buf1; the result slot's first `copy_words`
+// (all zero before and after), a private log of `cap` 8-byte entries per block in `logs`; the result slot's first `copy_words`
 // words go to out_bitmaps + b * out_stride (device or pinned host memory; the rest of the row is zeroed), the id counts to out_counts.
 // *status != 0 afterwards (the caller zeroes it; it may live in pinned host memory): redo on the level loop (1) / a row beyond the enumeration limit (2);
 // out_counts[b] = ids in the row | reverse levels walked << 56
@@ -169,7 +169,7 @@ struct RevUseful {  // the slots a lookup has to walk (Snapshot::rev_useful's ro
 };
 // target_slot | kRevTargetSink: nothing above the result slot leads back into it (Snapshot::rev_sink) -- its states end the walk instead of being expanded
 constexpr uint32_t kRevTargetSink = 0x80000000u;
-void launch_rev_local(hipStream_t s, const DevReverse &r, const uint32_t *sids, uint32_t n, uint32_t key, uint32_t target_slot, void *buf0, void *buf1,
+void launch_rev_local(hipStream_t s, const DevReverse &r, const uint32_t *sids, uint32_t n, uint32_t key, uint32_t target_slot, void *logs,
                       uint32_t cap, uint32_t *out_bitmaps, uint32_t out_stride, uint32_t copy_words, uint64_t *out_counts, uint32_t *status,
                       uint32_t lds_row_words /* words covering the result slot's id space: kept in LDS when <= kRevLdsRowBytes, else (or 0) in r.visited */,
                       uint32_t *done_ctr = nullptr, uint32_t *done_flag = nullptr, uint32_t done_val = 0 /* as launch_check_local: the last block stores done_val into the pinned

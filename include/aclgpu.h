@@ -323,6 +323,48 @@ int acl_lookup_subjects(acl_engine_t *h, const char *resource_type, const char *
                         const char *subject_relation, const acl_call_opts_t *opts, uint32_t **bitmap_out, size_t *words_out, uint64_t *count_out,
                         int *wildcard_out, uint32_t **excluded_out);
 
+/* ---- paged lookups: limit and cursor of LookupResources / LookupSubjects, served from rows kept in device memory ----
+ * Open walks ONCE on the current snapshot and keeps the n rows on the device: row i is bit for bit what acl_lookup_resources_batch (open) or
+ * acl_lookup_subjects_batch with excluded_out == NULL (open_subjects) answers for ids[i] on that snapshot, and fails as that call fails (a depth error of a
+ * permission with `-`, `&` or `.all()` unless ACL_FLAG_LENIENT_LOOKUP; such rows are confirmed on the host and uploaded once, the rows of any other
+ * permission never cross PCIe).  n == 0: a valid cursor without rows.  A subject cursor's flags are that call's flags_out (ACL_SUBJECTS_WILDCARD); its rows
+ * hold the subjects that relationships name, and the `excluded` row of a wildcard answer is NOT paged (ask acl_lookup_subjects_batch for it).
+ * The cursor is PINNED: writes, deletes, expiries and growth of the type after the open change neither its rows nor its counts nor its revision (the
+ * snapshot's at the open), so every page of one enumeration comes from one snapshot.  A schema reload expires it: every call but close then answers
+ * ACL_ERR_FAILED_PRECONDITION.
+ * pages: request q is answered with the ascending ids of row reqs[q].row that are > after_id (ACL_PAGE_FROM_START: from id 0), at most `limit` of them, written
+ * at ids_out + (limit_0 + ... + limit_{q-1}); n_out[q] = how many, more_out[q] = 1 iff a larger id remains in the row; the words of ids_out behind n_out[q] are
+ * left alone.  after_id need not be set in the row nor lie inside the type.  Requests may name a row repeatedly and in any order.  Only ids cross PCIe: the
+ * written prefix of ids_out, n_out and more_out.  ACL_ERR_INVALID_ARGUMENT: limit == 0, reserved != 0, row >= n, ids_cap below the sum of the limits, a sum
+ * above 2^28; m == 0: ACL_OK, nothing written.
+ * page_names: one request plus the ids' names, packed as acl_bitmap_names packs them (ends[k] = end of name k in buf; cap >= 1024; ids_out and ends hold
+ * `limit` entries; an anonymous id: an empty name).  Names that do not fit cut the page short: *more_out = 1, continue behind the last id returned.  A name
+ * is only returned while the id is sure to carry it still: once ANY id of the engine has been recycled since the open (acl_stats_t.ids_recycled moved)
+ * the call answers ACL_ERR_FAILED_PRECONDITION ("expired: reopen"); the id forms keep answering.
+ * Arguments are validated before the engine's mode is looked at (NULL pointer: ACL_ERR_INVALID_ARGUMENT; unknown type, permission or relation:
+ * ACL_ERR_FAILED_PRECONDITION); then a store-only engine: ACL_ERR_UNAVAILABLE, a sharded engine: ACL_ERR_FAILED_PRECONDITION.  A pointer that is not an open
+ * cursor of this engine: ACL_ERR_INVALID_ARGUMENT.  The open cursors of an engine hold at most 1 GiB of rows together: beyond, open answers
+ * ACL_ERR_RESOURCE_EXHAUSTED.  acl_close frees the cursors still open.  On an engine with several replicas the rows live on ONE device and pages run there.
+ * Calls on one cursor serialise; no call on a cursor may be started after its close. */
+typedef struct acl_lookup_cursor acl_lookup_cursor_t;
+#define ACL_PAGE_FROM_START 0xFFFFFFFFu /* after_id: start before id 0 */
+typedef struct { uint32_t row, after_id, limit, reserved; } acl_page_req_t; /* 16 bytes */
+int acl_lookup_cursor_open(acl_engine_t *h, int rtype, int permission, int stype, int srel /* -1 none */, const uint32_t *subject_ids, size_t n,
+                           const acl_call_opts_t *opts, acl_lookup_cursor_t **out);
+int acl_lookup_cursor_open_subjects(acl_engine_t *h, int rtype, int permission, int stype, int srel /* -1 none */, const uint32_t *resource_ids, size_t n,
+                                    const acl_call_opts_t *opts, acl_lookup_cursor_t **out);
+/* row_type: the type the rows' ids belong to (rtype; stype for a subject cursor); counts_out / flags_out: n entries, may be NULL (flags: 0 for a resource cursor) */
+int acl_lookup_cursor_info(acl_engine_t *h, acl_lookup_cursor_t *cur, uint64_t *revision_out, uint32_t *n_rows_out, uint32_t *row_type_out,
+                           uint64_t *counts_out, uint8_t *flags_out);
+int acl_lookup_cursor_pages(acl_engine_t *h, acl_lookup_cursor_t *cur, const acl_page_req_t *reqs, size_t m, uint32_t *ids_out, size_t ids_cap,
+                            uint32_t *n_out, uint8_t *more_out, const acl_call_opts_t *opts);
+int acl_lookup_cursor_page_names(acl_engine_t *h, acl_lookup_cursor_t *cur, uint32_t row, uint32_t after_id, uint32_t limit, uint32_t *ids_out,
+                                 char *buf, size_t cap, uint32_t *ends, uint32_t *n_out, uint8_t *more_out);
+int acl_lookup_cursor_close(acl_engine_t *h, acl_lookup_cursor_t *cur);
+/* since open / the last acl_stats_reset: kernel launches of acl_lookup_cursor_pages / _page_names (two per call: plan + pages, whatever m is) and their
+ * HIP-event time (needs timing on).  Either pointer may be NULL. */
+int acl_lookup_cursor_stats(acl_engine_t *h, uint64_t *page_launches_out, double *page_ms_out);
+
 /* ---- Explain: Check + a witness, the chain of stored relationships that grants the item ----
  * perm_out / err_out per item are exactly what acl_check_bulk_ids answers for the same items on the same snapshot (the Check and the walk run inside one
  * evaluation).  An item that answers HAS_PERMISSION on a permission built from `+`, `->` and references alone also gets a witness: hops

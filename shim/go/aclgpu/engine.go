@@ -127,6 +127,7 @@ func OpenBootstrap(cfg Config, bootstrapFilePath string, bootstrapContent map[st
 
 func (e *Engine) Close() {
 	e.stopPoller()
+	pagedTables.Delete(e) // (lookup_cursor.go: the cursors themselves go with acl_close)
 	C.acl_close(e.h)
 }
 

@@ -94,7 +94,11 @@ func (p *permissionsClient) CheckBulkPermissions(ctx context.Context, in *v1.Che
 }
 
 // LookupResources: pkg/authz/lookups.go:65; the proxy drains the stream until io.EOF (lookups.go:75-83).
+// With optional_limit or optional_cursor the answer is paged out of a lookup cursor (lookup_cursor.go): one walk, every page from that snapshot.
 func (p *permissionsClient) LookupResources(ctx context.Context, in *v1.LookupResourcesRequest, _ ...grpc.CallOption) (v1.PermissionsService_LookupResourcesClient, error) {
+	if in.OptionalLimit != 0 || in.OptionalCursor != nil {
+		return p.lookupResourcesPaged(ctx, in)
+	}
 	var cs cstrings
 	defer cs.free()
 	var st, sid, srel string
@@ -290,10 +294,11 @@ func (s *relStream) RecvMsg(any) error            { return io.EOF }
 
 // LookupSubjects: who holds a permission on ONE resource (acl_lookup_subjects).  One HAS_PERMISSION message per subject, names fetched a block at a
 // time as for LookupResources; a `T:*` grant comes first as the subject "*" with the subjects it leaves out (unless the request excludes wildcards).
-// Limits and cursors are not supported: Unimplemented, as DeleteRelationships with a limit.
+// With optional_concrete_limit or optional_cursor the answer is paged out of a lookup cursor (lookup_cursor.go); an answer that holds a wildcard is
+// not paged (Unimplemented: the subjects it leaves out are a row of their own).
 func (p *permissionsClient) LookupSubjects(ctx context.Context, in *v1.LookupSubjectsRequest, _ ...grpc.CallOption) (v1.PermissionsService_LookupSubjectsClient, error) {
 	if in.OptionalConcreteLimit != 0 || in.OptionalCursor != nil {
-		return nil, status.Error(codes.Unimplemented, "LookupSubjects with a limit or a cursor is not implemented by the GPU ACL engine")
+		return p.lookupSubjectsPaged(ctx, in)
 	}
 	var cs cstrings
 	defer cs.free()

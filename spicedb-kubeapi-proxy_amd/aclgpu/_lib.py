@@ -36,6 +36,8 @@ SYMBOLS = [
     "acl_explain_proof_bulk_ids", "acl_explain_proof",
     "acl_explain_denial_bulk_ids", "acl_explain_denial", "acl_selfcheck_denial_grants",
     "acl_lookup_resources_multi", "acl_access_review", "acl_schema_name_copy",
+    "acl_lookup_cursor_open", "acl_lookup_cursor_open_subjects", "acl_lookup_cursor_info", "acl_lookup_cursor_pages", "acl_lookup_cursor_page_names",
+    "acl_lookup_cursor_close", "acl_lookup_cursor_stats",
 ]
 
 
@@ -119,6 +121,11 @@ class Stats(C.Structure):
 class Target(C.Structure):
     """acl_target_t: one (type, relation or permission) of acl_lookup_resources_multi / acl_access_review."""
     _fields_ = [("rtype", C.c_int32), ("permission", C.c_int32)]
+
+
+class PageReq(C.Structure):
+    """acl_page_req_t: one request of acl_lookup_cursor_pages -- the ids of `row` behind `after_id`, at most `limit` of them."""
+    _fields_ = [("row", C.c_uint32), ("after_id", C.c_uint32), ("limit", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class ReviewRow(C.Structure):
@@ -314,5 +321,13 @@ def load():
     L.acl_shard_lookup_step.argtypes = [H, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(ShardStep)]
     L.acl_shard_lookup_import.argtypes = [H, C.c_uint32, C.c_void_p, C.c_size_t]
     L.acl_shard_lookup_finish.argtypes = [H, C.c_void_p, C.c_size_t]
+    L.acl_lookup_cursor_open.argtypes = [H, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(CallOpts), C.POINTER(C.c_void_p)]
+    L.acl_lookup_cursor_open_subjects.argtypes = L.acl_lookup_cursor_open.argtypes
+    L.acl_lookup_cursor_info.argtypes = [H, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p]
+    L.acl_lookup_cursor_pages.argtypes = [H, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(CallOpts)]
+    L.acl_lookup_cursor_page_names.argtypes = [H, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_uint32),
+                                               C.POINTER(C.c_uint8)]
+    L.acl_lookup_cursor_close.argtypes = [H, C.c_void_p]
+    L.acl_lookup_cursor_stats.argtypes = [H, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
     _lib = L
     return L

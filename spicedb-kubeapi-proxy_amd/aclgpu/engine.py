@@ -28,6 +28,7 @@ ITEM_DTYPE = np.dtype([("resource_type", "<u2"), ("permission", "<u2"), ("resour
                        ("subject_relation", "<u2"), ("subject_id", "<u4")])
 assert ITEM_DTYPE.itemsize == 16
 WATCHER_FROM_NOW = 1  # ACL_WATCHER_FROM_NOW
+PAGE_FROM_START = 0xFFFFFFFF  # ACL_PAGE_FROM_START: a page's after_id "before id 0"
 WATCH_CHANGE_WILDCARD = 1  # ACL_WATCH_CHANGE_WILDCARD (a record's `reserved`, subject-direction sets)
 WATCH_CHANGE_DTYPE = np.dtype([("watcher", "<u4"), ("resource_id", "<u4"), ("gained", "<u4"), ("reserved", "<u4")])  # acl_watch_change_t
 assert WATCH_CHANGE_DTYPE.itemsize == C.sizeof(WatchChange) == 16
@@ -583,6 +584,25 @@ class Engine:
         self._check(self._L.acl_watch_set_open_subjects(self._h, self.type_id(rt), self.relation_id(rt, perm), self.type_id(st), sr, C.byref(out)))
         return WatchSet(self, out, st)  # (the ids of its rows and records are of the subject type)
 
+    # ---- paged lookups (include/aclgpu.h "paged lookups": limit and cursor, served from rows kept on the device)
+    def _cursor(self, fn, rt, perm, st, srel, ids, row_type, cancel, timeout_s) -> "LookupCursor":
+        sr = self.relation_id(st, srel)
+        if srel and sr < 0:
+            sr = -2  # (a relation that does not exist is not "no relation")
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        out = C.c_void_p()
+        o = self._opts(cancel, timeout_s)
+        self._check(fn(self._h, self.type_id(rt), self.relation_id(rt, perm), self.type_id(st), sr, ids.ctypes.data, ids.size, C.byref(o) if o else None, C.byref(out)))
+        return LookupCursor(self, out, row_type, int(ids.size))
+
+    def lookup_cursor(self, rt, perm, st, srel, subject_ids, cancel=None, timeout_s=None) -> "LookupCursor":
+        """One walk now, pages later: row i holds the resources of `rt` that subject_ids[i] (`st[#srel]`) holds `perm` on, pinned at this revision."""
+        return self._cursor(self._L.acl_lookup_cursor_open, rt, perm, st, srel, subject_ids, rt, cancel, timeout_s)
+
+    def subjects_cursor(self, rt, perm, st, srel, resource_ids, cancel=None, timeout_s=None) -> "LookupCursor":
+        """The other direction: row i holds the subjects `st[#srel]` that hold `perm` on resource_ids[i] of `rt` (LookupSubjects' named subjects)."""
+        return self._cursor(self._L.acl_lookup_cursor_open_subjects, rt, perm, st, srel, resource_ids, st, cancel, timeout_s)
+
     def selfcheck_subject_rows(self, rt, perm, st, srel, resource_ids) -> np.ndarray:
         """Test hook: the rows a subject-direction set would hold for these resource ids, by the set's device path -> [n, words] uint32."""
         rids = np.ascontiguousarray(resource_ids, dtype=np.uint32)
@@ -967,13 +987,84 @@ class Engine:
     def stats(self) -> dict:
         s = Stats()
         self._check(self._L.acl_stats(self._h, C.byref(s)))
-        return {n: getattr(s, n) for n, _ in Stats._fields_}
+        out = {n: getattr(s, n) for n, _ in Stats._fields_}
+        launches, ms = C.c_uint64(), C.c_double()  # (lookup cursors count on their own: acl_lookup_cursor_stats)
+        self._check(self._L.acl_lookup_cursor_stats(self._h, C.byref(launches), C.byref(ms)))
+        out["page_launches"], out["page_ms"] = launches.value, ms.value
+        return out
 
     def stats_reset(self):
         self._check(self._L.acl_stats_reset(self._h))
 
     def set_timing(self, on: bool):
         self._check(self._L.acl_set_timing(self._h, 1 if on else 0))
+
+
+class LookupCursor:
+    """One acl_lookup_cursor_t: the rows of a batched lookup kept on the device, pinned at the revision of the open, read a page of ids at a time."""
+
+    def __init__(self, engine: Engine, handle, row_type: str, n_rows: int):
+        self._e, self._c, self.row_type, self.n_rows = engine, handle, row_type, n_rows
+
+    def info(self):
+        """-> (revision, counts [n] u64, flags [n] u8: SUBJECTS_WILDCARD on a subject cursor's rows)"""
+        rev, n, rt = C.c_uint64(), C.c_uint32(), C.c_uint32()
+        counts, flags = np.zeros(self.n_rows, dtype=np.uint64), np.zeros(self.n_rows, dtype=np.uint8)
+        self._e._check(self._e._L.acl_lookup_cursor_info(self._e._h, self._c, C.byref(rev), C.byref(n), C.byref(rt), counts.ctypes.data, flags.ctypes.data))
+        assert n.value == self.n_rows
+        return rev.value, counts, flags
+
+    def pages_raw(self, reqs, cancel=None, timeout_s=None):
+        """reqs: [(row, after or None, limit), ...] -> (ids u32 [sum of limits], n u32 [m], more u8 [m]): request q's ids are
+        ids[off[q]:off[q] + n[q]] with off the exclusive prefix of the limits, exactly as acl_lookup_cursor_pages leaves them."""
+        m = len(reqs)
+        arr = np.zeros((m, 4), dtype=np.uint32)
+        for q, (row, after, limit) in enumerate(reqs):
+            arr[q] = (row, PAGE_FROM_START if after is None else after, limit, 0)
+        cap = int(arr[:, 2].sum(dtype=np.uint64))
+        ids, n, more = np.zeros(max(cap, 1), dtype=np.uint32), np.zeros(m, dtype=np.uint32), np.zeros(m, dtype=np.uint8)
+        o = Engine._opts(cancel, timeout_s)
+        self._e._check(self._e._L.acl_lookup_cursor_pages(self._e._h, self._c, arr.ctypes.data, m, ids.ctypes.data, cap, n.ctypes.data, more.ctypes.data,
+                                                          C.byref(o) if o else None))
+        return ids[:cap], n, more
+
+    def pages(self, reqs, cancel=None, timeout_s=None):
+        """reqs: [(row, after or None, limit), ...] -> [(ids u32, more: bool), ...], all in ONE call (two kernel launches whatever len(reqs) is)"""
+        ids, n, more = self.pages_raw(reqs, cancel, timeout_s)
+        out, off = [], 0
+        for q, (_row, _after, limit) in enumerate(reqs):
+            out.append((ids[off:off + int(n[q])].copy(), bool(more[q])))
+            off += int(limit)
+        return out
+
+    def page(self, row, after=None, limit=500):
+        """-> (ids, more): the next `limit` ids of `row` behind `after` (None: from the start); continue with after = ids[-1] while more."""
+        return self.pages([(row, after, limit)])[0]
+
+    def page_names(self, row, after=None, limit=500, buf_bytes: int = 1 << 16):
+        """-> (ids, names, more).  FAILED_PRECONDITION once an object id has been recycled since the open: reopen (page() keeps answering)."""
+        ids, ends = np.zeros(limit, dtype=np.uint32), np.zeros(limit, dtype=np.uint32)
+        buf = C.create_string_buffer(max(buf_bytes, 1024))
+        n, more = C.c_uint32(), C.c_uint8()
+        self._e._check(self._e._L.acl_lookup_cursor_page_names(self._e._h, self._c, int(row), PAGE_FROM_START if after is None else int(after), int(limit), ids.ctypes.data,
+                                                               buf, len(buf), ends.ctypes.data, C.byref(n), C.byref(more)))
+        raw, names, start = buf.raw, [], 0
+        for k in range(n.value):
+            names.append(raw[start:int(ends[k])].decode())
+            start = int(ends[k])
+        return ids[:n.value].copy(), names, bool(more.value)
+
+    def close(self):
+        if self._c is not None and getattr(self._e, "_h", None):
+            c, self._c = self._c, None
+            self._e._check(self._e._L.acl_lookup_cursor_close(self._e._h, c))
+        self._c = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
 
 
 class WatchSet:

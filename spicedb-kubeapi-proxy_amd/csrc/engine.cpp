@@ -140,6 +140,7 @@ void acl_close(acl_engine_t *h) {
     (void)acl_shard_rccl_destroy(h);
     compaction_join(h);
     watch_sets_release(h);
+    lookup_cursors_release(h);
     if (h->store_only) {
         delete h;
         return;
@@ -517,6 +518,8 @@ int acl_stats_reset(acl_engine_t *h) {
     h->stats.snapshot_edges_local = el;
     h->stats.snapshot_edges = e;
     h->stats.snapshot_bytes = b;
+    h->page_launches = 0;
+    h->page_ms = 0;
     return ACL_OK;
 }
 int acl_set_timing(acl_engine_t *h, int on) {

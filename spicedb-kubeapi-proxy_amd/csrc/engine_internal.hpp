@@ -458,6 +458,12 @@ struct acl_engine {
     // open watch sets (engine_watchset.cpp): acl_close releases what is left
     std::mutex watch_sets_mu;
     std::vector<struct acl_watch_set *> watch_sets;
+    // open lookup cursors (engine_cursor.cpp): acl_close releases what is left; cursor_bytes: the rows they hold together (at most kCursorBytes)
+    std::mutex cursors_mu;
+    std::vector<struct acl_lookup_cursor *> cursors;
+    size_t cursor_bytes = 0;
+    uint64_t page_launches = 0;  // acl_lookup_cursor_stats (under stats_mu)
+    double page_ms = 0;
     uint32_t max_sub_batch = 1u << 20;
     uint32_t local_max_items = 1u << 20;  // batches up to this size take the single-launch path (k_check_local) first; 0 = never.  Measured on C4
                                           // (profiles/r02_walk_vs_levels.txt): faster than the level loop at every batch size, 1.5x at 262 144 items
@@ -632,6 +638,14 @@ int lookup_batch(acl_engine *h, PassCtx *c, int rtype, int perm, int stype, int 
 int lookup_refine(acl_engine *h, PassCtx *c, int rtype, int perm, int stype, int srel, const uint32_t *sids, size_t n, uint32_t *bitmaps, size_t words, size_t cw,
                   uint64_t *counts);
 void watch_sets_release(acl_engine_t *h);  // engine_watchset.cpp: acl_close frees the sets still open
+void lookup_cursors_release(acl_engine_t *h);  // engine_cursor.cpp: acl_close frees the cursors still open
+// rows kept on the device (watch sets, lookup cursors) are 16-byte multiples: one dwordx4 per lane in the diff and page kernels
+inline size_t row_words_for(uint32_t nobj) { return std::max<size_t>(4, (((size_t)nobj + 31) / 32 + 3) / 4 * 4); }
+// engine_watchset.cpp: count + scan of a diff on c's stream; the total crosses once.  The tile offsets stay in d_offs ([tiles + 1], the last one the total).
+int rows_diff_scan(PassCtx *c, const DevRowsDiff &d, DevArray<uint32_t> &d_counts, DevArray<uint64_t> &d_offs, int kind, uint64_t *total_out);
+// engine_subjects.cpp: acl_lookup_subjects_batch behind its argument checks (caller holds an Eval with the subject rows current)
+int subjects_batch(acl_engine *h, PassCtx *c, int rt, int pm, int st, int srel, const uint32_t *rids, size_t n, uint32_t *bitmaps, size_t words, uint64_t *counts,
+                   uint8_t *flags, uint32_t *excluded);
 bool empty(const char *s);
 FilterText to_filter(const acl_filter_t *f);
 // strings -> interned item; returns 0 or the per-item error the pair carries (check.go:55).  Caller holds names_mu shared.

@@ -92,6 +92,8 @@ int check_items(acl_engine *h, PassCtx *c, std::vector<acl_item_t> &items, std::
     return ACL_OK;
 }
 
+}  // namespace
+
 // caller holds an Eval (snapshot + subject rows current) and validated the arguments
 int subjects_batch(acl_engine *h, PassCtx *c, int rt, int pm, int st, int srel, const uint32_t *rids, size_t n, uint32_t *bitmaps, size_t words, uint64_t *counts,
                    uint8_t *flags, uint32_t *excluded) {
@@ -183,6 +185,8 @@ int subjects_batch(acl_engine *h, PassCtx *c, int rt, int pm, int st, int srel, 
     }
     return ACL_OK;
 }
+
+namespace {
 
 int subjects_args_ok(acl_engine *h, int rt, int pm, int st, int srel) {
     const Schema &sc = h->store.schema();

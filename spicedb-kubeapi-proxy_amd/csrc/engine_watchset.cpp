@@ -54,8 +54,6 @@ namespace aclint {
 constexpr size_t kWatchSetBytes = (size_t)1 << 30;     // both row arrays of a set, at most (the bound lookup_batch puts on a group's visited bits)
 constexpr uint64_t kWatchSetMaxChanges = 1ull << 28;  // records of one poll, at most (4 GiB)
 
-static size_t row_words_for(uint32_t nobj) { return std::max<size_t>(4, (((size_t)nobj + 31) / 32 + 3) / 4 * 4); }  // 16-byte rows: one dwordx4 per lane in the diff
-
 static int set_args_ok(acl_engine *h, int rtype, int perm, int stype, int srel) {
     if (!h->store.has_schema()) return fail(ACL_ERR_FAILED_PRECONDITION, "no schema loaded");
     const Schema &sc = h->store.schema();
@@ -66,7 +64,7 @@ static int set_args_ok(acl_engine *h, int rtype, int perm, int stype, int srel) 
 }
 
 // count + scan on c's stream; the total crosses once.  The tile offsets stay in d_offs ([tiles + 1], the last one the total).
-static int rows_diff_scan(PassCtx *c, const DevRowsDiff &d, DevArray<uint32_t> &d_counts, DevArray<uint64_t> &d_offs, int kind, uint64_t *total_out) {
+int rows_diff_scan(PassCtx *c, const DevRowsDiff &d, DevArray<uint32_t> &d_counts, DevArray<uint64_t> &d_offs, int kind, uint64_t *total_out) {
     const uint64_t tiles = (uint64_t)rows_diff_tiles(d) * d.n_rows;
     HIP_TRY(d_counts.ensure(tiles));
     HIP_TRY(d_offs.ensure(tiles + 1));

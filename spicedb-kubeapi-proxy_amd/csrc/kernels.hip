@@ -3955,6 +3955,82 @@ void launch_rows_diff_emit(hipStream_t st, const DevRowsDiff &d, const uint64_t 
     });
 }
 
+// ---- lookup cursors: pages of ids out of rows kept on the device (kernels.hpp DevRowsPage) ----
+// The rank index is the diff's own count + scan against an empty old array: offs[row * ntiles + tile] = set bits in front of the tile, over all rows.
+// plan: one wave per request.  start = after_id + 1 (ACL_PAGE_FROM_START wraps to 0); rank0 = the index's offset of the start's tile + the popcount of the
+//       tile's bits below start; rank_end = min(rank0 + limit, the row's end rank).  Leaves {rank0, rank_end} for the emit and n | more << 31 for the host.
+// page: one wave per (request, tile).  The tile's rank interval [offs[t], offs[t + 1]) against [rank0, rank_end) decides whether the wave has anything to
+//       do; a live wave walks its tile as k_rows_diff_emit does and writes the id of every set bit whose rank is in range at ids[base + rank - rank0].
+//       Where an id lands depends on its rank alone: no atomics, no order between waves.
+__global__ __launch_bounds__(256) void k_rows_page_plan(DevRowsPage p, const uint4 *__restrict__ reqs, uint32_t m, ulonglong2 *__restrict__ plan, uint32_t *__restrict__ res) {
+    const uint32_t lane = lane_id();
+    for (uint32_t q = blockIdx.x * 4u + uniform(threadIdx.x >> 6); q < m; q += gridDim.x * 4u) {
+        const uint4 rq = reqs[q];  // {row, after_id, limit, base}
+        const uint32_t row = rq.x, start = rq.y + 1u;
+        const unsigned long long *ro = (const unsigned long long *)p.offs + (size_t)row * p.ntiles;
+        const unsigned long long row_end = ro[p.ntiles];
+        unsigned long long rank0 = row_end;
+        if (start < p.row_words * 32ull) {  // (wave-uniform: the request's own words)
+            const uint32_t t0 = start / (kDiffTileWords * 32u), sw = start >> 5, smask = (1u << (start & 31u)) - 1u;
+            const uint32_t *r = p.rows + (size_t)row * p.row_words;
+            uint32_t cnt = 0;
+            for (uint32_t w0 = t0 * kDiffTileWords + lane * 4u; w0 <= sw; w0 += kDiffStepWords) {  // (w0 <= sw < row_words, both multiples of 4 apart from sw: the load is inside the row)
+                const uint4 v = *reinterpret_cast<const uint4 *>(r + w0);
+                const uint32_t x[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (uint32_t k = 0; k < 4u; k++) cnt += __popc(w0 + k < sw ? x[k] : (w0 + k == sw ? x[k] & smask : 0u));
+            }
+            rank0 = ro[t0] + wave_last(wave_incl_scan(cnt, 0u));
+        }
+        const unsigned long long rank_end = min(rank0 + rq.z, row_end);
+        if (lane == 0) {
+            plan[q] = make_ulonglong2(rank0, rank_end);
+            res[q] = (uint32_t)(rank_end - rank0) | (row_end > rank_end ? 0x80000000u : 0u);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_rows_page(DevRowsPage p, const uint4 *__restrict__ reqs, uint32_t m, const ulonglong2 *__restrict__ plan, uint32_t *__restrict__ ids) {
+    const uint32_t lane = lane_id();
+    const uint64_t total = (uint64_t)p.ntiles * m;
+    for (uint64_t t = (uint64_t)blockIdx.x * 4u + uniform(threadIdx.x >> 6); t < total; t += (uint64_t)gridDim.x * 4u) {
+        const uint32_t q = (uint32_t)(t / p.ntiles), tile = (uint32_t)(t - (uint64_t)q * p.ntiles);
+        const ulonglong2 pl = plan[q];
+        const unsigned long long rank0 = pl.x, rank_end = pl.y;
+        if (rank0 >= rank_end) continue;
+        const uint4 rq = reqs[q];
+        const unsigned long long *ro = (const unsigned long long *)p.offs + (size_t)rq.x * p.ntiles + tile;
+        unsigned long long base = ro[0];
+        if (base >= rank_end || ro[1] <= rank0) continue;  // (the tile's ranks do not meet the page's: most waves leave here)
+        const uint32_t *r = p.rows + (size_t)rq.x * p.row_words;
+        uint32_t *out = ids + rq.w;
+        const uint32_t w_begin = tile * kDiffTileWords, w_end = min(w_begin + kDiffTileWords, p.row_words);
+        for (uint32_t ws = w_begin; ws < w_end && base < rank_end; ws += kDiffStepWords) {  // (wave-uniform trip count: the prefix sum needs every lane)
+            const uint32_t w0 = ws + lane * 4u;
+            const uint4 v = diff_load4<true>(r, p.row_words, w0);
+            const uint32_t xw[4] = {v.x, v.y, v.z, v.w};
+            const uint32_t cnt = __popc(xw[0]) + __popc(xw[1]) + __popc(xw[2]) + __popc(xw[3]);
+            const uint32_t incl = wave_incl_scan(cnt, 0u);
+            unsigned long long pos = base + (incl - cnt);
+            base += wave_last(incl);
+            if (pos + cnt > rank0 && pos < rank_end) {  // (else: this lane's bits lie outside the page)
+#pragma unroll
+                for (uint32_t k = 0; k < 4u; k++)
+                    for (uint32_t mm = xw[k]; mm; mm &= mm - 1u) {
+                        if (pos >= rank0 && pos < rank_end) out[pos - rank0] = (w0 + k) * 32u + (uint32_t)__ffs((int)mm) - 1u;  // (pos - rank0 < limit: inside the request's own slice of ids)
+                        pos++;
+                    }
+            }
+        }
+    }
+}
+
+void launch_rows_page(hipStream_t st, const DevRowsPage &p, const uint4 *reqs, uint32_t m, void *plan, uint32_t *res, uint32_t *ids) {
+    if (!m) return;
+    hipLaunchKernelGGL(k_rows_page_plan, dim3(std::min<uint32_t>((m + 3u) / 4u, 4096u)), dim3(256), 0, st, p, reqs, m, (ulonglong2 *)plan, res);
+    hipLaunchKernelGGL(k_rows_page, dim3(rows_diff_blocks((uint64_t)p.ntiles * m)), dim3(256), 0, st, p, reqs, m, (const ulonglong2 *)plan, ids);
+}
+
 // ---- subject-direction watch sets: the candidates of a non-monotone permission confirmed where the rows are (kernels.hpp DevRefine) ----
 // The candidate records are the diff's own (rows against an empty old array: one {row, bit, 1, 0} per set bit, ordered by (row, bit)); the stand-ins
 // of the flagged rows follow them.  Item k answers record k, so k_refine_apply needs no search: lanes of a wave hold consecutive records, the ones

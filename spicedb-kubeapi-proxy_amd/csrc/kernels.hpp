@@ -267,6 +267,17 @@ struct DevRowsDiff {
 inline uint32_t rows_diff_tiles(const DevRowsDiff &d) { return (std::max(d.old_words, d.new_words) + kDiffTileWords - 1) / kDiffTileWords; }  // per row
 void launch_rows_diff_count(hipStream_t s, const DevRowsDiff &d, uint32_t *tile_counts, uint64_t *offs);  // count + scan
 void launch_rows_diff_emit(hipStream_t s, const DevRowsDiff &d, const uint64_t *offs, uint4 *out, uint64_t out_cap);
+// Lookup cursors (engine_cursor.cpp): pages of ids out of packed rows ([n_rows][row_words], row_words a multiple of 4) and their rank index -- offs as
+// launch_rows_diff_count leaves it for these rows against an empty old array ([n_rows * ntiles + 1], ntiles = tiles of kDiffTileWords words per row).
+// Request q = {row, after_id, limit, base}: the ascending ids of the row that are > after_id (0xFFFFFFFF: from id 0), at most `limit` of them, at
+// ids[base ..]; res[q] = how many | 0x80000000 when a larger id remains.  row < n_rows and base + limit inside `ids` are the caller's to check.
+// Two launches on `s` (a plan step of one wave per request into plan[m] of 16 bytes each, then one wave per (request, tile)); nothing is synchronised.
+struct DevRowsPage {
+    const uint32_t *rows;
+    const uint64_t *offs;
+    uint32_t row_words, ntiles, n_rows;
+};
+void launch_rows_page(hipStream_t s, const DevRowsPage &p, const uint4 *reqs, uint32_t m, void *plan, uint32_t *res, uint32_t *ids);
 // Subject-direction watch sets (engine_watchset.cpp subject_rows): the candidates of a permission with `&` / `-` / `.all()` confirmed on the device.  One slice of
 // whole rows [row0, row0 + rows of the slice) of a packed row array at a time:
 //   fill  : rows wrows[0 .. nflag) (the walk reached `T:*` there) become "every id of the type": bits [0, nobj) set, the wildcard's own bit cleared

@@ -226,6 +226,7 @@ Status Store::load_schema(const std::string &text) {
     if (!parse_schema(text, &s, &err)) return Status::Err(ACL_ERR_INVALID_ARGUMENT, err);
     schema_ = std::move(s);
     schema_loaded_ = true;
+    schema_loads_++;
     objects_.assign(schema_.defs.size(), ObjectTable());
     tables_.assign(schema_.nslots, {});
     expiry_index_.clear();

@@ -258,6 +258,7 @@ class Store {
     Status load_schema(const std::string &text);
     const Schema &schema() const { return schema_; }
     bool has_schema() const { return !schema_.defs.empty() || schema_loaded_; }
+    uint64_t schema_loads() const { return schema_loads_; }  // counts load_schema: ids handed out under an earlier schema mean nothing (lookup cursors expire by it)
 
     ObjectTable &objects(int type) { return objects_[type]; }
     const ObjectTable &objects(int type) const { return objects_[type]; }
@@ -399,6 +400,7 @@ class Store {
     std::vector<uint8_t> no_recycle_;             // [type] a numeric bulk load chose ids of this type: its counts are not tracked
     std::unordered_map<uint64_t, uint64_t> recycled_rev_;  // type << 32 | id -> revision at which the id changed its name (changes_since)
     uint64_t ids_recycled_ = 0;
+    uint64_t schema_loads_ = 0;
     int64_t reuse_quarantine_ms_ = kReuseQuarantineMs;
     void ref(int type, uint32_t id, int delta);
     void ref_key(int slot, int cls, uint64_t key, int delta);

@@ -365,6 +365,46 @@ int acl_lookup_cursor_close(acl_engine_t *h, acl_lookup_cursor_t *cur);
  * HIP-event time (needs timing on).  Either pointer may be NULL. */
 int acl_lookup_cursor_stats(acl_engine_t *h, uint64_t *page_launches_out, double *page_ms_out);
 
+/* ---- derived lookup cursors: set algebra over rows pinned in device memory ----
+ * A kube principal is a user AND the groups authn attached to it; "what may this principal see" is the union of what each of its subject forms may see,
+ * and the audits around it ("pods alice sees and bob does not", "users who can view ALL of these pods", "how many pods two accounts share") are unions,
+ * intersections and differences of such rows.  These calls compute them where the rows live and leave an ordinary cursor behind.
+ * open_mixed is acl_lookup_cursor_open where every row names its own subject form: row i is bit for bit what acl_lookup_resources_batch answers for
+ * subjects[i] = {stype, srel (-1 none), id}, all rows from ONE snapshot (one evaluation; one walk per maximal run of consecutive subjects with equal
+ * (stype, srel), so sort the subjects by form), a permission with `-`, `&` or `.all()` confirmed on the host and uploaded per run, and it fails exactly as
+ * that batch call fails.  reserved != 0: ACL_ERR_INVALID_ARGUMENT.
+ * derive makes a NEW cursor of n_exprs rows out of the rows of the open cursors srcs[0 .. n_srcs).  refs[k] = {cursor: index into srcs, row} names a
+ * source row.  Expression e owns refs[first .. first + n_any + n_all + n_none): its any-list, then its all-list, then its none-list, and its row is
+ * A & B & ~C with A = the union of the any-list (every id when n_any == 0), B = the intersection of the all-list (every id when n_all == 0), C = the union
+ * of the none-list.  n_any + n_all >= 1.  The result is an ordinary cursor: info (flags 0), pages, page_names, close, the 1 GiB budget and acl_close work
+ * unchanged; it owns its rows, so the sources may be closed afterwards, and it is a legal source itself.  Two kernel launches per call, whatever n_exprs
+ * and the lists' lengths are; no row crosses PCIe.
+ *  - all sources have the same direction and the same row_type, else ACL_ERR_INVALID_ARGUMENT; a subject-direction row whose flag holds
+ *    ACL_SUBJECTS_WILDCARD and that an expression references: ACL_ERR_FAILED_PRECONDITION (such a row means "everyone but ...", it is not a bitmap);
+ *  - all sources have the same revision, else ACL_ERR_FAILED_PRECONDITION -- unless flags holds ACL_DERIVE_ANY_REVISION: then the derived cursor reports
+ *    the smallest one; no source may be expired (a schema reload), and the derived cursor's mark for page_names (ids recycled) is the oldest of the sources';
+ *  - sources may have rows of different widths (the type grew between the opens): the derived width is the largest, words a source does not have read as zero;
+ *  - sources whose rows live on different devices: ACL_ERR_FAILED_PRECONDITION.
+ * Validation comes first, as acl_lookup_resources_multi orders it: a NULL pointer where one is needed, an unknown flag bit, refs[k].cursor >= n_srcs, an
+ * expression running past n_refs or with n_any + n_all == 0, a source that is not an open cursor of this engine, refs[k].row >= that cursor's rows, mixed
+ * directions or row types: ACL_ERR_INVALID_ARGUMENT; n_exprs == 0: a valid cursor without rows.  Then a store-only engine: ACL_ERR_UNAVAILABLE, a sharded
+ * engine: ACL_ERR_FAILED_PRECONDITION; then the preconditions above; then the budget (ACL_ERR_RESOURCE_EXHAUSTED).  The sources' locks are taken in address
+ * order, so concurrent derives over shared sources do not deadlock.
+ * count is the same evaluation with no row kept: counts_out[e] = ids in expression e's row.  It takes nothing from the budget and allocates no rows. */
+typedef struct { int32_t stype, srel /* -1 none */; uint32_t id, reserved; } acl_subject_ref_t; /* 16 bytes */
+typedef struct { uint32_t cursor /* index into srcs[] */, row; } acl_row_ref_t;                   /* 8 bytes */
+typedef struct { uint32_t first, n_any, n_all, n_none; } acl_row_expr_t;                          /* 16 bytes */
+#define ACL_DERIVE_ANY_REVISION 1u
+int acl_lookup_cursor_open_mixed(acl_engine_t *h, int rtype, int permission, const acl_subject_ref_t *subjects, size_t n, const acl_call_opts_t *opts,
+                                 acl_lookup_cursor_t **out);
+int acl_lookup_cursor_derive(acl_engine_t *h, acl_lookup_cursor_t *const *srcs, size_t n_srcs, const acl_row_ref_t *refs, size_t n_refs,
+                             const acl_row_expr_t *exprs, size_t n_exprs, uint32_t flags, acl_lookup_cursor_t **out);
+int acl_lookup_cursor_count(acl_engine_t *h, acl_lookup_cursor_t *const *srcs, size_t n_srcs, const acl_row_ref_t *refs, size_t n_refs,
+                            const acl_row_expr_t *exprs, size_t n_exprs, uint32_t flags, uint64_t *counts_out);
+/* since open / the last acl_stats_reset: kernel launches of derive / count (two per call: combine + scan) and their HIP-event time (needs timing on).
+ * Either pointer may be NULL.  Like the page counters these are not fields of acl_stats_t. */
+int acl_lookup_derive_stats(acl_engine_t *h, uint64_t *derive_launches_out, double *derive_ms_out);
+
 /* ---- Explain: Check + a witness, the chain of stored relationships that grants the item ----
  * perm_out / err_out per item are exactly what acl_check_bulk_ids answers for the same items on the same snapshot (the Check and the walk run inside one
  * evaluation).  An item that answers HAS_PERMISSION on a permission built from `+`, `->` and references alone also gets a witness: hops

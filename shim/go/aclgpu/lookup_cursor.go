@@ -9,6 +9,7 @@ import (
 	"context"
 	"encoding/base64"
 	"io"
+	"sort"
 	"strconv"
 	"strings"
 	"sync"
@@ -371,3 +372,85 @@ func (r *pagedSubjectStream) CloseSend() error             { return nil }
 func (r *pagedSubjectStream) Context() context.Context     { return r.s.ctx }
 func (r *pagedSubjectStream) SendMsg(any) error            { return nil }
 func (r *pagedSubjectStream) RecvMsg(any) error            { return io.EOF }
+
+// PrincipalSubject is one subject form of a kube principal: the user itself (`user:<name>`), or a group that authn attached to it, as the
+// rule templates address it (`group:<name>#member`; rules.go:269).  Relation "" or "..." is no relation.
+type PrincipalSubject struct{ Type, ID, Relation string }
+
+// principalCursor binds the two calls of aclgpu.h "derived lookup cursors" for a pre-filter over `user` + `user.groups`: ONE
+// acl_lookup_cursor_open_mixed over every subject form of every principal (one snapshot; the forms sorted by type and relation, so the engine
+// walks once per form), then ONE acl_lookup_cursor_derive with an any-list per principal.  Row p of the cursor returned is what principal p
+// may see: the union of its forms' individual answers -- the right definition for permissions with `-`, `&` and `.all()` too, which a
+// reverse walk seeded with all the forms at once is not.  The mixed cursor is closed here; the caller pages the derived one
+// (acl_lookup_cursor_page_names) and closes it.  No row crosses PCIe.
+func (p *permissionsClient) principalCursor(ctx context.Context, resourceType, permission string, principals [][]PrincipalSubject) (*C.acl_lookup_cursor_t, error) {
+	var cs cstrings
+	defer cs.free()
+	rt := C.acl_type_id(p.e.h, cs.add(resourceType))
+	pm := C.int(-1)
+	if rt >= 0 {
+		pm = C.acl_relation_id(p.e.h, rt, cs.add(permission))
+	}
+	type flat struct {
+		stype, srel C.int
+		id          C.uint32_t
+		principal   int
+	}
+	var all []flat
+	for i, forms := range principals {
+		for _, f := range forms {
+			stype := C.acl_type_id(p.e.h, cs.add(f.Type))
+			sr := C.int(-1)
+			if f.Relation != "" && f.Relation != "..." {
+				sr = -2 // (a relation that does not exist is not "no relation")
+				if stype >= 0 {
+					if r := C.acl_relation_id(p.e.h, stype, cs.add(f.Relation)); r >= 0 {
+						sr = r
+					}
+				}
+			}
+			var id C.uint32_t
+			if stype >= 0 {
+				if rc := C.acl_intern(p.e.h, stype, cs.add(f.ID), &id); rc != 0 {
+					return nil, lastError(rc)
+				}
+			}
+			all = append(all, flat{stype, sr, id, i})
+		}
+	}
+	sort.SliceStable(all, func(a, b int) bool {
+		if all[a].stype != all[b].stype {
+			return all[a].stype < all[b].stype
+		}
+		return all[a].srel < all[b].srel
+	})
+	subjects := make([]C.acl_subject_ref_t, len(all)+1) // (+1: &subjects[0] exists for a principal list without forms)
+	perPrincipal := make([][]uint32, len(principals))
+	for k, f := range all {
+		subjects[k] = C.acl_subject_ref_t{stype: C.int32_t(f.stype), srel: C.int32_t(f.srel), id: f.id, reserved: 0}
+		perPrincipal[f.principal] = append(perPrincipal[f.principal], uint32(k))
+	}
+	refs := make([]C.acl_row_ref_t, 0, len(all)+1)
+	exprs := make([]C.acl_row_expr_t, len(principals)+1)
+	for i, rows := range perPrincipal {
+		if len(rows) == 0 {
+			return nil, status.Error(codes.InvalidArgument, "a principal without a subject form")
+		}
+		exprs[i] = C.acl_row_expr_t{first: C.uint32_t(len(refs)), n_any: C.uint32_t(len(rows)), n_all: 0, n_none: 0}
+		for _, row := range rows {
+			refs = append(refs, C.acl_row_ref_t{cursor: 0, row: C.uint32_t(row)})
+		}
+	}
+	refs = append(refs, C.acl_row_ref_t{cursor: 0, row: 0}) // (so that &refs[0] exists; not counted below)
+	opts, stop := callOpts(ctx)
+	defer stop()
+	var mixed, derived *C.acl_lookup_cursor_t
+	if rc := C.acl_lookup_cursor_open_mixed(p.e.h, rt, pm, &subjects[0], C.size_t(len(all)), opts, &mixed); rc != 0 {
+		return nil, status.Error(itemCode(C.int32_t(rc)), C.GoString(C.acl_last_error()))
+	}
+	defer C.acl_lookup_cursor_close(p.e.h, mixed) // (the derived cursor owns its rows)
+	if rc := C.acl_lookup_cursor_derive(p.e.h, &mixed, 1, &refs[0], C.size_t(len(refs)-1), &exprs[0], C.size_t(len(principals)), 0, &derived); rc != 0 {
+		return nil, lastError(rc)
+	}
+	return derived, nil
+}

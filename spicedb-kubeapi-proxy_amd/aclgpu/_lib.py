@@ -38,6 +38,7 @@ SYMBOLS = [
     "acl_lookup_resources_multi", "acl_access_review", "acl_schema_name_copy",
     "acl_lookup_cursor_open", "acl_lookup_cursor_open_subjects", "acl_lookup_cursor_info", "acl_lookup_cursor_pages", "acl_lookup_cursor_page_names",
     "acl_lookup_cursor_close", "acl_lookup_cursor_stats",
+    "acl_lookup_cursor_open_mixed", "acl_lookup_cursor_derive", "acl_lookup_cursor_count", "acl_lookup_derive_stats",
 ]
 
 
@@ -126,6 +127,21 @@ class Target(C.Structure):
 class PageReq(C.Structure):
     """acl_page_req_t: one request of acl_lookup_cursor_pages -- the ids of `row` behind `after_id`, at most `limit` of them."""
     _fields_ = [("row", C.c_uint32), ("after_id", C.c_uint32), ("limit", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class SubjectRef(C.Structure):
+    """acl_subject_ref_t: one subject of acl_lookup_cursor_open_mixed -- `stype:id[#srel]`, srel -1 = none."""
+    _fields_ = [("stype", C.c_int32), ("srel", C.c_int32), ("id", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class RowRef(C.Structure):
+    """acl_row_ref_t: one operand of acl_lookup_cursor_derive -- row `row` of source cursor number `cursor`."""
+    _fields_ = [("cursor", C.c_uint32), ("row", C.c_uint32)]
+
+
+class RowExpr(C.Structure):
+    """acl_row_expr_t: one derived row -- refs[first ..): n_any rows to unite, n_all rows to intersect with, n_none rows to take away."""
+    _fields_ = [("first", C.c_uint32), ("n_any", C.c_uint32), ("n_all", C.c_uint32), ("n_none", C.c_uint32)]
 
 
 class ReviewRow(C.Structure):
@@ -329,5 +345,9 @@ def load():
                                                C.POINTER(C.c_uint8)]
     L.acl_lookup_cursor_close.argtypes = [H, C.c_void_p]
     L.acl_lookup_cursor_stats.argtypes = [H, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+    L.acl_lookup_cursor_open_mixed.argtypes = [H, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(CallOpts), C.POINTER(C.c_void_p)]
+    L.acl_lookup_cursor_derive.argtypes = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(C.c_void_p)]
+    L.acl_lookup_cursor_count.argtypes = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]
+    L.acl_lookup_derive_stats.argtypes = [H, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
     _lib = L
     return L

@@ -29,6 +29,8 @@ ITEM_DTYPE = np.dtype([("resource_type", "<u2"), ("permission", "<u2"), ("resour
 assert ITEM_DTYPE.itemsize == 16
 WATCHER_FROM_NOW = 1  # ACL_WATCHER_FROM_NOW
 PAGE_FROM_START = 0xFFFFFFFF  # ACL_PAGE_FROM_START: a page's after_id "before id 0"
+SUBJECT_REF_DTYPE = np.dtype([("stype", "<i4"), ("srel", "<i4"), ("id", "<u4"), ("reserved", "<u4")])  # acl_subject_ref_t
+DERIVE_ANY_REVISION = 1  # ACL_DERIVE_ANY_REVISION: the sources of a derived cursor may have been opened at different revisions
 WATCH_CHANGE_WILDCARD = 1  # ACL_WATCH_CHANGE_WILDCARD (a record's `reserved`, subject-direction sets)
 WATCH_CHANGE_DTYPE = np.dtype([("watcher", "<u4"), ("resource_id", "<u4"), ("gained", "<u4"), ("reserved", "<u4")])  # acl_watch_change_t
 assert WATCH_CHANGE_DTYPE.itemsize == C.sizeof(WatchChange) == 16
@@ -603,6 +605,63 @@ class Engine:
         """The other direction: row i holds the subjects `st[#srel]` that hold `perm` on resource_ids[i] of `rt` (LookupSubjects' named subjects)."""
         return self._cursor(self._L.acl_lookup_cursor_open_subjects, rt, perm, st, srel, resource_ids, st, cancel, timeout_s)
 
+    # ---- derived cursors (include/aclgpu.h "derived lookup cursors": set algebra over rows kept on the device)
+    def lookup_cursor_mixed(self, rt, perm, subjects, cancel=None, timeout_s=None) -> "LookupCursor":
+        """lookup_cursor where every row names its own subject form: subjects = [(st, srel, id), ...]; row i is what lookup_ids_batch answers for
+        subjects[i], all rows from one snapshot.  One walk per run of consecutive subjects of one form: sort them by form."""
+        arr = np.zeros(len(subjects), dtype=SUBJECT_REF_DTYPE)
+        form_ids = {}
+        for i, (st, srel, sid) in enumerate(subjects):
+            if (st, srel) not in form_ids:
+                sr = self.relation_id(st, srel) if srel else -1
+                form_ids[(st, srel)] = (self.type_id(st), -2 if srel and sr < 0 else sr)  # (a relation that does not exist is not "no relation")
+            arr[i] = form_ids[(st, srel)] + (sid, 0)
+        out = C.c_void_p()
+        o = self._opts(cancel, timeout_s)
+        self._check(self._L.acl_lookup_cursor_open_mixed(self._h, self.type_id(rt), self.relation_id(rt, perm), arr.ctypes.data, len(subjects), C.byref(o) if o else None,
+                                                         C.byref(out)))
+        return LookupCursor(self, out, rt, len(subjects))
+
+    @staticmethod
+    def _derive_args(srcs, exprs):
+        """exprs = [(any, all, none), ...], each a list of (src, row) with src an index into srcs -> (handles, refs u32 [k, 2], exprs u32 [n, 4])"""
+        handles = (C.c_void_p * max(len(srcs), 1))(*[s._c for s in srcs])
+        if isinstance(exprs, tuple) and len(exprs) == 2 and isinstance(exprs[0], np.ndarray):  # (already packed: (refs, exprs) arrays)
+            return handles, np.ascontiguousarray(exprs[0], dtype=np.uint32).reshape(-1, 2), np.ascontiguousarray(exprs[1], dtype=np.uint32).reshape(-1, 4)
+        refs, recs = [], []
+        for any_, all_, none in exprs:
+            recs.append((len(refs), len(any_), len(all_), len(none)))
+            refs += list(any_) + list(all_) + list(none)
+        return handles, np.array(refs, dtype=np.uint32).reshape(-1, 2), np.array(recs, dtype=np.uint32).reshape(-1, 4)
+
+    def derive_cursor(self, srcs, exprs, any_revision=False) -> "LookupCursor":
+        """A NEW cursor whose row e is (union of any) & (intersection of all) & ~(union of none) over rows of the open cursors `srcs`:
+        exprs = [(any, all, none), ...], each a list of (index into srcs, row); or the packed pair (refs [k, 2], exprs [n, 4]) of uint32 arrays.
+        Computed on the device, two launches whatever the sizes; the sources may be closed afterwards."""
+        handles, refs, recs = self._derive_args(srcs, exprs)
+        out = C.c_void_p()
+        self._check(self._L.acl_lookup_cursor_derive(self._h, handles, len(srcs), refs.ctypes.data, len(refs), recs.ctypes.data, len(recs),
+                                                     DERIVE_ANY_REVISION if any_revision else 0, C.byref(out)))
+        return LookupCursor(self, out, srcs[0].row_type if srcs else None, len(recs))
+
+    def count_rows(self, srcs, exprs, any_revision=False) -> np.ndarray:
+        """derive_cursor's evaluation with no row kept: -> the number of ids in every expression's row (u64 [n])"""
+        handles, refs, recs = self._derive_args(srcs, exprs)
+        counts = np.zeros(len(recs), dtype=np.uint64)
+        self._check(self._L.acl_lookup_cursor_count(self._h, handles, len(srcs), refs.ctypes.data, len(refs), recs.ctypes.data, len(recs),
+                                                    DERIVE_ANY_REVISION if any_revision else 0, counts.ctypes.data))
+        return counts
+
+    def principal_cursor(self, rt, perm, principals, cancel=None, timeout_s=None) -> "LookupCursor":
+        """principals = [[(st, srel, name), ...], ...]: a user and the groups attached to it, as subject forms (an int in the place of a name is taken as
+        the object's id).  One mixed open over every form of every principal plus one derive with an any-list per principal; -> the derived cursor,
+        row p = the resources of `rt` principal p holds `perm` on."""
+        forms = sorted({(st, srel or "", name) for p in principals for st, srel, name in p}, key=lambda f: (f[0], f[1]))  # (one run per subject form)
+        index = {f: i for i, f in enumerate(forms)}
+        subjects = [(st, srel, int(name) if isinstance(name, (int, np.integer)) else self.intern(st, name)) for st, srel, name in forms]
+        with self.lookup_cursor_mixed(rt, perm, subjects, cancel, timeout_s) as src:
+            return self.derive_cursor([src], [([(0, index[(st, srel or "", name)]) for st, srel, name in p], [], []) for p in principals])
+
     def selfcheck_subject_rows(self, rt, perm, st, srel, resource_ids) -> np.ndarray:
         """Test hook: the rows a subject-direction set would hold for these resource ids, by the set's device path -> [n, words] uint32."""
         rids = np.ascontiguousarray(resource_ids, dtype=np.uint32)
@@ -991,6 +1050,8 @@ class Engine:
         launches, ms = C.c_uint64(), C.c_double()  # (lookup cursors count on their own: acl_lookup_cursor_stats)
         self._check(self._L.acl_lookup_cursor_stats(self._h, C.byref(launches), C.byref(ms)))
         out["page_launches"], out["page_ms"] = launches.value, ms.value
+        self._check(self._L.acl_lookup_derive_stats(self._h, C.byref(launches), C.byref(ms)))
+        out["derive_launches"], out["derive_ms"] = launches.value, ms.value
         return out
 
     def stats_reset(self):

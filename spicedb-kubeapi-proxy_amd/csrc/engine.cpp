@@ -520,6 +520,8 @@ int acl_stats_reset(acl_engine_t *h) {
     h->stats.snapshot_bytes = b;
     h->page_launches = 0;
     h->page_ms = 0;
+    h->derive_launches = 0;
+    h->derive_ms = 0;
     return ACL_OK;
 }
 int acl_set_timing(acl_engine_t *h, int on) {

@@ -464,6 +464,8 @@ struct acl_engine {
     size_t cursor_bytes = 0;
     uint64_t page_launches = 0;  // acl_lookup_cursor_stats (under stats_mu)
     double page_ms = 0;
+    uint64_t derive_launches = 0;  // acl_lookup_derive_stats (under stats_mu)
+    double derive_ms = 0;
     uint32_t max_sub_batch = 1u << 20;
     uint32_t local_max_items = 1u << 20;  // batches up to this size take the single-launch path (k_check_local) first; 0 = never.  Measured on C4
                                           // (profiles/r02_walk_vs_levels.txt): faster than the level loop at every batch size, 1.5x at 262 144 items
@@ -568,7 +570,9 @@ struct Eval {
     // rev_key_slot >= 0: the lookup's subject is `type#relation` of that slot -- the reverse rows must cover its id space
     // on_device >= 0: only a replica on that HIP device will do (calls that are handed device pointers)
     // need_subjects: the subject rows of LookupSubjects must be current too (engine_subjects.cpp ensure_subjects)
-    int begin(acl_engine *h_, bool need_reverse, const CallOpts &opts = CallOpts(), int rev_key_slot = -1, int on_device = -1, bool need_subjects = false);
+    // more_key_slots: further such slots (a call whose subjects have several `type#relation` forms); the same test for each
+    int begin(acl_engine *h_, bool need_reverse, const CallOpts &opts = CallOpts(), int rev_key_slot = -1, int on_device = -1, bool need_subjects = false,
+              const std::vector<int> *more_key_slots = nullptr);
     void end();
 };
 

@@ -345,7 +345,7 @@ int device_of(acl_engine *h, const void *p) {
     return a.device;
 }
 
-int Eval::begin(acl_engine *h_, bool need_reverse, const CallOpts &opts, int rev_key_slot, int on_device, bool need_subjects) {
+int Eval::begin(acl_engine *h_, bool need_reverse, const CallOpts &opts, int rev_key_slot, int on_device, bool need_subjects, const std::vector<int> *more_key_slots) {
     h = h_;
     if (h->store_only) return fail(ACL_ERR_UNAVAILABLE, "engine was opened store-only (no GPU): Check / LookupResources are unavailable");
     int rc = check_opts(opts);
@@ -354,9 +354,11 @@ int Eval::begin(acl_engine *h_, bool need_reverse, const CallOpts &opts, int rev
         h->state_mu.lock_shared();
         bool ok = snapshot_current(h, need_reverse);
         // a `type#relation` lookup subject is itself a state of the walk: its id must lie inside the visited bitmap
-        if (ok && need_reverse && rev_key_slot >= 0 &&
-            h->store.objects(h->store.schema().slot_owner[rev_key_slot].first).count() > h->snap.slot_nobjects[rev_key_slot])
-            ok = false;
+        const auto key_slot_covered = [&](int slot) { return h->store.objects(h->store.schema().slot_owner[slot].first).count() <= h->snap.slot_nobjects[slot]; };
+        if (ok && need_reverse && rev_key_slot >= 0 && !key_slot_covered(rev_key_slot)) ok = false;
+        if (ok && need_reverse && more_key_slots)
+            for (int slot : *more_key_slots)
+                if (slot >= 0 && !key_slot_covered(slot)) ok = false;
         if (ok && need_subjects && !subjects_current(h)) ok = false;
         if (ok) {
             locked = true;

@@ -4031,6 +4031,70 @@ void launch_rows_page(hipStream_t st, const DevRowsPage &p, const uint4 *reqs, u
     hipLaunchKernelGGL(k_rows_page, dim3(rows_diff_blocks((uint64_t)p.ntiles * m)), dim3(256), 0, st, p, reqs, m, (const ulonglong2 *)plan, ids);
 }
 
+// ---- derived lookup cursors: rows that are boolean combinations of rows kept on the device (kernels.hpp DevRowsDerive) ----
+// One wave per (expression, tile), walked as k_rows_diff_count walks its tile: per step a lane holds 4 words of the result.  The wave's expression and tile
+// are made uniform (readfirstlane), so the expression record and the operand records {row base, words} come by scalar loads and every lane of a step loads
+// from the same operand row.  A lane whose words lie behind an operand's width takes zero for it and does not load.  The result is stored once (not in count
+// mode), its popcount is reduced over the wave and left in tile_counts[expr * ntiles + tile] by one lane: no atomics, no LDS, no order between waves.
+// "Everything" (an empty any-list) is the start value of the AND over the all-list, which is never empty then -- so bits behind the type's last id, zero in
+// every operand, stay zero.
+__device__ __forceinline__ uint4 derive_load4(const ulonglong2 op, uint32_t w0) {  // op: {row base, words (a multiple of 4) in the low half of y}
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    typedef const u32x4 __attribute__((address_space(1))) * global_u32x4;  // (an address out of a record: say that it is global memory, else the load is a flat one)
+    if (w0 >= (uint32_t)op.y) return make_uint4(0u, 0u, 0u, 0u);
+    const u32x4 v = *(global_u32x4)(op.x + (unsigned long long)w0 * 4u);
+    return make_uint4(v.x, v.y, v.z, v.w);
+}
+// folds the n operand rows ops[0 .. n) into r at words w0 .. w0 + 3 -- MODE 0: r |= v, 1: r &= v, 2: r &= ~v.  Four operands per trip: their loads are issued
+// together (the list's length is wave-uniform, so is every guard; a guard that fails stands in the fold's neutral value and reads no record)
+template <int MODE>
+__device__ __forceinline__ void derive_fold(uint4 &r, const ulonglong2 *__restrict__ ops, uint32_t n, uint32_t w0) {
+    const uint32_t neutral = MODE == 1 ? 0xFFFFFFFFu : 0u;
+    for (uint32_t k = 0; k < n; k += 4u) {
+        uint4 v[4];
+#pragma unroll
+        for (uint32_t j = 0; j < 4u; j++) v[j] = k + j < n ? derive_load4(ops[k + j], w0) : make_uint4(neutral, neutral, neutral, neutral);
+        issue_fence();
+#pragma unroll
+        for (uint32_t j = 0; j < 4u; j++) {
+            if (MODE == 0) r.x |= v[j].x, r.y |= v[j].y, r.z |= v[j].z, r.w |= v[j].w;
+            if (MODE == 1) r.x &= v[j].x, r.y &= v[j].y, r.z &= v[j].z, r.w &= v[j].w;
+            if (MODE == 2) r.x &= ~v[j].x, r.y &= ~v[j].y, r.z &= ~v[j].z, r.w &= ~v[j].w;
+        }
+    }
+}
+__global__ __launch_bounds__(256) void k_rows_derive(const uint4 *__restrict__ exprs, const ulonglong2 *__restrict__ ops, uint32_t *__restrict__ out, uint32_t out_words,
+                                                     uint32_t ntiles, uint32_t n_exprs, uint32_t *__restrict__ tile_counts) {
+    const uint32_t lane = lane_id();
+    const uint64_t total = (uint64_t)ntiles * n_exprs;
+    for (uint64_t t = (uint64_t)blockIdx.x * 4u + uniform(threadIdx.x >> 6); t < total; t += (uint64_t)gridDim.x * 4u) {
+        const uint32_t e = uniform((uint32_t)(t / ntiles)), tile = uniform((uint32_t)(t - (uint64_t)e * ntiles));
+        const uint4 x = exprs[e];  // {first, n_any, n_all, n_none}
+        const ulonglong2 *any = ops + x.x, *all = any + x.y, *none = all + x.z;
+        const uint32_t w_begin = tile * kDiffTileWords, w_end = min(w_begin + kDiffTileWords, out_words);
+        uint32_t cnt = 0;
+        for (uint32_t w0 = w_begin + lane * 4u; w0 < w_end; w0 += kDiffStepWords) {
+            const uint32_t init = x.y ? 0u : 0xFFFFFFFFu;  // (no any-list: "everything", cut down by the all-list, which is not empty then)
+            uint4 r = make_uint4(init, init, init, init);
+            derive_fold<0>(r, any, x.y, w0);
+            derive_fold<1>(r, all, x.z, w0);
+            derive_fold<2>(r, none, x.w, w0);
+            if (out) *reinterpret_cast<uint4 *>(out + (size_t)e * out_words + w0) = r;  // (w0 + 3 < w_end <= out_words: inside the expression's own row)
+            cnt += __popc(r.x) + __popc(r.y) + __popc(r.z) + __popc(r.w);
+        }
+        const uint32_t sum = wave_last(wave_incl_scan(cnt, 0u));
+        if (lane == 0) tile_counts[t] = sum;
+    }
+}
+
+void launch_rows_derive(hipStream_t st, const DevRowsDerive &d, uint32_t *tile_counts, uint64_t *offs) {
+    const uint64_t tiles = (uint64_t)d.ntiles * d.n_exprs;
+    if (!tiles) return;
+    hipLaunchKernelGGL(k_rows_derive, dim3(rows_diff_blocks(tiles)), dim3(256), 0, st, (const uint4 *)d.exprs, (const ulonglong2 *)d.ops, d.out, d.out_words, d.ntiles, d.n_exprs,
+                       tile_counts);
+    hipLaunchKernelGGL(k_rows_diff_scan, dim3(1), dim3(1024), 0, st, tile_counts, tiles, (unsigned long long *)offs);
+}
+
 // ---- subject-direction watch sets: the candidates of a non-monotone permission confirmed where the rows are (kernels.hpp DevRefine) ----
 // The candidate records are the diff's own (rows against an empty old array: one {row, bit, 1, 0} per set bit, ordered by (row, bit)); the stand-ins
 // of the flagged rows follow them.  Item k answers record k, so k_refine_apply needs no search: lanes of a wave hold consecutive records, the ones

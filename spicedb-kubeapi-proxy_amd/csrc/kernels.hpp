@@ -278,6 +278,21 @@ struct DevRowsPage {
     uint32_t row_words, ntiles, n_rows;
 };
 void launch_rows_page(hipStream_t s, const DevRowsPage &p, const uint4 *reqs, uint32_t m, void *plan, uint32_t *res, uint32_t *ids);
+// Derived lookup cursors (engine_cursor.cpp): n_exprs new rows of out_words words (a multiple of 4), each a boolean combination of rows that already live on
+// this device.  Expression e = exprs[e] = {first, n_any, n_all, n_none} owns the operand records ops[first ..): its any-list, then its all-list, then its
+// none-list; its row is (OR of the any-list, or everything when n_any == 0) AND (every row of the all-list) AND NOT (OR of the none-list), n_any + n_all >= 1.
+// An operand record is 16 bytes, {device address of the row (16-byte aligned), words of the row (a multiple of 4, at most out_words) in the low half of the
+// second 8 bytes}: words an operand does not have read as zero and no operand is read past its end.  Bits behind the type's last id must be zero in every
+// operand; they are zero in the result.  out == NULL: count mode, no row is written.  Two launches on `s`, whatever n_exprs and the lists' lengths are: one
+// wave per (expression, tile of kDiffTileWords words) leaves the tile's popcount in tile_counts[e * ntiles + tile], then the diff's scan turns the counts into
+// the rank index offs[n_exprs * ntiles + 1] that launch_rows_page reads.  Nothing is synchronised; n_exprs == 0: nothing is launched.
+struct DevRowsDerive {
+    const void *exprs;  // [n_exprs] 16-byte expression records
+    const void *ops;    // 16-byte operand records
+    uint32_t *out;      // [n_exprs][out_words] or NULL
+    uint32_t out_words, ntiles, n_exprs;
+};
+void launch_rows_derive(hipStream_t s, const DevRowsDerive &d, uint32_t *tile_counts, uint64_t *offs);
 // Subject-direction watch sets (engine_watchset.cpp subject_rows): the candidates of a permission with `&` / `-` / `.all()` confirmed on the device.  One slice of
 // whole rows [row0, row0 + rows of the slice) of a packed row array at a time:
 //   fill  : rows wrows[0 .. nflag) (the walk reached `T:*` there) become "every id of the type": bits [0, nobj) set, the wildcard's own bit cleared

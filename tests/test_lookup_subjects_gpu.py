@@ -8,7 +8,8 @@ import numpy as np
 import pytest
 
 from oracle import orc
-from oracle.pyoracle import ERR, HAS, MAX_DEPTH, PyOracle
+from oracle.pyoracle import MAX_DEPTH
+from tests.subjects_contract import contract
 
 pytestmark = pytest.mark.gpu
 
@@ -28,44 +29,6 @@ def ids_of(row):
 def subjects_of_type(e, st):
     """every name of the subject type the engine holds but the wildcard's own"""
     return [n for n in (e.object_name(st, i) for i in range(e.object_count(st))) if n != "*"]
-
-
-def contract(schema, rels, rt, rid, perm, st, srel, names, lenient=False, now=0):
-    """the contract by the Python oracle: (ids, wildcard, excluded) or the string "DEPTH" when the call must fail.
-    rels: [(rt, rid, rel, st, sid, srel, expires)]"""
-    full, relaxed, relaxed_w = PyOracle(schema), PyOracle(schema), PyOracle(schema)
-    for r in rels:
-        full.touch(*r[:6], expires=r[6] if len(r) > 6 else 0)
-        relaxed_w.touch(*r[:6], expires=r[6] if len(r) > 6 else 0)
-        if not (r[3] == st and r[4] == "*"):
-            relaxed.touch(*r[:6], expires=r[6] if len(r) > 6 else 0)
-    for o in (full, relaxed, relaxed_w):
-        o.now = now
-    relaxed.relaxed = relaxed_w.relaxed = True
-    fail = False
-    ids = set()
-    for s in names:
-        c, rx = full.check(rt, rid, perm, st, s, srel), relaxed.check(rt, rid, perm, st, s, srel)
-        if rx == HAS and c == HAS:
-            ids.add(s)
-        if rx == HAS and c == ERR and not lenient:
-            fail = True
-    fresh = "nobody-names-this-subject"
-    wild = False
-    if not srel and relaxed_w.check(rt, rid, perm, st, fresh) == HAS:
-        cf = full.check(rt, rid, perm, st, fresh)
-        wild = cf == HAS
-        if cf == ERR and not lenient:
-            fail = True
-    excluded = set()
-    if wild:
-        for s in names:
-            c = full.check(rt, rid, perm, st, s, srel)
-            if c != HAS:
-                excluded.add(s)
-                if c == ERR and not lenient:
-                    fail = True
-    return "DEPTH" if fail else (ids, wild, excluded)
 
 
 def engine_answer(aclgpu, e, rt, rid, perm, st, srel=""):

@@ -6,7 +6,17 @@ and between the writes both sides answer the same random Check batches (1 ... 70
 kernels, the host-mapped small-batch path, the micro-batcher's single checks) and LookupResources requests (single and batched).  Every
 answer, every error code and every allowed-id set must be equal.  Writes land in the device snapshot as in-place patches, background
 compactions happen when the headroom runs low: the fuzz is what exercises patch -> query -> patch sequences nobody wrote a test for.
-The oracle is the checker (tests / tools only).  Exit code 1 and a dump of the first difference on a mismatch."""
+The oracle is the checker (tests / tools only).  Exit code 1 and a dump of the first difference on a mismatch.
+
+--reads (run_reads) is the same kind of write stream under the engine's other read paths, each held to the oracles between the writes:
+  a. LookupSubjects -- batches of 1, 5 and 33 resources, the n = 1 call, the string form, a group#member subject form -- against the C oracle's Check (C4
+     schema) or the contract of tests/subjects_contract.py (combine schema: ids, wildcard, excluded, or the call fails at the depth limit);
+  b. Explain witness: perm / err of the oracle's Check, a witness for every item a monotone permission grants, each through tests/explain_checker.py;
+  c. Explain proof (combine schema): every granted item proved, each proof through tests/proof_checker.py;
+  d. Explain denial (monotone permissions): the grants through tests/denial_checker.py;
+  e. multi-target LookupResources over every relation and permission, bit for bit the single-target rows, by name the oracle's lookups, and access_review;
+  f. lookup, subject and mixed cursors held open across later writes, compactions and recycled ids, with derived cursors and counts over them.
+--reads --dry is the oracle's half alone (no GPU).  --expiry also asks LookupSubjects and Explain about live and expired idempotency keys."""
 import argparse
 import os
 import random
@@ -51,20 +61,18 @@ definition pod {
 """
 
 
-def run(seed: int, steps: int, big: int = 70000, verbose: bool = True, burst: int = 25, universe: int = 1, compact_early: bool = False, schema: str = "c4",
-        recycle: bool = False, acyclic: bool = False) -> dict:
-    import aclgpu
-    from aclgpu import workloads
-    from oracle import orc
-    combine = schema == "combine"
-    schema_text = SCHEMA_COMBINE if combine else workloads.SCHEMA_C4
-
-    rng = random.Random(seed)
+def make_universe(rng, universe: int = 1):
+    """(users, groups, namespaces, pods): the names the write stream draws from.  The pods' namespaces are the stream's first draws from `rng`."""
     users = [f"u{i}" for i in range(160 * universe)]
     groups = [f"g{i}" for i in range(48 * universe)]
     nss = [f"n{i}" for i in range(8 * universe)]
     pods = [f"{rng.choice(nss)}/p{i}" for i in range(240 * universe)]
+    return users, groups, nss, pods
 
+
+def make_rand_tuple(rng, names, combine: bool = False, recycle: bool = False, acyclic: bool = False):
+    """-> rand_tuple(): one random relationship text over `names` (make_universe), every draw from `rng`; rand_tuple.fresh[0] counts the never-seen names"""
+    users, groups, nss, pods = names
     fresh = [0]
 
     def rand_tuple():
@@ -97,74 +105,127 @@ def run(seed: int, steps: int, big: int = 70000, verbose: bool = True, burst: in
         if k == 7: return f"namespace:{rng.choice(nss)}#viewer@user:{rng.choice(users)}"
         return f"namespace:{rng.choice(nss)}#viewer@group:{rng.choice(groups)}#member"
 
-    def rand_query():
-        k = rng.randrange(10)
-        u = rng.choice(users) if rng.random() < 0.97 else "stranger"
-        if combine and rng.random() < 0.45:
-            kk = rng.randrange(6)
-            if kk < 3: return ("pod", rng.choice(pods), rng.choice(("audit", "edit", "hidden", "everywhere", "vetted")), "user", u, "")
-            if kk == 3: return ("group", rng.choice(groups), "active", "user", u, "")
-            if kk == 4: return ("pod", rng.choice(pods), "view", "group", rng.choice(groups), "active")  # a non-monotone userset as the subject
-            return ("namespace", rng.choice(nss), "view", "group", rng.choice(groups), "member")
-        if k < 6: return ("pod", rng.choice(pods) if rng.random() < 0.97 else "n0/ghost", "view", "user", u, "")
-        if k < 8: return ("namespace", rng.choice(nss), "view", "user", u, "")
-        if k < 9: return ("group", rng.choice(groups), "member", "user", u, "")
-        return ("pod", rng.choice(pods), "view", "group", rng.choice(groups), "member")  # a userset as the subject
+    rand_tuple.fresh = fresh
+    return rand_tuple
 
+
+def rand_query(rng, names, combine: bool = False):
+    """one random Check item (rtype, rid, permission, stype, sid, srel) over `names`, every draw from `rng`"""
+    users, groups, nss, pods = names
+    k = rng.randrange(10)
+    u = rng.choice(users) if rng.random() < 0.97 else "stranger"
+    if combine and rng.random() < 0.45:
+        kk = rng.randrange(6)
+        if kk < 3: return ("pod", rng.choice(pods), rng.choice(("audit", "edit", "hidden", "everywhere", "vetted")), "user", u, "")
+        if kk == 3: return ("group", rng.choice(groups), "active", "user", u, "")
+        if kk == 4: return ("pod", rng.choice(pods), "view", "group", rng.choice(groups), "active")  # a non-monotone userset as the subject
+        return ("namespace", rng.choice(nss), "view", "group", rng.choice(groups), "member")
+    if k < 6: return ("pod", rng.choice(pods) if rng.random() < 0.97 else "n0/ghost", "view", "user", u, "")
+    if k < 8: return ("namespace", rng.choice(nss), "view", "user", u, "")
+    if k < 9: return ("group", rng.choice(groups), "member", "user", u, "")
+    return ("pod", rng.choice(pods), "view", "group", rng.choice(groups), "member")  # a userset as the subject
+
+
+def open_engine(schema_text: str, recycle: bool, compact_early: bool):
+    import aclgpu
     if recycle:
         os.environ["ACL_ID_QUARANTINE_MS"] = "0"  # (read when the schema is loaded) freed ids are reused by the next new name at once
     if compact_early:
         os.environ["ACL_COMPACTION_SLACK"] = "0"  # (read at acl_open) background compactions, adopted with the writes since replayed, on this small graph too
     try:
-        e = aclgpu.Engine(schema_text)
+        return aclgpu.Engine(schema_text)
     finally:
         os.environ.pop("ACL_COMPACTION_SLACK", None)
         os.environ.pop("ACL_ID_QUARANTINE_MS", None)
-    o = orc.Oracle(schema_text)
-    live = set()
+
+
+def load_initial(rand_tuple, o, e, live: set, universe: int = 1):
+    """the starting graph: 2500 draws of rand_tuple per universe, written to the oracle and (unless e is None) to the engine"""
+    import aclgpu
+    from oracle import orc
     init = list(dict.fromkeys(rand_tuple() for _ in range(2500 * universe)))
     for i in range(0, len(init), 500):
         o.write([(orc.OP_TOUCH, t) for t in init[i:i + 500]])
-        e.write([(aclgpu.OP_TOUCH, t) for t in init[i:i + 500]])
+        if e is not None:
+            e.write([(aclgpu.OP_TOUCH, t) for t in init[i:i + 500]])
     live.update(init)
+
+
+def write_batch(rng, step, rand_tuple, o, e, live: set, burst: int, stats: dict) -> bool:
+    """One write batch (TOUCH / CREATE / DELETE) on both sides, which accept it or reject it with the same code; e is None: the oracle alone.
+    -> True when it was accepted (`live` follows it)."""
+    import aclgpu
+    from oracle import orc
+    ups = []
+    pool = sorted(live) if live else []  # (once per batch: a delete picks from the relationships that exist)
+    for _ in range(rng.randrange(1, burst)):
+        q = rng.random()
+        if q < 0.5: ups.append((aclgpu.OP_TOUCH, rand_tuple()))
+        elif q < 0.5 + 0.1 / max(1, burst // 25): ups.append((aclgpu.OP_CREATE, rand_tuple()))
+        elif pool: ups.append((aclgpu.OP_DELETE, rng.choice(pool) if rng.random() < 0.9 else rand_tuple()))
+    ups = list({t: (op, t) for op, t in ups}.values())  # one update per relationship in a request
+    eo = ee = None
+    try:
+        o.write([({aclgpu.OP_TOUCH: orc.OP_TOUCH, aclgpu.OP_CREATE: orc.OP_CREATE, aclgpu.OP_DELETE: orc.OP_DELETE}[op], t) for op, t in ups])
+    except orc.OracleError as x:
+        eo = x.code
+    if e is not None:
+        try:
+            e.write(ups)
+        except aclgpu.AclError as x:
+            ee = x.code
+        assert eo == ee, f"step {step}: write outcome differs: oracle {eo}, engine {ee}: {ups}"
+    stats["writes"] += 1
+    if eo is None:
+        for op, t in ups:
+            (live.discard if op == aclgpu.OP_DELETE else live.add)(t)
+    else:
+        stats["write_errors"] += 1
+    return eo is None
+
+
+def filter_delete(rng, step, names, combine: bool, o, e, live: set, stats: dict) -> int:
+    """DeleteRelationships by one random filter on both sides (e is None: the oracle alone) -> how many relationships it removed; `live` is read back"""
+    users, groups, nss, pods = names
+    f = rng.choice([dict(rtype="pod", rid=rng.choice(pods)), dict(rtype="group", rel="member", stype="user", sid=rng.choice(users)),
+                    dict(rtype="namespace", rid=rng.choice(nss), rel="viewer")] +
+                   ([dict(rtype="pod", rel="banned", stype="user", sid="*"), dict(rtype="namespace", rel="banned")] if combine else []))
+    n1 = o.delete_by_filter(**f)
+    if e is not None:
+        n2 = e.delete_by_filter(**f)
+        assert n1 == n2, f"step {step}: delete_by_filter {f}: oracle removed {n1}, engine {n2}"
+    now = set(f"{a}:{b}#{c}@{d}:{x}" + (f"#{y}" if y else "") for t in ("group", "namespace", "pod") for a, b, c, d, x, y, _ in o.read(rtype=t))
+    live.clear()
+    live.update(now)
+    stats["filter_deletes"] += 1
+    return n1
+
+
+def run(seed: int, steps: int, big: int = 70000, verbose: bool = True, burst: int = 25, universe: int = 1, compact_early: bool = False, schema: str = "c4",
+        recycle: bool = False, acyclic: bool = False) -> dict:
+    import aclgpu
+    from aclgpu import workloads
+    from oracle import orc
+    combine = schema == "combine"
+    schema_text = SCHEMA_COMBINE if combine else workloads.SCHEMA_C4
+
+    rng = random.Random(seed)
+    names = users, groups, nss, pods = make_universe(rng, universe)
+    rand_tuple = make_rand_tuple(rng, names, combine, recycle, acyclic)
+
+    e = open_engine(schema_text, recycle, compact_early)
+    o = orc.Oracle(schema_text)
+    live = set()
+    load_initial(rand_tuple, o, e, live, universe)
     stats = {"writes": 0, "write_errors": 0, "filter_deletes": 0, "checks": 0, "lookups": 0, "single_checks": 0}
     e.batcher_start(4096, 100)
     t0 = time.time()
     for step in range(steps):
         r = rng.random()
         if r < 0.45:  # ---- a write batch: both sides accept it or reject it with the same code
-            ups = []
-            pool = sorted(live) if live else []  # (once per batch: a delete picks from the relationships that exist)
-            for _ in range(rng.randrange(1, burst)):
-                q = rng.random()
-                if q < 0.5: ups.append((aclgpu.OP_TOUCH, rand_tuple()))
-                elif q < 0.5 + 0.1 / max(1, burst // 25): ups.append((aclgpu.OP_CREATE, rand_tuple()))
-                elif pool: ups.append((aclgpu.OP_DELETE, rng.choice(pool) if rng.random() < 0.9 else rand_tuple()))
-            ups = list({t: (op, t) for op, t in ups}.values())  # one update per relationship in a request
-            eo = ee = None
-            try:
-                o.write([({aclgpu.OP_TOUCH: orc.OP_TOUCH, aclgpu.OP_CREATE: orc.OP_CREATE, aclgpu.OP_DELETE: orc.OP_DELETE}[op], t) for op, t in ups])
-            except orc.OracleError as x:
-                eo = x.code
-            try:
-                e.write(ups)
-            except aclgpu.AclError as x:
-                ee = x.code
-            assert eo == ee, f"step {step}: write outcome differs: oracle {eo}, engine {ee}: {ups}"
-            stats["writes"] += 1
-            if eo is None:
-                for op, t in ups:
-                    (live.discard if op == aclgpu.OP_DELETE else live.add)(t)
-            else:
-                stats["write_errors"] += 1
+            write_batch(rng, step, rand_tuple, o, e, live, burst, stats)
         elif r < 0.5:  # ---- DeleteRelationships by filter
-            f = rng.choice([dict(rtype="pod", rid=rng.choice(pods)), dict(rtype="group", rel="member", stype="user", sid=rng.choice(users)),
-                            dict(rtype="namespace", rid=rng.choice(nss), rel="viewer")] +
-                           ([dict(rtype="pod", rel="banned", stype="user", sid="*"), dict(rtype="namespace", rel="banned")] if combine else []))
-            n1, n2 = o.delete_by_filter(**f), e.delete_by_filter(**f)
-            assert n1 == n2, f"step {step}: delete_by_filter {f}: oracle removed {n1}, engine {n2}"
-            live = set(f"{a}:{b}#{c}@{d}:{x}" + (f"#{y}" if y else "") for t in ("group", "namespace", "pod") for a, b, c, d, x, y, _ in o.read(rtype=t))
-            stats["filter_deletes"] += 1
+            filter_delete(rng, step, names, combine, o, e, live, stats)
         elif r < 0.56 and not combine:  # ---- PostFilter's shape: ONE user's pairs -- CheckBulkPermissions itself twice (the second call may sweep the type for depth
             # errors and take the reverse walk: engine_keep.cpp no_object_is_deep; with a cycle behind some resource the calls stay forward and carry its depth errors),
             # then the keep mask of the same pairs.  Every permissionship, every error and every keep byte against the oracle.
@@ -184,7 +245,7 @@ def run(seed: int, steps: int, big: int = 70000, verbose: bool = True, burst: in
             stats["one_user_calls"] = stats.get("one_user_calls", 0) + 3
         elif r < 0.85:  # ---- a Check batch
             n = rng.choice([1, 1, 7, 64, 64, 900, 5000, big if step % 7 == 3 else 3000])
-            qs = [rand_query() for _ in range(min(n, 6000))]
+            qs = [rand_query(rng, names, combine) for _ in range(min(n, 6000))]
             qs = (qs * (n // len(qs) + 1))[:n]
             want = {q: o.check(*q) for q in set(qs)}
             if n == 1 and rng.random() < 0.5:  # the micro-batcher's single check
@@ -229,6 +290,627 @@ def run(seed: int, steps: int, big: int = 70000, verbose: bool = True, burst: in
     st = e.stats()
     stats.update({k: int(st[k]) for k in ("snapshot_builds", "snapshot_patches", "snapshot_compactions", "local_passes", "rev_local_passes", "ids_recycled", "keep_route_calls", "depth_sweeps") if k in st})
     e.close()
+    return stats
+
+
+def nonmono_members(defs) -> set:
+    """{(type, member)}: the relations and permissions with `-`, `&` or `.all()` anywhere beneath (a least fixpoint over references, arrows and userset subjects)"""
+    from oracle.pyoracle import Relation
+    nm = set()
+
+    def expr(t, x):
+        if x[0] in ("inter", "excl", "arrow_all"):
+            return True
+        if x[0] == "union":
+            return expr(t, x[1]) or expr(t, x[2])
+        if x[0] == "ref":
+            return (t, x[1]) in nm
+        if x[0] == "arrow":
+            return any((a[0], x[2]) in nm for a in defs[t].members[x[1]].allowed)
+        return False
+
+    changed = True
+    while changed:
+        changed = False
+        for t, d in defs.items():
+            for m, mem in d.members.items():
+                if (t, m) in nm:
+                    continue
+                if any(a[1] and a[1] != "*" and (a[0], a[1]) in nm for a in mem.allowed) if isinstance(mem, Relation) else expr(t, mem.expr):
+                    nm.add((t, m))
+                    changed = True
+    return nm
+
+
+def _ids_of(row):
+    import numpy as np
+    return np.flatnonzero(np.unpackbits(np.ascontiguousarray(row, dtype=np.uint32).view(np.uint8), bitorder="little")).tolist()
+
+
+class _Reads:
+    """The read rounds of run_reads: every kind computes what the oracles expect from the generator's own names and the oracle's live relationships, and --
+    unless the run is a dry one (e is None) -- holds the engine's answer to it.  Every draw comes from `rr`, never from the write stream's generator."""
+
+    def __init__(self, rr, names, schema_text, combine, recycle, o, e, live, stats, depth_case, cyclic):
+        from oracle.pyoracle import parse_schema
+        self.rr, self.names, self.schema, self.combine, self.recycle, self.o, self.e, self.live, self.stats = rr, names, schema_text, combine, recycle, o, e, live, stats
+        self.depth_case, self.cyclic = depth_case, cyclic
+        self.defs = parse_schema(schema_text)
+        self.nonmono = nonmono_members(self.defs)
+        self.targets = [(t, m) for t, d in self.defs.items() for m in d.members]  # every relation and permission, in slot order
+        self.version = 0         # moves with every accepted write
+        self.compactions = 0     # the engine's snapshot_compactions / ids_recycled as of the last look
+        self.recycled = 0
+        self.round_no = 0
+        self.cursors = []        # kind f: the cursors held open
+        self.subject_targets = 0  # depth case: LookupSubjects targets asked so far
+        self._rels = (-1, None)
+        self._tables = None
+        self._schema_names = None
+
+    # ---- the generator's side of the names
+    def rels(self):
+        """the live relationships as 6-tuples (cached until the next accepted write)"""
+        from oracle import orc
+        if self._rels[0] != self.version:
+            self._rels = (self.version, [orc.parse_rel(t) for t in sorted(self.live)])
+        return self._rels[1]
+
+    def names_of(self, t):
+        """every name of type `t` the generator knows: the universe, `stranger`, and the names in the live relationships"""
+        users, groups, nss, pods = self.names
+        out = set({"user": users + ["stranger"], "group": groups, "namespace": nss, "pod": pods}[t])
+        for r in self.rels():
+            if r[0] == t:
+                out.add(r[1])
+            if r[3] == t and r[4] != "*":
+                out.add(r[4])
+        return sorted(out)
+
+    def resources_with_relationships(self, t):
+        return sorted({r[1] for r in self.rels() if r[0] == t})
+
+    def first_seen_in_stream(self, t):
+        """names of type `t` in the live relationships that the universe does not hold: they were first named by a write of this stream"""
+        users, groups, nss, pods = self.names
+        known = set({"user": users, "group": groups, "namespace": nss, "pod": pods}[t])
+        return [n for n in self.resources_with_relationships(t) if n not in known]
+
+    def look_at_engine(self):
+        if self.e is not None:
+            st = self.e.stats()
+            self.compactions, self.recycled = int(st["snapshot_compactions"]), int(st["ids_recycled"])
+
+    def items(self, named):
+        """named items as acl_item_t records: every name goes through acl_intern (a name the snapshot has never seen gets its id here)"""
+        import numpy as np
+        import aclgpu
+        e = self.e
+        if self._tables is None:
+            self._tables = ({t: e.type_id(t) for t in self.defs}, {(t, m): e.relation_id(t, m) for t, d in self.defs.items() for m in d.members})
+        tid, rid_ = self._tables
+        out = np.zeros(len(named), dtype=aclgpu.ITEM_DTYPE)
+        for i, (rt, rid, perm, st, sid, srel) in enumerate(named):
+            out[i] = (tid[rt], rid_[(rt, perm)], e.intern(rt, rid), tid[st], rid_[(st, srel)] if srel else aclgpu.NO_RELATION, e.intern(st, sid))
+        return out
+
+    def schema_names(self):
+        if self._schema_names is None:
+            e = self.e
+            self._schema_names = ({e.type_id(t): t for t in self.defs}, {(e.type_id(t), e.relation_id(t, m)): m for t, d in self.defs.items() for m in d.members})
+        return self._schema_names
+
+    def hop_names(self, raw):
+        """acl_explain_hop_t records -> relationship 6-tuples (a hop is a stored relationship: both its ids are live, their names are their own)"""
+        e = self.e
+        tname, rname = self.schema_names()
+        out = []
+        for h in raw:
+            rt, st = tname[int(h["rtype"])], tname[int(h["stype"])]
+            sid = "*" if int(h["flags"]) & 1 else e.object_name(st, int(h["sid"]))
+            srel = "" if int(h["srel"]) == 0xFFFF else rname[(int(h["stype"]), int(h["srel"]))]
+            out.append((rt, e.object_name(rt, int(h["rid"])), rname[(int(h["rtype"]), int(h["relation"]))], st, sid, srel))
+        return out
+
+    def absent_names(self, raw, named_item):
+        """acl_item_t records of a proof's absences -> Check items; the subject is the item's own (asserted by id), so its name is the generator's"""
+        e = self.e
+        tname, rname = self.schema_names()
+        out = []
+        for a in raw:
+            rt, st = tname[int(a["resource_type"])], tname[int(a["subject_type"])]
+            srel = "" if int(a["subject_relation"]) == 0xFFFF else rname[(int(a["subject_type"]), int(a["subject_relation"]))]
+            sid = named_item[4] if (st == named_item[3] and int(a["subject_id"]) == e.intern(st, named_item[4])) else e.object_name(st, int(a["subject_id"]))
+            out.append((rt, e.object_name(rt, int(a["resource_id"])), rname[(int(a["resource_type"]), int(a["permission"]))], st, sid, srel))
+        return out
+
+    # ---- a. LookupSubjects
+    def subjects_expected(self, rt, perm, st, srel, rids, contract_cache):
+        """per resource: (ids, wildcard, excluded) by name, or "DEPTH".  C4: the C oracle's Check over every name; combine: the contract of
+        tests/subjects_contract.py through the Python oracle"""
+        names = [n for n in self.names_of(st)]
+        if not self.combine:
+            return [({s for s in names if self.o.check(rt, rid, perm, st, s, srel) == (2, 0)}, False, set()) for rid in rids]
+        from tests.subjects_contract import SubjectsContract
+        if st not in contract_cache:
+            contract_cache[st] = SubjectsContract(self.schema, self.rels(), st)
+        return [contract_cache[st].answer(rt, rid, perm, srel, names) for rid in rids]
+
+    def subjects_compare(self, where, rt, perm, st, srel, rids, want):
+        """one acl_lookup_subjects_batch call against `want`; a resource whose contract is DEPTH fails the whole call"""
+        import aclgpu
+        e = self.e
+        ids = [e.intern(rt, r) for r in rids]
+        if any(w == "DEPTH" for w in want):
+            try:
+                e.lookup_subjects_ids_batch(rt, perm, st, srel, ids, want_excluded=True)
+            except aclgpu.AclError as x:
+                assert x.code == aclgpu.ERR_DEPTH, f"{where}: {x}"
+                return None
+            raise AssertionError(f"{where}: the contract of {[r for r, w in zip(rids, want) if w == 'DEPTH']} is DEPTH, the engine answered")
+        bms, counts, flags, ex = e.lookup_subjects_ids_batch(rt, perm, st, srel, ids, want_excluded=True)
+        for i, (rid, (wids, wild, wex)) in enumerate(zip(rids, want)):
+            got = set(e.bitmap_names(st, bms[i]))
+            assert got == wids, f"{where}: {rt}:{rid}#{perm} subjects {st}#{srel}: engine only {sorted(got - wids)[:5]}, contract only {sorted(wids - got)[:5]}"
+            assert int(counts[i]) == len(_ids_of(bms[i])) == len(wids), f"{where}: {rt}:{rid}#{perm}: count {int(counts[i])}, row {len(_ids_of(bms[i]))}, contract {len(wids)}"
+            assert bool(flags[i] & 1) == wild, f"{where}: {rt}:{rid}#{perm}: wildcard flag {int(flags[i])}, contract {wild}"
+            gex = set(e.bitmap_names(st, ex[i]))
+            assert gex == wex, f"{where}: {rt}:{rid}#{perm}: excluded {sorted(gex ^ wex)[:5]}"
+        return bms, counts, flags
+
+    def round_subjects(self, step):
+        import numpy as np
+        rr, e, st_ = self.rr, self.e, self.stats
+        where = f"step {step} (LookupSubjects)"
+        perms = [("pod", "view"), ("namespace", "view"), ("group", "member")]
+        if self.combine:
+            perms += [("pod", "audit"), ("pod", "edit"), ("pod", "hidden"), ("pod", "everywhere"), ("pod", "vetted"), ("group", "active")]
+        cache = {}
+        if self.depth_case:  # one target a round, three in all: picked on the oracle side, by turns a resource with a Check that ends at the depth limit and one without
+            rt, perm = rr.choice([("pod", "view"), ("pod", "hidden"), ("pod", "edit")])
+            users = self.names_of("user")
+            pool = self.resources_with_relationships(rt)
+            rr.shuffle(pool)
+            want_err = self.subject_targets % 2 == 0
+            if want_err:  # a user whose LookupResources fails has a candidate whose Check errs: that resource's LookupSubjects reaches the user and must fail too
+                from tests.subjects_contract import SubjectsContract
+                cache["user"] = SubjectsContract(self.schema, self.rels(), "user")
+                u = next((u for u in rr.sample(users, 40) if self.lookup_expected(rt, perm, "user", u)[0] == "err"), None)
+                pick = u and next((r for r in pool if self.o.check(rt, r, perm, "user", u)[1] and cache["user"].relaxed.check(rt, r, perm, "user", u) == "HAS"), None)
+            else:
+                pick = next((r for r in pool[:40] if not any(self.o.check(rt, r, perm, "user", u)[1] for u in users)), None)
+            if pick is None:
+                return False
+            self.subject_targets += 1
+            want = self.subjects_expected(rt, perm, "user", "", [pick], cache)
+            st_["subj_rows"] += 1
+            st_["subj_depth"] += want[0] == "DEPTH"
+            st_["subj_nonempty"] += want[0] != "DEPTH" and bool(want[0][0])
+            if e is not None:
+                self.subjects_compare(where, rt, perm, "user", "", [pick], want)
+            return True
+        rt, perm = rr.choice(perms)
+        # 1, 5 or 33 resources by turns; on the combine schema 33 once a run (the contract's Python oracles need 0.1 s a resource)
+        n = (5, 1, 33)[self.stats["rounds_subjects"] % 3] if not self.combine or self.stats["rounds_subjects"] < 3 else (5, 1)[self.stats["rounds_subjects"] % 2]
+        pool = self.resources_with_relationships(rt)
+        if self.combine:  # (most pods grant `audit`, `everywhere` or `vetted` to nobody: four resources in five come from those that some of forty random users hold the permission on)
+            held = set()
+            for u in rr.sample(self.names[0], 40):
+                if len(held) >= n:
+                    break
+                w = self.lookup_expected(rt, perm, "user", u)
+                held |= (w[1] if w[0] == "ok" else set()) & set(pool)
+            held = sorted(held)
+            rr.shuffle(held)
+            rest = [r for r in pool if r not in set(held)]
+            rr.shuffle(rest)
+            pool = [held.pop() if held and (i % 5 or not rest) else rest.pop() for i in range(min(40, len(pool)))]
+        empty ={"pod": "n0/", "namespace": "", "group": ""}[rt] + f"nothing-{self.round_no}"  # interned by this call, never written
+        if n == 1:  # (the batch is one resource with relationships -- under recycling a name first seen in this stream; the empty one is asked alone below)
+            rids = rr.sample(self.first_seen_in_stream(rt) if self.recycle and self.first_seen_in_stream(rt) else pool, 1)
+            st_["subj_first_seen"] += rids[0] in self.first_seen_in_stream(rt)
+        else:
+            extra = [empty]
+            if self.recycle and self.first_seen_in_stream(rt):
+                extra.append(rr.choice(self.first_seen_in_stream(rt)))
+                st_["subj_first_seen"] += 1
+            rids = list(dict.fromkeys(extra + rr.sample(pool, min(len(pool), n - len(extra)))))
+        want = self.subjects_expected(rt, perm, "user", "", rids, cache)
+        want_empty = self.subjects_expected(rt, perm, "user", "", [empty], cache) if n == 1 else None
+        k = rr.randrange(len(rids))
+        g_rid = rr.choice(rids)
+        want_g = self.subjects_expected(rt, perm, "group", "member", [g_rid], cache)
+        for w in want + (want_empty or []):
+            st_["subj_rows"] += 1
+            st_["subj_depth"] += w == "DEPTH"
+            st_["subj_nonempty"] += w != "DEPTH" and bool(w[0])
+            st_["subj_empty"] += w != "DEPTH" and not w[0] and not w[1]
+            st_["subj_wildcard"] += w != "DEPTH" and w[1]
+        st_["subj_interned_only"] += 1
+        if e is None:
+            return True
+        got = self.subjects_compare(where, rt, perm, "user", "", rids, want)
+        if want_empty is not None:
+            self.subjects_compare(where, rt, perm, "user", "", [empty], want_empty)
+        if got is not None:  # the n = 1 call equals its row of the batch; the string form answers the same by name
+            b1, c1, f1 = e.lookup_subjects_ids_batch(rt, perm, "user", "", [e.intern(rt, rids[k])])
+            words = min(b1.shape[1], got[0].shape[1])
+            assert np.array_equal(b1[0][:words], got[0][k][:words]) and not b1[0][words:].any() and c1[0] == got[1][k] and f1[0] == got[2][k], f"{where}: n = 1 row of {rt}:{rids[k]}#{perm}"
+            assert e.lookup_subjects(rt, rids[k], perm, "user") == want[k], f"{where}: string form of {rt}:{rids[k]}#{perm}"
+        self.subjects_compare(where + " group#member", rt, perm, "group", "member", [g_rid], want_g)
+        return True
+
+    # ---- b. Explain witness
+    def explain_items(self, n):
+        rr = self.rr
+        users, groups, nss, pods = self.names
+        qs = [rand_query(rr, self.names, self.combine) for _ in range(n)]
+        if self.combine:  # group#member is the one monotone permission rand_query asks on this schema: relations without `-`, `&`, `.all()` beneath fill the round up
+            for _ in range(n):
+                k = rr.randrange(4)
+                u = rr.choice(users)
+                qs.append(("group", rr.choice(groups), "member", "user", u, "") if k == 0 else ("namespace", rr.choice(nss), "viewer", "user", u, "") if k == 1 else
+                          ("pod", rr.choice(pods), "auditor", "user", u, "") if k == 2 else ("group", rr.choice(groups), "member", "group", rr.choice(groups), "member"))
+        return qs
+
+    def round_explain(self, step):
+        import aclgpu
+        from tests import explain_checker as X
+        rr, e, o, st_ = self.rr, self.e, self.o, self.stats
+        qs = self.explain_items(rr.choice([64, 150, 300]) // (2 if self.combine else 1))
+        want = [tuple(o.check(*q)) for q in qs]
+        st_["explain_items"] += len(qs)
+        granted_mono = [i for i, (q, w) in enumerate(zip(qs, want)) if w == (2, 0) and (q[0], q[2]) not in self.nonmono]
+        st_["witnesses"] += len(granted_mono)
+        st_["replayed"] += min(32, len(granted_mono))
+        if e is None:
+            return True
+        perm, err, flags, off, raw = e.explain_ids(self.items(qs))
+        relset = set(self.rels())
+        replayed = 0
+        for i, q in enumerate(qs):
+            where = f"step {step} (Explain) {q} (item {i})"
+            assert (int(perm[i]), int(err[i])) == want[i], f"{where}: engine {(int(perm[i]), int(err[i]))}, oracle {want[i]}"
+            hops = raw[off[i]:off[i + 1]]
+            if want[i] != (2, 0):
+                assert int(flags[i]) == 0 and not len(hops), f"{where}: not granted, flags {int(flags[i])}, {len(hops)} hops"
+            elif (q[0], q[2]) in self.nonmono:
+                assert int(flags[i]) == aclgpu.EXPLAIN_UNSUPPORTED and not len(hops), f"{where}: flags {int(flags[i])}, {len(hops)} hops"
+            else:
+                assert int(flags[i]) == aclgpu.EXPLAIN_WITNESS, f"{where}: granted by a monotone permission, flags {int(flags[i])}"
+                try:
+                    X.check_witness(self.schema, relset, q, self.hop_names(hops), replay_it=replayed < 32)
+                except AssertionError as x:
+                    raise AssertionError(f"{where}: {x}") from None
+                replayed += 1
+        return True
+
+    # ---- c. Explain proof
+    def round_proof(self, step):
+        import aclgpu
+        from tests import proof_checker as P
+        rr, e, o, st_ = self.rr, self.e, self.o, self.stats
+        users, groups, nss, pods = self.names
+        qs = [rand_query(rr, self.names, True) for _ in range(48)]
+        for _ in range(48):
+            k = rr.randrange(7)
+            u = rr.choice(users)
+            qs.append(("group", rr.choice(groups), "active", "user", u, "") if k == 6 else
+                      ("pod", rr.choice(pods), ("audit", "edit", "hidden", "everywhere", "vetted", "view")[k], "user", u, ""))
+        want = [tuple(o.check(*q)) for q in qs]
+        granted = [i for i, w in enumerate(want) if w == (2, 0)]
+        st_["proof_items"] += len(qs)
+        st_["proofs"] += len(granted)
+        if e is None:
+            P.ProofChecker(self.schema, self.rels())  # (the dry run pays for the checker's oracles as the real one does)
+            return True
+        chk = P.ProofChecker(self.schema, self.rels())
+        perm, err, flags, off, raw, aoff, araw = e.explain_proof_ids(self.items(qs))
+        for i, q in enumerate(qs):
+            where = f"step {step} (Explain proof) {q} (item {i})"
+            assert (int(perm[i]), int(err[i])) == want[i], f"{where}: engine {(int(perm[i]), int(err[i]))}, oracle {want[i]}"
+            hops, absent = raw[off[i]:off[i + 1]], araw[aoff[i]:aoff[i + 1]]
+            if want[i] != (2, 0):
+                assert int(flags[i]) == 0 and not len(hops) and not len(absent), f"{where}: not granted, flags {int(flags[i])}"
+                continue
+            assert int(flags[i]) == (aclgpu.EXPLAIN_PROOF if (q[0], q[2]) in self.nonmono else aclgpu.EXPLAIN_WITNESS), f"{where}: granted, flags {int(flags[i])}"
+            try:
+                chk.check(q, self.hop_names(hops), self.absent_names(absent, q))
+            except AssertionError as x:
+                raise AssertionError(f"{where}: {x}") from None
+        return True
+
+    # ---- d. Explain denial
+    def round_denial(self, step):
+        import aclgpu
+        from tests import denial_checker as D
+        rr, e, st_ = self.rr, self.e, self.stats
+        orcs = D.Oracles(self.schema, self.rels())
+        cand = [q for q in self.explain_items(120) if (q[0], q[2]) not in self.nonmono]
+        denied = []
+        for q in dict.fromkeys(cand):
+            if orcs.denied(q):
+                denied.append(q)
+                if len(denied) == 8:
+                    break
+        if not denied:
+            return False
+        # the restatement's own answer: which of them have a grant at all, and -- in a dry run -- the lists the checker is timed on
+        restated = [D.grants_of(orcs.defs, D.closure(orcs.defs, orcs.rels, q[:3]), q[3], q[5]) for q in denied]
+        st_["denied_items"] += len(denied)
+        st_["denied_with_grants"] += sum(bool(g) for g in restated)
+        if e is None:
+            for k, (q, g) in enumerate(zip(denied, restated)):
+                D.check_grants(orcs, q, [(t, o_, m, lv) for (t, o_, m), lv in g.items()], seed=step)
+            return True
+        perm, err, flags, off, recs = e.explain_denial_ids(self.items(denied))
+        for k, q in enumerate(denied):
+            where = f"step {step} (Explain denial) {q}"
+            assert (int(perm[k]), int(err[k])) == (1, 0), f"{where}: engine {(int(perm[k]), int(err[k]))}, the oracles deny it without error"
+            assert int(flags[k]) == aclgpu.EXPLAIN_DENIAL, f"{where}: flags {int(flags[k])}"
+            grants = D.name_grants(e, self.schema, recs[off[k]:off[k + 1]])
+            assert bool(grants) == bool(restated[k]), f"{where}: {len(grants)} grants, the closure has {len(restated[k])}"
+            try:  # (every grant written alone grants the item at its level, by both oracles; no other single write does)
+                D.check_grants(orcs, q, grants, seed=step)
+            except AssertionError as x:
+                raise AssertionError(f"{where}: {x}") from None
+        return True
+
+    # ---- e. multi-target LookupResources
+    def lookup_expected(self, rt, pm, st, sid, srel=""):
+        """("ok", names) or ("err", code): a lookup whose candidate's Check errs fails as a whole"""
+        try:
+            return ("ok", set(self.o.lookup(rt, pm, st, sid, srel)))
+        except Exception as ex:  # noqa: BLE001
+            if getattr(ex, "code", None) is None:
+                raise
+            return ("err", ex.code)
+
+    def round_multi(self, step):
+        import numpy as np
+        import aclgpu
+        rr, e, st_ = self.rr, self.e, self.stats
+        users = self.names_of("user")
+        # 1, 3 or 20 subjects by turns; with group cycles 20 once a run (the oracle's brute-force lookups need 20 ms a row there), and never in the depth case
+        k = self.stats["rounds_multi"]
+        subs = rr.sample(users, (1, 1, 1, 1, 1, 3)[k % 6] if self.depth_case else (3, 1)[k % 2] if self.cyclic and k >= 3 else (3, 1, 20)[k % 3])
+        targets = self.targets
+        want = [[self.lookup_expected(rt, pm, "user", u) for u in subs] for rt, pm in targets]
+        failing = [j for j in range(len(targets)) if any(w[0] == "err" for w in want[j])]
+        st_["multi_rows"] += len(subs) * len(targets)
+        st_["multi_failing_targets"] += len(failing)
+        review_u = rr.randrange(len(subs))
+        if e is None:
+            return True
+        where = f"step {step} (multi-target lookup, {len(subs)} subjects)"
+        sids = [e.intern("user", u) for u in subs]
+        singles = {}
+        for j, (rt, pm) in enumerate(targets):  # every target alone: its rows by name against the oracle, or its failure
+            if j in failing:
+                try:
+                    e.lookup_ids_batch(rt, pm, "user", "", sids)
+                except aclgpu.AclError as x:
+                    assert x.code == aclgpu.ERR_DEPTH, f"{where}: {rt}#{pm}: {x}"
+                    continue
+                raise AssertionError(f"{where}: the oracle fails {rt}#{pm}, the engine answered")
+            singles[j] = e.lookup_ids_batch(rt, pm, "user", "", sids)
+            for i, u in enumerate(subs):
+                got = set(e.bitmap_names(rt, singles[j][0][i]))
+                assert got == want[j][i][1], f"{where}: {rt}#{pm}@user:{u}: engine only {sorted(got - want[j][i][1])[:5]}, oracle only {sorted(want[j][i][1] - got)[:5]}"
+        if failing:  # a candidate's error fails the call (no ACL_FLAG_LENIENT_LOOKUP here); the targets that answer alone still answer together
+            try:
+                e.lookup_ids_multi(targets, "user", "", sids)
+            except aclgpu.AclError as x:
+                assert x.code == aclgpu.ERR_DEPTH and "max depth exceeded" in str(x), f"{where}: {x}"
+            else:
+                raise AssertionError(f"{where}: the oracle fails {[targets[j] for j in failing]}, the multi call answered")
+        ok = [j for j in range(len(targets)) if j not in failing]
+        rows, counts = e.lookup_ids_multi([targets[j] for j in ok], "user", "", sids)
+        for k, j in enumerate(ok):  # bit for bit what the single-target call answers
+            assert np.array_equal(rows[k], singles[j][0]) and np.array_equal(counts[:, k], singles[j][1]), f"{where}: {targets[j]} differs from lookup_ids_batch"
+        u = subs[review_u]
+        try:
+            rev = e.access_review("user", u)
+        except aclgpu.AclError as x:
+            assert x.code == aclgpu.ERR_DEPTH and any(want[j][review_u][0] == "err" for j in range(len(targets))), f"{where}: access_review of {u}: {x}"
+        else:
+            assert all(want[j][review_u][0] == "ok" for j in range(len(targets))), f"{where}: access_review of {u} answered, the oracle fails a target"
+            assert rev == {t: want[j][review_u][1] for j, t in enumerate(targets)}, f"{where}: access_review of {u}"
+        return True
+
+    # ---- f. cursors held across writes
+    def cursor_chain(self, cur, row, limit):
+        out, after = [], None
+        while True:
+            ids, more = cur.page(row, after, limit)
+            out += ids.tolist()
+            if not more:
+                return out
+            assert len(ids), "a page says `more` and holds no id"
+            after = out[-1]
+
+    def cursor_open(self, step, kind, rt, perm, st):
+        """one cursor: its expected rows by name on the oracle side; on the engine its rows paged whole, held to them by name, the ids remembered"""
+        import aclgpu
+        rr, e = self.rr, self.e
+        where = f"step {step} (cursor open {kind} {rt}#{perm})"
+        users, groups = self.names_of("user"), self.names_of("group")
+        if kind == "subjects":
+            keys = rr.sample(self.resources_with_relationships(rt), 3)
+            want = self.subjects_expected(rt, perm, "user", "", keys, {})
+            if any(w == "DEPTH" for w in want):
+                want = None
+            else:
+                flags, want = [w[1] for w in want], [w[0] for w in want]
+        else:
+            keys = [("user", "", u) for u in rr.sample(users, 3)] + ([("group", "member", g) for g in rr.sample(groups, 2)] if kind == "mixed" else [])
+            w = [self.lookup_expected(rt, perm, s, n, r) for s, r, n in keys]
+            want, flags = (None if any(x[0] == "err" for x in w) else [x[1] for x in w]), [False] * len(keys)
+        held = dict(kind=kind, row_type=st if kind == "subjects" else rt, want=want, version=self.version, reads=0, cur=None, ids=None, names=None, flags=flags)
+        if e is None:
+            return held if want is not None else None
+        try:
+            if kind == "subjects":
+                cur = e.subjects_cursor(rt, perm, "user", "", [e.intern(rt, k) for k in keys])
+            elif kind == "lookup":
+                cur = e.lookup_cursor(rt, perm, "user", "", [e.intern("user", n) for _s, _r, n in keys])
+            else:
+                cur = e.lookup_cursor_mixed(rt, perm, [(s, r, e.intern(s, n)) for s, r, n in keys])
+        except aclgpu.AclError as x:
+            assert want is None and x.code == aclgpu.ERR_DEPTH, f"{where}: {x}"
+            return None
+        assert want is not None, f"{where}: the oracle fails a row, the engine opened the cursor"
+        self.look_at_engine()
+        held.update(cur=cur, ids=[], names=[], compactions=self.compactions, recycled=self.recycled)
+        _rev, counts, cflags = cur.info()
+        for i in range(len(keys)):
+            ids = self.cursor_chain(cur, i, 500)
+            pid, names, more = cur.page_names(i, None, len(ids) + 1)
+            assert pid.tolist() == ids and not more and int(counts[i]) == len(ids), f"{where}: row {i}: pages, names and count disagree"
+            assert set(names) == want[i] and len(names) == len(want[i]), f"{where}: row {i} ({keys[i]}): engine only {sorted(set(names) - want[i])[:5]}, oracle only {sorted(want[i] - set(names))[:5]}"
+            assert bool(cflags[i] & 1) == bool(flags[i]), f"{where}: row {i}: wildcard flag {int(cflags[i])}"
+            held["ids"].append(ids)
+            held["names"].append(names)
+        return held
+
+    def cursor_read(self, step, h):
+        """a cursor opened before at least one accepted write: its rows are what they were"""
+        import aclgpu
+        st_ = self.stats
+        st_["cursors_read_later"] += 1
+        h["reads"] += 1
+        if self.e is None:
+            return
+        self.look_at_engine()
+        st_["cursors_read_after_compaction"] += self.compactions > h["compactions"]
+        moved = self.recycled > h["recycled"]
+        st_["cursors_read_after_recycling"] += moved
+        cur = h["cur"]
+        for i, ids in enumerate(h["ids"]):
+            where = f"step {step} (cursor {h['kind']} opened {self.version - h['version']} writes ago, row {i})"
+            for limit in (1, 7, 500):
+                got = self.cursor_chain(cur, i, limit)
+                assert got == ids, f"{where}: limit {limit}: {len(got)} ids, {len(ids)} at the open; differ at {sorted(set(got) ^ set(ids))[:5]}"
+            try:
+                pid, names, _more = cur.page_names(i, None, len(ids) + 1)
+            except aclgpu.AclError as x:
+                assert moved and x.code == aclgpu.ERR_FAILED_PRECONDITION, f"{where}: page_names: {x}"
+                st_["page_names_refused"] += 1
+            else:
+                assert pid.tolist() == ids and names == h["names"][i], f"{where}: page_names answers other names than at the open"
+
+    def cursor_derive(self, step, a, b):
+        """any & all & ~none over two cursors of one direction and revision: the set algebra of the remembered ids"""
+        rr, e = self.rr, self.e
+        rows = [(c, r) for c, h in enumerate((a, b)) for r in range(len(h["want"])) if not h["flags"][r]]  # (a wildcard row is no bitmap: derive refuses it)
+        if len(rows) < 4:
+            return
+        self.stats["derives"] += 1
+        exprs = [(rr.sample(rows, 2), rr.sample(rows, 1), rr.sample(rows, 1)) for _ in range(3)]  # (drawn in a dry run too: one stream for both)
+        if e is None:
+            return
+        S = lambda ref: set((a, b)[ref[0]]["ids"][ref[1]])  # noqa: E731
+        want = [sorted(((S(any_[0]) | S(any_[1])) & S(all_[0])) - S(none[0])) for any_, all_, none in exprs]
+        counts = e.count_rows([a["cur"], b["cur"]], exprs)
+        with e.derive_cursor([a["cur"], b["cur"]], exprs) as d:
+            for k, w in enumerate(want):
+                got = self.cursor_chain(d, k, 7)
+                assert got == w and int(counts[k]) == len(w), f"step {step} (derived cursor, expression {k}): {len(got)} ids, count {int(counts[k])}, set algebra {len(w)}"
+
+    def round_cursors(self, step):
+        rr, st_ = self.rr, self.stats
+        old = [h for h in self.cursors if h["version"] < self.version]
+        if old:
+            for h in old:
+                self.cursor_read(step, h)
+            pairs = [(a, b) for a in old for b in old if a is not b and a.get("pair") is b]
+            if pairs:
+                self.cursor_derive(step, *pairs[0])
+            for h in old:  # some are closed here, the rest when the engine closes
+                if h["reads"] >= 3 and (h["reads"] >= 6 or rr.random() < 0.3):
+                    if h["cur"] is not None:
+                        h["cur"].close()
+                    self.cursors.remove(h)
+                    st_["cursors_closed"] += 1
+            return True
+        if len(self.cursors) >= 3:
+            return False
+        perms = [("pod", "view"), ("namespace", "view"), ("group", "member")] + ([("pod", "edit"), ("pod", "hidden"), ("pod", "vetted")] if self.combine else [])
+        rt, perm = rr.choice(perms)
+        if len(self.cursors) <= 1:  # a pair of one direction, opened on one snapshot: the sources of a derived cursor
+            kinds = rr.choice([("lookup", "mixed"), ("subjects", "subjects")])
+        else:
+            kinds = (rr.choice(["lookup", "mixed", "subjects"]),)
+        opened = [h for h in (self.cursor_open(step, k, rt, perm, "user") for k in kinds) if h is not None]
+        if len(opened) == 2:
+            opened[0]["pair"], opened[1]["pair"] = opened[1], opened[0]
+        self.cursors += opened
+        st_["cursors_opened"] += len(opened)
+        return bool(opened)
+
+
+def run_reads(seed: int, steps: int, schema: str = "c4", acyclic: bool = False, recycle: bool = False, compact_early: bool = False, universe: int = 1, engine: bool = True,
+              verbose: bool = True, depth_case: bool = False, read_share: float = 0.75) -> dict:
+    """The read paths the Check campaign does not reach, on the same kind of live graph: between run()'s writes (TOUCH / CREATE / DELETE batches, filter
+    deletes) a step is, with probability `read_share`, one read round -- LookupSubjects, Explain witness, Explain proof (combine schema), Explain denial,
+    multi-target LookupResources with access_review, or cursors held open across the writes (paged, named, derived, counted) -- each held to the oracles.
+    engine=False: the oracle's half alone, same stream, same expected values, no GPU: what a case costs on the oracle side and whether its stream covers what
+    it is for.  depth_case: kinds a and e only, one LookupSubjects target a round and three in all (a cyclic combine graph: the Python oracle needs over a second
+    per target there), picked by turns with and without a Check that ends at the depth limit.  -> stats."""
+    from aclgpu import workloads
+    from oracle import orc
+    combine = schema == "combine"
+    schema_text = SCHEMA_COMBINE if combine else workloads.SCHEMA_C4
+    rng = random.Random(seed)
+    rr = random.Random(f"reads/{seed}")  # (the write stream's generator is never drawn from by a read)
+    names = make_universe(rng, universe)
+    rand_tuple = make_rand_tuple(rng, names, combine, recycle, acyclic)
+    e = open_engine(schema_text, recycle, compact_early) if engine else None
+    o = orc.Oracle(schema_text)
+    live = set()
+    load_initial(rand_tuple, o, e, live, universe)
+    stats = {k: 0 for k in ("writes", "write_errors", "filter_deletes", "writes_accepted", "rounds", "skipped", "subj_rows", "subj_nonempty", "subj_empty", "subj_depth",
+                            "subj_wildcard", "subj_interned_only", "subj_first_seen", "explain_items", "witnesses", "replayed", "proof_items", "proofs", "denied_items",
+                            "denied_with_grants", "multi_rows", "multi_failing_targets", "cursors_opened", "cursors_read_later", "cursors_read_after_compaction",
+                            "cursors_read_after_recycling", "page_names_refused", "cursors_closed", "derives")}
+    reads = _Reads(rr, names, schema_text, combine, recycle, o, e, live, stats, depth_case, not acyclic)
+    kinds = ["subjects", "multi"] if depth_case else ["subjects", "explain", "explain", "denial", "multi", "cursors", "cursors"] + (["proof"] if combine else [])
+    for k in dict.fromkeys(kinds):
+        stats["rounds_" + k], stats["seconds_" + k] = 0, 0.0
+    todo = []
+    t0 = time.time()
+    for step in range(steps):
+        if rng.random() < 0.9:
+            accepted = write_batch(rng, step, rand_tuple, o, e, live, 25, stats)
+        else:
+            accepted = filter_delete(rng, step, names, combine, o, e, live, stats) > 0
+        if accepted:
+            reads.version += 1
+            stats["writes_accepted"] += 1
+        if rr.random() < read_share:
+            if not todo:  # every enabled kind once (cursors twice) in a shuffled order, then again
+                # (the kinds whose oracle side is dear -- LookupSubjects, denial, multi-target lookups outside the depth case -- run four rounds, then the cheap ones go on)
+                todo = [k for k in kinds if not (k == "subjects" and depth_case and reads.subject_targets >= 3) and
+                        not (k in ("subjects", "denial", "multi") and not depth_case and stats["rounds_" + k] >= 4)]
+                rr.shuffle(todo)
+            kind = todo.pop()
+            reads.round_no += 1
+            t1 = time.time()
+            done = getattr(reads, "round_" + kind)(step)
+            stats["seconds_" + kind] = round(stats["seconds_" + kind] + time.time() - t1, 2)
+            stats["rounds"] += 1
+            stats["rounds_" + kind] += bool(done)
+            stats["skipped"] += not done
+        if verbose and step % 10 == 9:
+            print(f"step {step + 1}/{steps}: {stats}, {len(live)} relationships, {time.time() - t0:.1f} s", file=sys.stderr, flush=True)
+    if not depth_case and not reads.cursors:  # (at least one cursor is still open when the engine closes)
+        reads.cursors += [h for h in [reads.cursor_open(steps, "lookup", "group", "member", "user")] if h is not None]
+    stats["cursors_left_open"] = len(reads.cursors)
+    stats["seconds"] = round(time.time() - t0, 1)
+    if e is not None:
+        st = e.stats()
+        stats.update({k: int(st[k]) for k in ("snapshot_builds", "snapshot_patches", "snapshot_compactions", "ids_recycled", "rev_multi_passes") if k in st})
+        e.close()  # (with the cursors still held: the engine closes them)
     return stats
 
 
@@ -301,6 +983,8 @@ def run_expiry(seed: int, steps: int, verbose: bool = True) -> dict:
 
     import aclgpu
     from oracle import orc
+    from aclgpu.text import parse_relationship
+    from oracle.orc import parse_rel
 
     rng = random.Random(seed)
     b = json.load(open(os.path.join(ROOT, "tests", "golden", "bootstrap.json")))
@@ -315,7 +999,9 @@ def run_expiry(seed: int, steps: int, verbose: bool = True) -> dict:
     locks = [f"lk{i:x}" for i in range(30)]
     users = [f"u{i}" for i in range(20)]
     nss = [f"ns{i}" for i in range(12)]
-    stats = {"writes": 0, "write_errors": 0, "clock_moves": 0, "checks": 0, "reads": 0}
+    stats = {"writes": 0, "write_errors": 0, "clock_moves": 0, "checks": 0, "reads": 0, "subject_lookups": 0, "subject_rows_nonempty": 0, "live_keys_explained": 0,
+             "expired_keys_explained": 0}
+    written_keys = set()
     OPS = {aclgpu.OP_TOUCH: orc.OP_TOUCH, aclgpu.OP_CREATE: orc.OP_CREATE, aclgpu.OP_DELETE: orc.OP_DELETE}
     for step in range(steps):
         r = rng.random()
@@ -346,6 +1032,8 @@ def run_expiry(seed: int, steps: int, verbose: bool = True) -> dict:
             assert eo == ee, f"step {step}: write outcome differs: oracle {eo}, engine {ee}: {ups} {pre}"
             stats["writes"] += 1
             stats["write_errors"] += eo is not None
+            if eo is None:  # (the keys this stream has written, for the reads below: an expired one is one of these that the oracle no longer reads)
+                written_keys.update(parse_rel(u[1])[:6] for u in ups if u[0] != aclgpu.OP_DELETE and u[1].startswith("workflow:"))
         elif r < 0.7:
             now += rng.choice([1, 1, 3, 10, 61, 3601, 50000, 90000])
             e.set_now(now)
@@ -363,6 +1051,28 @@ def run_expiry(seed: int, steps: int, verbose: bool = True) -> dict:
             a, b2 = sorted(e.read(rtype="workflow")), sorted(o.read(rtype="workflow"))
             assert [x[:6] for x in a] == [x[:6] for x in b2], f"step {step} (now {now}): workflow relationships differ: {set(a) ^ set(b2)}"
             stats["reads"] += 1
+        # ---- the other read paths on the same snapshot, without a draw from rng: LookupSubjects of three workflows' keys, Explain of a live and of an expired key
+        held = {}
+        for x in o.read(rtype="workflow"):
+            held.setdefault(x[1], set()).add(x[4])
+        for k in range(3):
+            wf = wfs[(3 * step + k) % len(wfs)]
+            got = e.lookup_subjects("workflow", wf, "idempotency_key", "activity")
+            assert got == (held.get(wf, set()), False, set()), f"step {step} (now {now}): LookupSubjects of workflow:{wf}#idempotency_key: engine {got}, the oracle reads {held.get(wf, set())}"
+            stats["subject_lookups"] += 1
+            stats["subject_rows_nonempty"] += bool(held.get(wf))
+        live_keys = sorted((wf, a) for wf, acts_ in held.items() for a in acts_)
+        if live_keys:
+            wf, a = live_keys[step % len(live_keys)]
+            got = e.explain("workflow", wf, "idempotency_key", "activity", a)
+            assert got[:3] == (2, 0, aclgpu.EXPLAIN_WITNESS) and [tuple(parse_relationship(ln))[:6] for ln in got[3]] == [("workflow", wf, "idempotency_key", "activity", a, "")], f"step {step} (now {now}): Explain of the live key {wf}/{a}: {got}"
+            stats["live_keys_explained"] += 1
+        expired = sorted((r6[1], r6[4]) for r6 in written_keys if r6[4] not in held.get(r6[1], ()))
+        if expired:
+            wf, a = expired[step % len(expired)]
+            got = e.explain("workflow", wf, "idempotency_key", "activity", a)
+            assert got == (1, 0, 0, []) and tuple(o.check("workflow", wf, "idempotency_key", "activity", a)) == (1, 0), f"step {step} (now {now}): Explain of the expired key {wf}/{a}: {got}"
+            stats["expired_keys_explained"] += 1
         if verbose and step % 100 == 99:
             print(f"step {step + 1}/{steps}: {stats}, now +{now - 1_700_000_000} s", file=sys.stderr, flush=True)
     st = e.stats()
@@ -382,10 +1092,15 @@ if __name__ == "__main__":
     ap.add_argument("--schema", choices=["c4", "combine"], default="c4", help="combine: the C4 schema with exclusions, intersections, wildcards and a non-monotone userset subject")
     ap.add_argument("--recycle", action="store_true", help="ACL_ID_QUARANTINE_MS=0 and a stream of never-seen object names in the writes: ids of objects that lost their last relationship are taken over under the reads")
     ap.add_argument("--acyclic", action="store_true", help="group nesting without cycles: one-user CheckBulkPermissions calls take the reverse walk once the depth sweep has run")
+    ap.add_argument("--reads", action="store_true", help="the read campaign (run_reads): LookupSubjects, Explain witness / proof / denial, multi-target lookups and cursors held across the writes")
+    ap.add_argument("--dry", action="store_true", help="with --reads: the oracle's half alone, no engine and no GPU")
+    ap.add_argument("--depth-case", action="store_true", help="with --reads: LookupSubjects and multi-target lookups only, four LookupSubjects targets in all (cyclic combine graphs)")
     ap.add_argument("--universe", type=int, default=1, help="scale of the object universe (x 160 users, 48 groups, 8 namespaces, 240 pods)")
     a = ap.parse_args()
     try:
         print(run_patcher(a.seed, a.steps, a.universe, a.burst, schema=a.schema) if a.patcher else run_expiry(a.seed, a.steps) if a.expiry
+              else run_reads(a.seed, a.steps, schema=a.schema, acyclic=a.acyclic, recycle=a.recycle, compact_early=a.compact_early, universe=a.universe, engine=not a.dry,
+                             depth_case=a.depth_case) if a.reads
               else run(a.seed, a.steps, burst=a.burst, universe=a.universe, compact_early=a.compact_early, schema=a.schema, recycle=a.recycle, acyclic=a.acyclic))
     except AssertionError as x:
         print("MISMATCH:", x)

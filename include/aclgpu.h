@@ -709,6 +709,10 @@ typedef struct {
 enum { ACL_SHARD_VISIT = 1, ACL_SHARD_EXPAND = 2 };
 int acl_shard_configure(acl_engine_t *h, uint32_t rank, uint32_t world); /* world == 1 restores the single-GPU engine */
 int acl_shard_of_type(acl_engine_t *h, int type);                        /* shard holding the type's rows; -1 if unknown */
+/* after overflow == 1, before the batch is redone: four times the frontier -- or, the first time a Check batch of at most 16 384 items asks, the same
+ * frontier with duplicate (request, state, level) entries merged behind every level until acl_shard_check_finish (nesting with branching cycles doubles
+ * a frontier per level: no size catches up with it).  A LookupResources batch always grows.  Larger Check batches on such graphs run out at 2^28
+ * entries (ACL_ERR_RESOURCE_EXHAUSTED): ask in slices. */
 int acl_shard_grow_frontier(acl_engine_t *h);
 /* hipStream_t every acl_shard_* call launches on (the protocol's own evaluation context): the host orders its
  * collectives after / before the steps on this stream.  NULL without a GPU. */

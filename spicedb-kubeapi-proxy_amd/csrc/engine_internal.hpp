@@ -275,6 +275,10 @@ struct PassCtx {
     DevArray<uint32_t> d_xctrl;
     PinnedBuf h_xctrl;
     uint32_t xcap = 0;
+    // host-driven step protocol (engine_shard.cpp): the batch acl_shard_check_begin seeded, and whether the levels merge duplicate entries since a batch
+    // overflowed the frontier (group nesting with branching cycles: growing never catches up with a frontier that doubles per level)
+    size_t shard_step_items = 0;
+    bool shard_step_merge = false;
     std::vector<uint8_t> xplan_fwd, xplan_rev, xplan_subj;  // [iteration] the previous batch exported something there: exchange entries (empty: always)
     uint32_t rev_levels_hint = 4;
     uint32_t subj_levels_hint = 6;
@@ -599,6 +603,16 @@ int check_pass(acl_engine *h, PassCtx *c, const uint4 *d_items, uint32_t n, uint
 // every level in ONE launch, wave-private frontiers; an internal negative code when a wave's private frontier overflowed (kTakeLevelLoop; engine_pass.cpp)
 int check_pass_local(acl_engine *h, PassCtx *c, const DevGraph &g, const uint4 *d_items, uint32_t n, uint8_t *d_perm, int32_t *d_errout);
 constexpr int kTakeLevelLoop = -1000;  // internal: a single-launch walk declines the batch, the level loop takes it (never leaves the library)
+constexpr int kRetryMerging = -1002;   // internal: a level loop ran out of frontier; the batch is redone with duplicates merged before the frontier grows (further)
+// The table of a duplicate-merging level (launch_dedup) for the frontier as it is now: levels_pass and the sharded level loops.  Nested groups with
+// branching cycles double a frontier per level for 50 levels, and no growth catches up with that.  `cells`: the two-part key of `&` / `-` schemas.
+inline int dedup_table(PassCtx *c, bool cells, uint32_t *bits_out) {
+    uint32_t bits = 0;
+    while ((1ull << bits) < 2 * c->frontier_entries) bits++;
+    HIP_TRY(c->d_dedup.ensure(((size_t)1 << bits) + (cells ? (size_t)1 << (bits - 1) : 0)));  // (+ 2^bits u32 second halves)
+    *bits_out = bits;
+    return ACL_OK;
+}
 #pragma GCC visibility push(hidden)
 bool spin_for(const volatile uint32_t *word, uint32_t val);  // engine_pass.cpp: the completion word of a small launch, polled instead of a stream synchronisation
 uint32_t next_done_val(PassCtx *c);                          // the value the next launch of c stores there (never 0)

@@ -372,8 +372,6 @@ static void walk_outcome(acl_engine *h, PassCtx *c, size_t n, int rc) {
     else if (!rc) h->local_fail_streak.store(0, std::memory_order_relaxed);
 }
 
-constexpr int kRetryMerging = -1002;  // internal: the level loop ran out of frontier on its first attempt
-
 // the level-synchronous pass (one k_expand launch per dispatch level); `merging`: duplicate entries are struck after every level
 static int levels_pass(acl_engine *h, PassCtx *c, const DevGraph &g0, const uint4 *d_items, uint32_t n, uint8_t *d_perm, int32_t *d_errout, bool merging_asked) {
     // Schemas with `&` / `-`: entries carry result CELLS where the request would be; duplicates are merged on (cell, state, level) through a
@@ -389,8 +387,8 @@ static int levels_pass(acl_engine *h, PassCtx *c, const DevGraph &g0, const uint
         }
         uint32_t bits = 0;
         if (merging) {
-            while ((1ull << bits) < 2 * c->frontier_entries) bits++;
-            HIP_TRY(c->d_dedup.ensure(((size_t)1 << bits) + (combine ? (size_t)1 << (bits - 1) : 0)));  // (+ 2^bits u32 second halves)
+            int rc = dedup_table(c, combine, &bits);
+            if (rc) return rc;
         }
         DevFrontier f = h->dev_frontier(*c);
         ev_begin(c, 0);

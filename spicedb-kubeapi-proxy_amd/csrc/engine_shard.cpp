@@ -4,7 +4,7 @@
 //   * native loop (engine_shard_rccl.cpp, acl_shard_check_bulk): the whole level loop inside this library over an RCCL
 //     communicator -- one fixed-capacity exchange per level, termination decided on the device.
 // The protocol keeps state across calls, so it owns a context of its own (h->shard_ctx, never pooled) and serialises on shard_mu.
-#include "engine_internal.hpp"
+#include "engine_shard_exchange.hpp"
 
 namespace aclint {
 
@@ -91,6 +91,14 @@ int check_step(acl_engine *h, uint32_t level, void *d_has, void *d_err, void *d_
     HIP_TRY(hipMemsetAsync(c->d_status.p + 2 * kLevelSlots + 1, 0, (1 + kMaxShards) * sizeof(uint32_t), c->stream));
     DevShard sh = dev_shard(h, c, d_export, cap);
     sh.by_dest = by_dest ? 1u : 0u;
+    // A batch overflowed this shard's frontier before (acl_shard_grow_frontier): the level before this one -- its own entries and the imported ones -- has
+    // its duplicates merged first, as the native loop and check_pass do.  (The merge key holds 14 request bits.)
+    if (c->shard_step_merge && level > 1 && c->shard_step_items <= kDedupBatch) {
+        uint32_t bits = 0;
+        rc = dedup_table(c, false, &bits);
+        if (rc) return rc;
+        launch_dedup(c->stream, h->dev_frontier(*c), level - 1, c->d_dedup.p, bits, false);
+    }
     ev_begin(c, 1);
     launch_expand(c->stream, h->dev_graph(c), h->dev_frontier(*c), level, (uint8_t *)d_has, (uint8_t *)d_err, sh);
     ev_end(c);
@@ -144,6 +152,14 @@ int acl_shard_grow_frontier(acl_engine_t *h) {
     if (rc) return rc;
     if (sc.c->frontier_entries >= (uint64_t)kMaxFrontierChunks * kChunk) return fail(ACL_ERR_RESOURCE_EXHAUSTED, "frontier capacity exceeded");
     sc.c->stats.overflow_retries++;
+    // A Check batch of one merge slice that outgrew the frontier is exploding (branching group cycles): its redo merges duplicates, and only if that
+    // overflows too does the frontier grow.  Larger batches cannot be merged here (the caller owns the batch: no slices) and grow as before.  The flag
+    // lasts for that batch: acl_shard_check_finish and acl_shard_lookup_begin clear it, so a later batch pays for no merge table it does not need, and
+    // a lookup's overflow (shard_step_items == 0) always grows.
+    if (!sc.c->shard_step_merge && sc.c->shard_step_items && sc.c->shard_step_items <= kDedupBatch) {
+        sc.c->shard_step_merge = true;
+        return ACL_OK;
+    }
     return alloc_frontier(h, sc.c, sc.c->frontier_entries * 4);
 }
 
@@ -162,6 +178,7 @@ int acl_shard_check_begin(acl_engine_t *h, const void *d_items, size_t n, void *
     launch_seed(c->stream, h->dev_graph(c), h->dev_frontier(*c), (const uint4 *)d_items, (uint32_t)n, (uint8_t *)d_has, (uint8_t *)d_err,
                 dev_shard(h, c, nullptr, 0));  // also resets the status block
     ev_end(c);
+    c->shard_step_items = n;
     c->stats.check_items += n;
     return ACL_OK;
 }
@@ -196,6 +213,8 @@ int acl_shard_check_finish(acl_engine_t *h, const void *d_has, const void *d_err
     int rc = sc.begin(h, false, false);
     if (rc) return rc;
     PassCtx *c = sc.c;
+    c->shard_step_items = 0;  // (the batch is over: the next one merges only after an overflow of its own)
+    c->shard_step_merge = false;
     ev_begin(c, 0);
     launch_finalize(c->stream, (uint32_t)n, (const uint8_t *)d_has, (const uint8_t *)d_err, (uint8_t *)d_perm_out, (int32_t *)d_err_out);
     ev_end(c);
@@ -222,6 +241,8 @@ int acl_shard_lookup_begin(acl_engine_t *h, int rtype, int perm, int stype, int 
     }
     h->lk_target = (uint32_t)sc.slot(rtype, perm);
     h->lk_n = n;
+    c->shard_step_items = 0;  // (no Check batch is under way: acl_shard_grow_frontier grows)
+    c->shard_step_merge = false;
     const uint32_t key = sc.subject_key(stype, srel < 0 ? kNoRelation : srel);
     HIP_TRY(c->d_visited.ensure(std::max<size_t>(n, 1) * vwords));
     HIP_TRY(hipMemsetAsync(c->d_visited.p, 0, std::max<size_t>(n, 1) * vwords * 4, c->stream));

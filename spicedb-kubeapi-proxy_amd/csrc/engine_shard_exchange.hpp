@@ -73,7 +73,7 @@ struct Exchange {
             if (seen->size() <= it) seen->resize(it + 1, 0);
             (*seen)[it] = k[0] ? 1 : 0;
             if (k[2]) {  // some shard overflowed (frontier, export block, a row beyond the enumeration limit, the combine pools) or exported on a level planned without entries
-                *redo_code = (k[2] & 2u) ? 2u : (k[2] & kOverflowPools) ? kOverflowPools : (k[2] & 1u) ? 1u : 4u;
+                *redo_code = (k[2] & 2u) ? 2u : (k[2] & kOverflowPools) ? kOverflowPools : (k[2] & 1u) ? 1u : (k[2] & kOverflowExport) ? kOverflowExport : 4u;
                 *redo_max = std::max(*redo_max, k[3]);
                 return 2;
             }
@@ -98,7 +98,7 @@ struct Exchange {
             c->shard_pool_shift += 2;
             return ACL_OK;
         }
-        if (redo_max > cap) {
+        if (redo_max > cap) {  // (kOverflowExport, or a frontier that ran out on the same level: the block first)
             uint32_t nc = cap;
             while (nc < redo_max + redo_max / 4 && nc < (1u << 27)) nc <<= 1;
             c->xcap = a2a ? (uint32_t)std::min<uint64_t>((uint64_t)nc * world, 1u << 30) : nc;  // (xcap = entries a shard may export per level in all)
@@ -108,6 +108,8 @@ struct Exchange {
     }
 };
 
+// (The sharded level loops merge duplicates like check_pass does -- dedup_table, engine_internal.hpp.  Merging is local to a shard: the entries struck
+//  have the subtree of the one that stays, so the shards need not agree on it.)
 inline uint32_t first_xcap(PassCtx *c) {
     if (!c->xcap) {
         const char *e = getenv("ACL_SHARD_XCAP");  // test knob: a tiny first export block forces the grow-and-redo path

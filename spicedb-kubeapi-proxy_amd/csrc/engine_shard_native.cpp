@@ -103,10 +103,14 @@ int rccl_all_to_all(void *user, const void *send, void *recv, size_t bytes, void
 
 }  // namespace
 
-// the native Check loop on context c (the caller holds the shard call's locks): acl_shard_check_bulk, and the forward half of LookupResources over
-// a non-monotone permission (candidates + one Check)
-int aclint::shard_check_core(acl_engine_t *h, PassCtx *c, const acl_shard_comm_t *comm, const void *d_items, size_t n, void *d_perm_out, void *d_err_out,
-                             acl_shard_bulk_stats_t *stats_out) {
+namespace {
+
+// One pass of the native Check loop over n items.  `merging`: duplicate (request, state, level) entries of a level are struck behind its imports
+// (n <= kDedupBatch then: the merge key holds 14 request bits).  Without it, a frontier or pool overflow answers kRetryMerging -- at once for a batch of
+// one merge slice, behind one growth of the frontier or the pools for a larger one; taken from the control records, so on every shard alike.  An outgrown
+// export block is no such overflow: it is grown and the pass redone, merging or not.
+int shard_check_pass(acl_engine_t *h, PassCtx *c, const acl_shard_comm_t *comm, const void *d_items, size_t n, void *d_perm_out, void *d_err_out,
+                     acl_shard_bulk_stats_t *stats_out, bool merging) {
     int rc = ACL_OK;
     acl_shard_bulk_stats_t st{};
     Exchange X{h, c, comm, h->shard.world, h->shard.rank, 0, comm->all_to_all != nullptr && h->shard.world <= kMaxShards && h->shard_a2a, &st, &c->xplan_fwd};
@@ -128,6 +132,7 @@ int aclint::shard_check_core(acl_engine_t *h, PassCtx *c, const acl_shard_comm_t
     }
     first_xcap(c);
     std::vector<uint8_t> seen;
+    bool grown = false;  // this pass grew the frontier or the pools already
     for (int attempt = 0;; attempt++) {
         X.size_blocks();
         rc = X.alloc();
@@ -158,6 +163,11 @@ int aclint::shard_check_core(acl_engine_t *h, PassCtx *c, const acl_shard_comm_t
         }
         DevFrontier f = h->dev_frontier(*c);
         DevShard sh = X.shard();
+        uint32_t dedup_bits = 0;
+        if (merging) {
+            rc = dedup_table(c, combine, &dedup_bits);
+            if (rc) return rc;
+        }
         HIP_TRY(hipMemsetAsync(c->d_xctrl.p, 0, (size_t)kLevelSlots * kCtrlWords * sizeof(uint32_t), c->stream));
         ev_begin(c, 0);
         launch_seed(c->stream, g, f, (const uint4 *)d_items, (uint32_t)n, c->d_has.p, c->d_err.p, sh);  // also resets the status block
@@ -176,6 +186,7 @@ int aclint::shard_check_core(acl_engine_t *h, PassCtx *c, const acl_shard_comm_t
                     launch_import_gathered(c->stream, g, f, it, hdrs, data, X.world, X.rank, X.cap, have, ctrl);
                 });
                 if (rc) return rc;
+                if (merging) launch_dedup(c->stream, f, it, c->d_dedup.p, dedup_bits, combine);  // (this level's entries, the imported ones among them)
                 c->stats.expand_launches++;
             }
             HIP_TRY(hipMemcpyAsync(hc, c->d_xctrl.p, (size_t)kLevelSlots * kCtrlWords * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
@@ -191,6 +202,20 @@ int aclint::shard_check_core(acl_engine_t *h, PassCtx *c, const acl_shard_comm_t
             burst = 4;
         }
         if (verdict == 2) {
+            // the frontier (or, on a cyclic graph under `&` / `-`, the combine pools) ran out: a batch of one merge slice that outgrew a frontier sized for
+            // thousands of entries per item is exploding, a larger one gets one growth first -- then, before growing further, duplicates are merged.
+            // An outgrown export block alone (kOverflowExport) is grown by X.grow and the pass redone as it was -- unless the block is what shows the
+            // explosion first: where every hop crosses shards a level's exports are its frontier, and a block of 2^16 entries is outgrown ten levels before
+            // a frontier of 2^25 is, one redo a level.  So: one level exporting what the default frontier holds per item of a full slice (2^25 / 2^14
+            // entries) for every item of a one-slice batch, or a block outgrown for the sixth time (a graph without such cycles outgrows it once per level
+            // whose exports exceed all before, a handful), is taken for the same explosion.
+            const bool ran_out = redo_code == kOverflowPools || redo_code == 1u;
+            const bool block_explodes = redo_code == kOverflowExport && ((n <= kDedupBatch && redo_max >= 2048ull * std::max<size_t>(n, 1)) || attempt >= 5);
+            if (!merging && (block_explodes || (ran_out && (n <= kDedupBatch || grown)))) {
+                if (stats_out) *stats_out = st;
+                return kRetryMerging;
+            }
+            grown |= ran_out && (redo_code == kOverflowPools || redo_max <= X.cap);  // (X.grow: an outgrown block comes before the frontier)
             rc = X.grow(redo_code, redo_max, attempt);
             if (rc) return rc;
             continue;
@@ -244,6 +269,44 @@ int aclint::shard_check_core(acl_engine_t *h, PassCtx *c, const acl_shard_comm_t
     c->stats.check_items += n;
     c->stats.check_passes++;
     c->stats.levels_last = st.levels;
+    if (stats_out) *stats_out = st;
+    return ACL_OK;
+}
+
+void add_pass_stats(acl_shard_bulk_stats_t *a, const acl_shard_bulk_stats_t &b) {
+    a->levels = std::max(a->levels, b.levels);
+    a->exchanges += b.exchanges;
+    a->host_syncs += b.host_syncs;
+    a->retries += b.retries;
+    a->exchanged_bytes += b.exchanged_bytes;
+    a->entries_exchanged += b.entries_exchanged;
+    a->export_capacity = std::max(a->export_capacity, b.export_capacity);
+    a->data_exchanges += b.data_exchanges;
+}
+
+}  // namespace
+
+// the native Check loop on context c (the caller holds the shard call's locks): acl_shard_check_bulk, and the forward half of LookupResources over
+// a non-monotone permission (candidates + one Check)
+int aclint::shard_check_core(acl_engine_t *h, PassCtx *c, const acl_shard_comm_t *comm, const void *d_items, size_t n, void *d_perm_out, void *d_err_out,
+                             acl_shard_bulk_stats_t *stats_out) {
+    acl_shard_bulk_stats_t st{};
+    int rc = shard_check_pass(h, c, comm, d_items, n, d_perm_out, d_err_out, &st, false);
+    if (rc != kRetryMerging) {
+        if (!rc && stats_out) *stats_out = st;
+        return rc;
+    }
+    // The batch again with duplicates merged behind every level, on slices the merge key can hold (what check_pass does on one device).  Every shard is
+    // here: the verdict came from the control records.
+    st.retries++;
+    c->stats.overflow_retries++;
+    for (size_t off = 0; off < n; off += kDedupBatch) {
+        const size_t m = std::min<size_t>(kDedupBatch, n - off);
+        acl_shard_bulk_stats_t pst{};
+        rc = shard_check_pass(h, c, comm, (const uint4 *)d_items + off, m, (uint8_t *)d_perm_out + off, d_err_out ? (int32_t *)d_err_out + off : nullptr, &pst, true);
+        if (rc) return rc;
+        add_pass_stats(&st, pst);
+    }
     if (stats_out) *stats_out = st;
     return ACL_OK;
 }
@@ -377,6 +440,7 @@ int acl_shard_lookup_bulk(acl_engine_t *h, const acl_shard_comm_t *comm, int rty
     HIP_TRY(hipStreamSynchronize(c->stream));
     ev_collect(c);
     st.host_syncs++;
+    uint64_t export_cap = X.cap;  // (entries per exchange block, as the Check and LookupSubjects loops report it: all three size their blocks from c->xcap)
     // Schemas with `&` / `-` (round 5): the reverse walk follows only POSITIVE occurrences (plan_reverse.cpp), so the rows are candidates -- a
     // superset.  The answer is the candidates the forward walk grants: every shard holds the same rows by now, builds the same items and takes
     // part in ONE sharded Check (shard_check_core: the collectives stay in lockstep); bits of everything but HAS are cleared (as lookup_refine on
@@ -406,6 +470,8 @@ int acl_shard_lookup_bulk(acl_engine_t *h, const acl_shard_comm_t *comm, int rty
                 for (size_t k = 0; k < errs.size(); k++)
                     if (errs[k]) return lookup_candidate_error(h, errs[k], items[k].resource_id, items[k].subject_id);
             }
+            st.retries += cst.retries;
+            export_cap = std::max<uint64_t>(export_cap, cst.export_capacity);
             st.exchanges += cst.exchanges;
             st.entries_exchanged += cst.entries_exchanged;
             st.exchanged_bytes += cst.exchanged_bytes;
@@ -422,7 +488,7 @@ int acl_shard_lookup_bulk(acl_engine_t *h, const acl_shard_comm_t *comm, int rty
             HIP_TRY(hipMemcpy(d_bitmaps_out, rows.data(), rows.size() * 4, hipMemcpyHostToDevice));
         }
     }
-    st.export_capacity = c->xcap;
+    st.export_capacity = export_cap;
     c->stats.lookup_requests += n;
     c->stats.levels_last = st.levels;
     if (stats_out) *stats_out = st;

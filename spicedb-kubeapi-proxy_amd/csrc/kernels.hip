@@ -2776,7 +2776,7 @@ __device__ __forceinline__ void fold_headers(const uint4 *__restrict__ hdrs, uin
         const uint4 h = hdrs[r];
         total += h.w;
         anyp |= h.y & 1u;
-        over |= (h.y >> 1) | (h.z > cap ? 1u : 0u) | ((!have_data && h.w) ? 4u : 0u);  // (h.w, every shard's own included: the same verdict on every shard)
+        over |= (h.y >> 1) | (h.z > cap ? kOverflowExport : 0u) | ((!have_data && h.w) ? 4u : 0u);  // (h.w, every shard's own included: the same verdict on every shard)
         mx = max(mx, h.z);
     }
 #pragma unroll

@@ -52,6 +52,8 @@ constexpr uint32_t kWalkNoDirect = 1u;
 constexpr uint32_t kWalkNoHop2 = 2u;  // ACL_HOP2=0 (A/B and tests, one library for both forms): the walk reads the one-hop rows even where two-hop rows exist -- the host
                                       // sets the bit and, with it, hop2_slot to no slot's number: the kernel's one test per pair is the slot compare
 constexpr uint32_t kOverflowPools = 8u;   // level loop on the SHARDED graph, schemas with `&` / `-`: a shard ran out of combine nodes / leaf cells -- the native loop grows the pools and redoes the batch
+constexpr uint32_t kOverflowExport = 16u;  // a level's control record on the SHARDED graph (fold_headers): a shard's export block is outgrown -- apart from bit 1, a frontier out of chunks, which the
+                                           // native Check loop answers by merging duplicates
 constexpr uint32_t kOverflowDirect = 4u;  // single-launch walk's overflow code: "redo, and stop using the direct task lists on this snapshot"
 struct DevReverse {
     const uint32_t *rmeta, *redges;  // uint2 {start, end} per (relation, class, subject); resource ids

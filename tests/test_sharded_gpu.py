@@ -251,6 +251,67 @@ def test_native_loop_depth_chain(aclgpu):
             assert got == want, (hops, got, want)
 
 
+# nesting with BRANCHING cycles over CHAIN_SCHEMA: a chain at first, closed into t0 -> {c0, c1}, c0 -> {t0, t1}, c1 -> {t0, t1}, t1 -> {c0, c1} by BRANCH_CYCLES
+BRANCH_CHAIN = [("team", "t0", "member", "crew", "c0", "member"), ("crew", "c0", "member", "team", "t1", "member"), ("team", "t1", "member", "crew", "c1", "member"),
+                ("crew", "c1", "member", "user", "in", ""), ("team", "t9", "member", "user", "apart", "")]
+BRANCH_CYCLES = [("team", "t0", "member", "crew", "c1", "member"), ("crew", "c0", "member", "team", "t0", "member"), ("crew", "c1", "member", "team", "t0", "member"),
+                 ("crew", "c1", "member", "team", "t1", "member"), ("team", "t1", "member", "crew", "c0", "member")]
+BRANCH_QUERIES = [("team", "t0", "member", "user", "in", ""), ("team", "t0", "member", "user", "out", ""), ("crew", "c0", "member", "user", "out", ""),
+                  ("team", "t9", "member", "user", "apart", ""), ("team", "t9", "member", "user", "out", ""), ("team", "t1", "member", "user", "in", "")]
+
+
+@pytest.mark.parametrize("exchange", ["allgather", "alltoall"])
+def test_branching_cycle_across_shards_after_a_write(exchange, aclgpu):
+    """What tests/test_fuzz_sharded_gpu.py's cyclic cases found: nesting with BRANCHING cycles (t0 -> {c0, c1}, c0 -> {t0, t1}, c1 -> {t0, t1}, t1 -> {c0, c1};
+    world 3: team 1, crew 0, every hop crosses shards) doubles the frontier per level for 50 levels.  The sharded level loops only ever grew the frontier and
+    failed such a batch with ACL_ERR_RESOURCE_EXHAUSTED; they now merge duplicate (request, state, level) entries as check_pass does.  The graph is a chain at
+    first; one write closes the cycles under the engines' feet.  Both routes, every rank: the oracle's HAS, NO and depth errors."""
+    from aclgpu import sharded
+    chain, cycles, queries = BRANCH_CHAIN, BRANCH_CYCLES, BRANCH_QUERIES
+    co = orc.Oracle(CHAIN_SCHEMA)
+    co.write([(orc.OP_TOUCH, t) for t in chain])
+    want_chain = [co.check(*q) for q in queries]
+    co.write([(orc.OP_TOUCH, t) for t in cycles])
+    want_cycles = [co.check(*q) for q in queries]
+    assert want_chain[:2] == [(2, 0), (1, 0)] and want_cycles[:5] == [(2, 0), (0, orc.ERR_DEPTH), (0, orc.ERR_DEPTH), (2, 0), (1, 0)]
+    engines = []
+
+    def make(rank, nshards):
+        e = aclgpu.Engine(CHAIN_SCHEMA, contexts=1)
+        e.write([(aclgpu.OP_TOUCH, t) for t in chain])
+        for q in queries:
+            e.intern(q[0], q[1])
+            e.intern(q[3], q[4])
+        engines.append(e)
+        return sharded.GpuShard(e, rank, nshards)
+
+    def run(se):
+        e = se.shard.e
+        items = np.zeros(len(queries), dtype=aclgpu.ITEM_DTYPE)
+        for i, (rt, rid, pm, st, sid, _sr) in enumerate(queries):
+            items[i] = (e.type_id(rt), e.relation_id(rt, pm), e.find(rt, rid), e.type_id(st), aclgpu.NO_RELATION, e.find(st, sid))
+        out = []
+        for rels in (None, cycles):
+            if rels:
+                e.write([(aclgpu.OP_TOUCH, t) for t in rels])
+            p, er, s = se.check_bulk_ids_native(items)
+            p2, er2 = se.check_bulk_ids(items)
+            out.append((list(zip(p.cpu().tolist(), er.cpu().tolist())), list(zip(p2.cpu().tolist(), er2.cpu().tolist())), s))
+        return out
+
+    run.exchange = exchange
+    try:
+        outs = sharded.run_logical_shards(3, make, run)
+    finally:
+        for e in engines:
+            e.close()
+    for (n1, h1, s1), (n2, h2, s2) in outs:
+        print(exchange, s1, s2)
+        assert n1 == want_chain and h1 == want_chain
+        assert n2 == want_cycles and h2 == want_cycles
+        assert s2["retries"] >= 1 and s2["levels"] >= 49  # (the batch behind the write ran to the depth limit, redone with duplicates merged)
+
+
 def test_sharded_engine_refuses_unsharded_entry_points(aclgpu):
     from aclgpu import sharded
     with aclgpu.Engine(SCHEMA) as e:
@@ -746,3 +807,46 @@ def test_native_loops_combine_schema_between_two_processes(a2a, aclgpu):
         assert o_["check"]["view/0"]["stats"]["entries_exchanged"] > 0 and 0 < o_["check"]["view/0"]["has"] < 20000
         assert o_["lookup"]["view"]["ids"] > 0 and o_["ipc"]["foreign_bytes"] > 0
     assert all(o_["local_relationships"] > 0 for o_ in outs)
+
+
+def test_branching_cycle_batch_of_two_merge_slices(aclgpu, monkeypatch):
+    """The same graph under a batch the merge key cannot hold in one piece: the six queries tiled to 18 000 items, more than one merge slice of 16 384.  The native
+    loop grows the frontier once (engines opened with 2^20 entries: to 2^22), and when that runs out too redoes the batch in two slices with duplicates merged --
+    the second one reads its items and writes its answers at an offset.  Every rank: the oracle's answers, item by item.  (The step protocol cannot slice a
+    batch it does not own; include/aclgpu.h says so.)  The export blocks start large enough (2^23 entries a shard) for the levels before the frontier runs out: an
+    outgrown block is grown level by level, out of the same eight redos, and is not what this test is about."""
+    from aclgpu import sharded
+    monkeypatch.setenv("ACL_SHARD_XCAP", str(1 << 23))
+    tile = 3000
+    co = orc.Oracle(CHAIN_SCHEMA)
+    co.write([(orc.OP_TOUCH, t) for t in BRANCH_CHAIN + BRANCH_CYCLES])
+    want = [co.check(*q) for q in BRANCH_QUERIES] * tile
+    assert len(want) > (1 << 14) and (0, orc.ERR_DEPTH) in want and (2, 0) in want and (1, 0) in want
+    engines = []
+
+    def make(rank, nshards):
+        e = aclgpu.Engine(CHAIN_SCHEMA, contexts=1, frontier_entries=1 << 20)
+        e.write([(aclgpu.OP_TOUCH, t) for t in BRANCH_CHAIN + BRANCH_CYCLES])
+        for q in BRANCH_QUERIES:
+            e.intern(q[0], q[1])
+            e.intern(q[3], q[4])
+        engines.append(e)
+        return sharded.GpuShard(e, rank, nshards)
+
+    def run(se):
+        e = se.shard.e
+        items = np.zeros(len(BRANCH_QUERIES), dtype=aclgpu.ITEM_DTYPE)
+        for i, (rt, rid, pm, st, sid, _sr) in enumerate(BRANCH_QUERIES):
+            items[i] = (e.type_id(rt), e.relation_id(rt, pm), e.find(rt, rid), e.type_id(st), aclgpu.NO_RELATION, e.find(st, sid))
+        p, er, s = se.check_bulk_ids_native(np.tile(items, tile))
+        return list(zip(p.cpu().tolist(), er.cpu().tolist())), s
+
+    try:
+        outs = sharded.run_logical_shards(3, make, run)
+    finally:
+        for e in engines:
+            e.close()
+    for got, s in outs:
+        print(s)
+        assert got == want, [(i, g, w) for i, (g, w) in enumerate(zip(got, want)) if g != w][:5]
+        assert s["retries"] >= 2 and s["levels"] >= 49  # (one growth, then the merging redo; the slices ran to the depth limit)

@@ -16,7 +16,17 @@ The oracle is the checker (tests / tools only).  Exit code 1 and a dump of the f
   d. Explain denial (monotone permissions): the grants through tests/denial_checker.py;
   e. multi-target LookupResources over every relation and permission, bit for bit the single-target rows, by name the oracle's lookups, and access_review;
   f. lookup, subject and mixed cursors held open across later writes, compactions and recycled ids, with derived cursors and counts over them.
---reads --dry is the oracle's half alone (no GPU).  --expiry also asks LookupSubjects and Explain about live and expired idempotency keys."""
+--reads --dry is the oracle's half alone (no GPU).  --expiry also asks LookupSubjects and Explain about live and expired idempotency keys.
+
+--sharded W (run_sharded) holds the loops of the type-hash sharded graph to the oracles under the same kind of stream.  Phase 1, no GPU: one pass with the oracles
+alone writes the script -- every write with its outcome, every read with its expected answer by name.  Phase 2: W logical shards of one GPU (one engine per rank over
+a replicated store, one thread each) replay it; a rank records a wrong answer as (step, rank, kind, request, got, want) and goes on, the first record is printed:
+  a. Check batches of 1, 7, 64, 900, 3000 items through acl_shard_check_bulk and, on the same step, the host-driven step protocol (--exchange), route against route;
+  b. LookupResources of 1 and 4 subjects through acl_shard_lookup_bulk and the host-driven protocol, or the oracle's failure code on every rank and a correct next call;
+  c. LookupSubjects of 1, 5, 33 resources with excluded rows through acl_shard_subjects_bulk, user and group#member subjects, or ACL_ERR_DEPTH on every rank;
+  d. levels / retries / entries_exchanged / host_syncs / export_capacity of every native call (burst hints outrun by a deeper batch, grow-and-redo under --xcap).
+On --schema combine the host-driven protocol refuses the schema (its code is recorded once) and the native loops alone answer.  --sharded W --dry is phase 1 plus the
+script's writes on W store-only engines (acl_shard_configure) whose patched host snapshot is verified against the store at every read step."""
 import argparse
 import os
 import random
@@ -126,14 +136,14 @@ def rand_query(rng, names, combine: bool = False):
     return ("pod", rng.choice(pods), "view", "group", rng.choice(groups), "member")  # a userset as the subject
 
 
-def open_engine(schema_text: str, recycle: bool, compact_early: bool):
+def open_engine(schema_text: str, recycle: bool, compact_early: bool, **engine_kw):
     import aclgpu
     if recycle:
         os.environ["ACL_ID_QUARANTINE_MS"] = "0"  # (read when the schema is loaded) freed ids are reused by the next new name at once
     if compact_early:
         os.environ["ACL_COMPACTION_SLACK"] = "0"  # (read at acl_open) background compactions, adopted with the writes since replayed, on this small graph too
     try:
-        return aclgpu.Engine(schema_text)
+        return aclgpu.Engine(schema_text, **engine_kw)
     finally:
         os.environ.pop("ACL_COMPACTION_SLACK", None)
         os.environ.pop("ACL_ID_QUARANTINE_MS", None)
@@ -974,6 +984,471 @@ def run_patcher(seed: int, steps: int, universe: int = 1, burst: int = 25, shard
     return codes
 
 
+# ---------------------------------------------------------------------------------------------------------------- the sharded campaign
+class _TapOracle:
+    """The oracle as write_batch / filter_delete / load_initial see it: every call goes through, the last write's outcome is remembered for _TapEngine."""
+
+    def __init__(self, o):
+        self._o, self.code, self.removed = o, None, 0
+
+    def __getattr__(self, k):
+        return getattr(self._o, k)
+
+    def write(self, ups):
+        from oracle import orc
+        self.code = None
+        try:
+            return self._o.write(ups)
+        except orc.OracleError as x:
+            self.code = x.code
+            raise
+
+    def delete_by_filter(self, **f):
+        self.removed = self._o.delete_by_filter(**f)
+        return self.removed
+
+
+class _TapEngine:
+    """Stands where write_batch / filter_delete / load_initial expect the engine: it writes the script -- what they send, with the outcome the oracle
+    just gave -- and answers as the oracle did."""
+
+    def __init__(self, tap, sink):
+        self.tap, self.sink, self.step = tap, sink, -1
+
+    def write(self, ups):
+        import aclgpu
+        self.sink.append(("write", self.step, list(ups), self.tap.code))
+        if self.tap.code is not None:
+            raise aclgpu.AclError(self.tap.code, "as the oracle")
+
+    def delete_by_filter(self, **f):
+        self.sink.append(("filter", self.step, dict(f), self.tap.removed))
+        return self.tap.removed
+
+
+class _ScriptReads(_Reads):
+    """_Reads without an engine: round_subjects picks the resources as the read campaign does, and every LookupSubjects request it computes the expected rows
+    of is kept for the script"""
+
+    def __init__(self, *a):
+        super().__init__(*a)
+        self.asked = []
+
+    def subjects_expected(self, rt, perm, st, srel, rids, contract_cache):
+        want = super().subjects_expected(rt, perm, st, srel, rids, contract_cache)
+        self.asked.append((rt, perm, st, srel, list(rids), want))
+        return want
+
+
+SHARD_CHECK_SIZES = (1, 7, 64, 900, 3000)
+
+
+def sharded_script(seed: int, steps: int, schema: str = "c4", acyclic: bool = False, recycle: bool = False, universe: int = 1, depth_case: bool = False,
+                   read_share: float = 0.75, verbose: bool = False) -> dict:
+    """Phase 1 of run_sharded (no GPU, no engine): one pass over run_reads' kind of stream with the oracles alone -> the ordered script every rank replays.
+    script["init"]: the starting graph's write steps; script["steps"]: in order
+      ("write", step, updates, the oracle's outcome code or None) | ("filter", step, filter, removed)
+      ("check", step, [item], [(permissionship, error)])
+      ("lookup", step, rtype, permission, [user], [("ok", names) | ("err", code)], [follow-up]) -- a follow-up is ("check", items, want) or ("lookup", [user], [outcome]):
+          asked behind a call that must fail, the next call on that engine has to answer
+      ("subjects", step, [(rtype, permission, stype, srel, [resource], [(ids, wildcard, excluded) | "DEPTH"])])
+    and script["stats"], what the stream covers.  Every draw of a read comes from a generator of its own: the write stream is run_reads' for the same seed."""
+    from aclgpu import workloads
+    from oracle import orc
+    combine = schema == "combine"
+    schema_text = SCHEMA_COMBINE if combine else workloads.SCHEMA_C4
+    rng = random.Random(seed)
+    rr = random.Random(f"sharded/{seed}")
+    names = make_universe(rng, universe)
+    users, groups, nss, pods = names
+    rand_tuple = make_rand_tuple(rng, names, combine, recycle, acyclic)
+    o = _TapOracle(orc.Oracle(schema_text))
+    init, script = [], []
+    rec = _TapEngine(o, init)
+    live = set()
+    load_initial(rand_tuple, o, rec, live, universe)
+    rec.sink = script
+    stats = {k: 0 for k in ("writes", "write_errors", "filter_deletes", "writes_accepted", "writes_read_before_next", "rounds", "skipped", "rounds_check", "rounds_lookup",
+                            "rounds_subjects", "check_items", "check_depth_items", "check_has_items", "check_first_seen_items", "check_outruns_expected", "lookup_rows", "lookup_calls",
+                            "lookup_calls_failed", "lookup_rows_nonempty", "subj_rows", "subj_nonempty", "subj_empty", "subj_depth", "subj_wildcard", "subj_interned_only",
+                            "subj_first_seen", "subj_no_relationships", "subj_calls", "subj_calls_failed", "subj_calls_answered", "subj_answered_over_arrow", "subj_wildcard_excluded")}
+    reads = _ScriptReads(rr, names, schema_text, combine, recycle, o, None, live, stats, depth_case, not acyclic)
+    lookup_perms = [("pod", "view"), ("namespace", "view"), ("group", "member")] + \
+        ([("pod", "audit"), ("pod", "edit"), ("pod", "hidden"), ("group", "active"), ("pod", "everywhere"), ("pod", "vetted")] if combine else [])
+    subject_rounds = 3 if depth_case else 4 if combine else 6  # (the contract's Python oracles are what a combine case costs: run_reads' budget; C4: 5, 1, 33 resources twice)
+    unread_write = False   # an accepted write no read has followed yet
+    last_check_deep = None  # did the previous Check round hold an item that ends at the depth limit
+    todo = []
+    t0 = time.time()
+
+    def check_round(n):
+        qs = [rand_query(rr, names, combine) for _ in range(n)]
+        if recycle and n >= 7:  # objects first named by this stream, on both sides of an item
+            fp, fu = reads.first_seen_in_stream("pod"), [u for u in reads.names_of("user") if u.startswith("newcomer")]
+            if fp: qs[1] = ("pod", rr.choice(fp), "view", "user", rr.choice(users), "")
+            if fu: qs[2] = ("pod", rr.choice(pods), "view", "user", rr.choice(fu), "")
+            stats["check_first_seen_items"] += bool(fp) + bool(fu)
+        want = {q: tuple(o.check(*q)) for q in set(qs)}
+        return qs, [want[q] for q in qs]
+
+    for step in range(steps):
+        rec.step = step
+        if rng.random() < 0.9:
+            accepted = write_batch(rng, step, rand_tuple, o, rec, live, 25, stats)
+        else:
+            accepted = filter_delete(rng, step, names, combine, o, rec, live, stats) > 0
+        if accepted:
+            reads.version += 1
+            stats["writes_accepted"] += 1
+            unread_write = True
+        if rr.random() < read_share:
+            if not todo:
+                todo = ["check", "lookup"] + (["subjects"] if (reads.subject_targets if depth_case else stats["rounds_subjects"]) < subject_rounds else [])
+                rr.shuffle(todo)
+            kind = todo.pop()
+            reads.round_no += 1
+            done = True
+            t1 = time.time()
+            if kind == "check":
+                qs, want = check_round(SHARD_CHECK_SIZES[stats["rounds_check"] % len(SHARD_CHECK_SIZES)])
+                deep = sum(w[1] == orc.ERR_DEPTH for w in want)
+                stats["check_items"] += len(qs)
+                stats["check_depth_items"] += deep
+                stats["check_has_items"] += sum(w == (2, 0) for w in want)
+                stats["check_outruns_expected"] += bool(deep) and last_check_deep is False  # the level loop's burst was sized by a shallower batch
+                last_check_deep = bool(deep)
+                script.append(("check", step, qs, want))
+            elif kind == "lookup":
+                rt, pm = rr.choice(lookup_perms)
+                subs = rr.sample(reads.names_of("user"), (1, 4)[stats["rounds_lookup"] % 2])
+                want = [reads.lookup_expected(rt, pm, "user", u) for u in subs]
+                after = []
+                if any(w[0] == "err" for w in want):
+                    stats["lookup_calls_failed"] += 1
+                    ok = [(u, w) for u, w in zip(subs, want) if w[0] == "ok"]
+                    after = [("lookup", [u], [w]) for u, w in ok] or [("check",) + check_round(7)]
+                stats["lookup_calls"] += 1
+                stats["lookup_rows"] += len(subs)
+                stats["lookup_rows_nonempty"] += sum(w[0] == "ok" and bool(w[1]) for w in want)
+                script.append(("lookup", step, rt, pm, subs, want, after))
+            else:
+                mark = len(reads.asked)
+                done = reads.round_subjects(step)
+                if done and not depth_case:  # ... and a resource the generator knows that has lost, or never had, relationships of its own
+                    rt, pm = reads.asked[mark][:2]
+                    bare = sorted(set({"pod": pods, "namespace": nss, "group": groups}[rt]) - set(reads.resources_with_relationships(rt)))
+                    if bare:
+                        reads.subjects_expected(rt, pm, "user", "", [rr.choice(bare)], {})
+                        stats["subj_no_relationships"] += 1
+                if done and depth_case and not stats["subj_answered_over_arrow"]:
+                    # the targets that answer there have no Check that errs, so no cyclic group behind them: what crosses shards in an answered call is a namespace's
+                    # viewer relation with its groups' members (monotone: users beyond the depth limit are left out silently, the call answers)
+                    with_groups = sorted({r[1] for r in reads.rels() if r[0] == "namespace" and r[2] == "viewer" and r[3] == "group"})
+                    if with_groups:
+                        reads.subjects_expected("namespace", "viewer", "user", "", [rr.choice(with_groups)], {})
+                asked = reads.asked[mark:]
+                for _rt, _pm, _st, _srel, _rids, want in asked:
+                    failed = any(w == "DEPTH" for w in want)
+                    stats["subj_calls"] += 1
+                    stats["subj_calls_failed"] += failed
+                    stats["subj_calls_answered"] += not failed
+                    # (an answered call that crosses shards at every world the cases use: a pod's permission through pod#namespace, a namespace's through its groups)
+                    stats["subj_answered_over_arrow"] += not failed and any(r[1] in _rids and ((_rt, r[0], r[2]) == ("pod", "pod", "namespace") and _pm != "edit" or
+                                                                                           (_rt, r[0], r[2], r[3]) == ("namespace", "namespace", "viewer", "group")) for r in reads.rels())
+                    stats["subj_wildcard_excluded"] += sum(w != "DEPTH" and w[1] and bool(w[2]) for w in want)
+                if done:
+                    script.append(("subjects", step, asked))
+            stats["seconds_" + kind] = round(stats.get("seconds_" + kind, 0.0) + time.time() - t1, 2)
+            stats["rounds"] += 1
+            stats["rounds_" + kind] += bool(done)
+            stats["skipped"] += not done
+            if done and unread_write:
+                stats["writes_read_before_next"] += 1
+                unread_write = False
+        elif accepted:
+            unread_write = False  # (the next write comes before a read)
+        if verbose and step % 10 == 9:
+            print(f"step {step + 1}/{steps}: {stats}, {len(live)} relationships, {time.time() - t0:.1f} s", file=sys.stderr, flush=True)
+    stats["seconds_script"] = round(time.time() - t0, 1)
+    return dict(schema_text=schema_text, combine=combine, init=init, steps=script, stats=stats)
+
+
+def step_names(st):
+    """the (type, name) pairs a read step interns, in the order every rank interns them"""
+    def of_items(qs):
+        for rt, rid, _pm, s, sid, _srel in qs:
+            yield (rt, rid)
+            yield (s, sid)
+
+    if st[0] == "check":
+        yield from of_items(st[2])
+    elif st[0] == "lookup":
+        for u in st[4]:
+            yield ("user", u)
+        for f in st[6]:
+            if f[0] == "check":
+                yield from of_items(f[1])
+    elif st[0] == "subjects":
+        for rt, _pm, _st, _srel, rids, _want in st[2]:
+            for r in rids:
+                yield (rt, r)
+
+
+def sharded_dry_engines(script, world: int, recycle: bool, compact_early: bool) -> list:
+    """The script's writes on one store-only engine per rank (acl_shard_configure(rank, world)), one after the other; at every read step the rank's host snapshot is
+    brought up to date the way a read would and verified against the store.  -> per rank {"owns", 0: rebuilt, 1: patched, 2: current, "adopted", "dropped"}."""
+    out = []
+    for rank in range(world):
+        e = open_engine(script["schema_text"], recycle, False, store_only=True)
+        try:
+            e._check(e._L.acl_shard_configure(e._h, rank, world))
+            for st in script["init"]:
+                e.write(st[2])
+            e.selfcheck_snapshot_code()  # (the first build is not counted)
+            codes = {"owns": [t for t in ("group", "namespace", "pod") if e._L.acl_shard_of_type(e._h, e.type_id(t)) == rank], 0: 0, 1: 0, 2: 0, "adopted": 0, "dropped": 0}
+            pending, nwrites, started = None, 0, 0
+            every = 8 if compact_early else 30  # (the engine compacts in the background on these graphs without ACL_COMPACTION_SLACK=0 too, only less often)
+            for st in script["steps"]:
+                if st[0] in ("write", "filter"):
+                    sharded_apply_write(e, st)
+                    nwrites += 1
+                    # a background compaction's two halves around the writes in between, as run_patcher drives them: built from a copy-on-write view behind
+                    # every `every`-th write, adopted 0, 1, ... 5 writes later with the writes since replayed onto it
+                    if pending is None and nwrites % every == every // 2:
+                        e.selfcheck_compaction(0)
+                        pending = started % 6
+                        started += 1
+                    elif pending is not None:
+                        if pending == 0:
+                            codes["adopted" if e.selfcheck_compaction(1) else "dropped"] += 1  # (phase 1 verifies the adopted snapshot against the store)
+                            pending = None
+                        else:
+                            pending -= 1
+                else:
+                    for t, n in dict.fromkeys(step_names(st)):
+                        e.intern(t, n)
+                    codes[e.selfcheck_snapshot_code()] += 1  # (raises when the snapshot does not describe the store)
+            codes["ids_recycled"] = int(e.stats().get("ids_recycled", 0))
+            out.append(codes)
+        finally:
+            e.close()
+    return out
+
+
+def sharded_apply_write(e, st):
+    """one write step of the script on an engine -> None, or what differs from the oracle's outcome"""
+    import aclgpu
+    if st[0] == "filter":
+        n = e.delete_by_filter(**st[2])
+        return None if n == st[3] else (st[2], n, st[3])
+    code = None
+    try:
+        e.write(st[2])
+    except aclgpu.AclError as x:
+        code = x.code
+    return None if code == st[3] else (st[2][:3], code, st[3])
+
+
+def sharded_replay(script, host_driven: bool):
+    """-> fn(ShardedEngine) for sharded.run_logical_shards: one rank's replay of the script.  A wrong answer is recorded as (step, rank, kind, request, got, want) and the
+    rank goes on; it returns its records, one line of the stats struct per native call, a digest of the ids it interned per read step, and its engine's stats."""
+    import zlib
+    import numpy as np
+    import aclgpu
+
+    def names_of_row(e, t, row):
+        return set(e.bitmap_names(t, row.cpu().numpy().view(np.uint32)))
+
+    def replay(se):
+        e, rank = se.shard.e, se.shard.rank
+        bad, calls, digests, refusals = [], [], [], []
+        tid = {t: e.type_id(t) for t in ("user", "group", "namespace", "pod")}
+        rel = {}
+
+        def rel_id(t, m):
+            if (t, m) not in rel:
+                rel[(t, m)] = e.relation_id(t, m)
+            return rel[(t, m)]
+
+        def items_of(qs, ids):
+            out = np.zeros(len(qs), dtype=aclgpu.ITEM_DTYPE)
+            for i, (rt, rid, pm, s, sid, srel) in enumerate(qs):
+                out[i] = (tid[rt], rel_id(rt, pm), ids[(rt, rid)], tid[s], rel_id(s, srel) if srel else aclgpu.NO_RELATION, ids[(s, sid)])
+            return out
+
+        def note(step, kind, follows_write, s):
+            calls.append((step, kind, follows_write, s["levels"], s["retries"], s["entries_exchanged"], s["host_syncs"], s["export_capacity"]))
+
+        def check(step, qs, want, ids, follows_write, kind="check"):
+            items = items_of(qs, ids)
+            p, er, s = se.check_bulk_ids_native(items)
+            note(step, kind, follows_write, s)
+            got = list(zip(p.cpu().tolist(), er.cpu().tolist()))
+            diff = [i for i in range(len(qs)) if got[i] != tuple(want[i])]
+            if diff:
+                bad.append((step, rank, kind + " native", (qs[diff[0]], f"item {diff[0]} of {len(qs)}, {len(diff)} differ"), got[diff[0]], want[diff[0]]))
+            if host_driven:
+                p2, er2 = se.check_bulk_ids(items)
+                got2 = list(zip(p2.cpu().tolist(), er2.cpu().tolist()))
+                diff = [i for i in range(len(qs)) if got2[i] != tuple(want[i])]
+                if diff:
+                    bad.append((step, rank, kind + " host-driven", (qs[diff[0]], f"item {diff[0]} of {len(qs)}, {len(diff)} differ"), got2[diff[0]], want[diff[0]]))
+                if got2 != got:
+                    i = next(i for i in range(len(qs)) if got[i] != got2[i])
+                    bad.append((step, rank, kind + ": the routes differ", qs[i], got2[i], got[i]))
+            elif not any(r[0] == "check" for r in refusals):  # a schema with `-` / `&` / .all(): the step protocol refuses it, on every rank before any collective
+                try:
+                    se.check_bulk_ids(items)
+                    refusals.append(("check", None))
+                except aclgpu.AclError as x:
+                    refusals.append(("check", x.code))
+
+        def lookup(step, rt, pm, subs, want, ids, follows_write, kind="lookup"):
+            sids = [ids[("user", u)] for u in subs]
+            fails = next((w[1] for w in want if w[0] == "err"), None)
+            routes = [("native", lambda: se.lookup_ids_batch_native(rt, pm, "user", "", sids))]
+            if host_driven:
+                routes.append(("host-driven", lambda: (se.lookup_ids_batch(rt, pm, "user", "", sids), None)))
+            elif not any(r[0] == "lookup" for r in refusals):
+                try:
+                    se.lookup_ids_batch(rt, pm, "user", "", sids)
+                    refusals.append(("lookup", None))
+                except aclgpu.AclError as x:
+                    refusals.append(("lookup", x.code))
+            for route, call in routes:
+                try:
+                    bm, s = call()
+                except aclgpu.AclError as x:  # a candidate's Check erred: every rank fails the call, at the same point
+                    if x.code != fails:
+                        bad.append((step, rank, f"{kind} {route}", (rt, pm, subs), ("err", x.code), [w[0] for w in want]))
+                    continue
+                if s is not None:
+                    note(step, kind, follows_write, s)
+                if fails is not None:
+                    bad.append((step, rank, f"{kind} {route}", (rt, pm, subs), "answered", ("err", fails)))
+                    continue
+                for i, (u, w) in enumerate(zip(subs, want)):
+                    got = names_of_row(e, rt, bm[i])
+                    if got != w[1]:
+                        bad.append((step, rank, f"{kind} {route}", (rt, pm, u), f"engine only {sorted(got - w[1])[:5]}", f"oracle only {sorted(w[1] - got)[:5]}"))
+
+        def subjects(step, req, ids, follows_write):
+            rt, pm, s_t, srel, rids, want = req
+            fails = any(w == "DEPTH" for w in want)
+            try:
+                bm, flags, ex, s = se.lookup_subjects_ids_batch_native(rt, pm, s_t, srel, [ids[(rt, r)] for r in rids], want_excluded=True)
+            except aclgpu.AclError as x:
+                if not (fails and x.code == aclgpu.ERR_DEPTH):
+                    bad.append((step, rank, "subjects", (rt, pm, s_t, srel, rids[:3]), ("err", x.code), "DEPTH" if fails else "an answer"))
+                return
+            note(step, "subjects", follows_write, s)
+            if fails:
+                bad.append((step, rank, "subjects", (rt, pm, s_t, srel, [r for r, w in zip(rids, want) if w == "DEPTH"][:3]), "answered", "DEPTH"))
+                return
+            for i, (r, (wids, wild, wex)) in enumerate(zip(rids, want)):
+                got = names_of_row(e, s_t, bm[i])
+                if got != wids:
+                    bad.append((step, rank, "subjects", (rt, r, pm, s_t, srel), f"engine only {sorted(got - wids)[:5]}", f"contract only {sorted(wids - got)[:5]}"))
+                if bool(flags[i] & 1) != wild:
+                    bad.append((step, rank, "subjects wildcard flag", (rt, r, pm, s_t, srel), int(flags[i]), wild))
+                if wild:
+                    gex = names_of_row(e, s_t, ex[i])
+                    if gex != wex:
+                        bad.append((step, rank, "subjects excluded", (rt, r, pm, s_t, srel), sorted(gex ^ wex)[:5], "(symmetric difference)"))
+
+        for st in script["init"]:
+            e.write(st[2])
+        follows_write = False  # (the first read follows the starting graph's load: a built snapshot, not a patched one)
+        for st in script["steps"]:
+            if st[0] in ("write", "filter"):
+                d = sharded_apply_write(e, st)
+                if d is not None:
+                    bad.append((st[1], rank, st[0]) + d)
+                follows_write = follows_write or (st[3] is None if st[0] == "write" else st[3] > 0)
+                continue
+            ids = {}
+            for k in step_names(st):
+                if k not in ids:
+                    ids[k] = e.intern(*k)
+            digests.append(zlib.crc32(np.asarray(list(ids.values()), dtype=np.uint32).tobytes()))
+            if st[0] == "check":
+                check(st[1], st[2], st[3], ids, follows_write)
+            elif st[0] == "lookup":
+                lookup(st[1], st[2], st[3], st[4], st[5], ids, follows_write)
+                for f in st[6]:
+                    if f[0] == "check":
+                        check(st[1], f[1], f[2], ids, False, kind="check behind a failed lookup")
+                    else:
+                        lookup(st[1], st[2], st[3], f[1], f[2], ids, False, kind="lookup behind a failed lookup")
+            else:
+                for req in st[2]:
+                    subjects(st[1], req, ids, follows_write)
+            follows_write = False
+        est = e.stats()
+        return dict(rank=rank, bad=bad, calls=calls, digests=digests, refusals=refusals, owns=[t for t in ("group", "namespace", "pod") if se.shard.owner_of_type(t) == rank],
+                    **{k: int(est[k]) for k in ("snapshot_builds", "snapshot_patches", "snapshot_compactions", "ids_recycled", "overflow_retries") if k in est})
+
+    return replay
+
+
+def run_sharded(seed: int, steps: int, world: int, schema: str = "c4", acyclic: bool = False, recycle: bool = False, compact_early: bool = False, universe: int = 1,
+                engine: bool = True, verbose: bool = True, depth_case: bool = False, read_share: float = 0.75, exchange: str = "allgather", xcap: int = 0) -> dict:
+    """The read campaign's kind of write stream under the loops of the type-hash sharded graph.  Phase 1 (sharded_script) computes, with the oracles alone, the script
+    of writes and reads with their expected outcomes; phase 2 replays it on `world` logical shards of one GPU (sharded.run_logical_shards: one Engine per rank, a
+    replicated store, one thread each), every rank holding every answer to the script by name:
+      a. Check batches of 1, 7, 64, 900 and 3000 items through acl_shard_check_bulk and, on the same step, the host-driven step protocol (`exchange`), route against route;
+      b. LookupResources of 1 and 4 subjects through acl_shard_lookup_bulk and the host-driven protocol, or the failure code on every rank and a correct next call;
+      c. LookupSubjects of 1, 5 and 33 resources with the excluded rows (acl_shard_subjects_bulk), user and group#member subjects, or ACL_ERR_DEPTH on every rank;
+      d. levels / retries / entries_exchanged / host_syncs / export_capacity of every native call, for the conditions on the burst hints and on grow-and-redo.
+    The host-driven protocol refuses schemas with `-` / `&` / .all() (ShardCall::begin): there the native loops alone answer and the refusal's code is recorded once.
+    engine=False: phase 1, and the script's writes on one store-only engine per rank whose patched host snapshot is verified against the store at every read step.
+    xcap: ACL_SHARD_XCAP around the replay (a first export block of that many entries: grow-and-redo).  -> stats; raises AssertionError on the first record."""
+    script = sharded_script(seed, steps, schema, acyclic, recycle, universe, depth_case, read_share, verbose)
+    stats = script["stats"]
+    t0 = time.time()
+    if not engine:
+        stats["dry_ranks"] = sharded_dry_engines(script, world, recycle, compact_early)
+        stats["seconds_dry_engines"] = round(time.time() - t0, 1)
+        return stats
+    import aclgpu
+    from aclgpu import sharded
+    env = {"ACL_ID_QUARANTINE_MS": "0" if recycle else None, "ACL_COMPACTION_SLACK": "0" if compact_early else None, "ACL_SHARD_XCAP": str(xcap) if xcap else None}
+    before = {k: os.environ.get(k) for k in env}
+    engines = []
+
+    def make(rank, nshards):  # (open_engine's environment, set once around every rank's engine: the ranks are threads of this process)
+        # (a frontier of 2^20 entries in place of the default 2^25: eight engines share the device, and a batch that outgrows it grows it under the reads)
+        e = aclgpu.Engine(script["schema_text"], contexts=1, frontier_entries=1 << 20)
+        engines.append(e)
+        return sharded.GpuShard(e, rank, nshards)
+
+    fn = sharded_replay(script, host_driven=not script["combine"])
+    fn.exchange = exchange
+    try:
+        for k, v in env.items():
+            if v is not None:
+                os.environ[k] = v
+        outs = sharded.run_logical_shards(world, make, fn)
+    finally:
+        for k, v in before.items():
+            os.environ.pop(k, None) if v is None else os.environ.__setitem__(k, v)
+        for e in engines:
+            e.close()
+    stats["seconds_replay"] = round(time.time() - t0, 1)
+    bad = [b for out in outs for b in out["bad"]]
+    for out in outs[1:]:  # a replicated store: every rank gave every name the id rank 0 gave it (recycled ones too)
+        d = next((i for i, (a, b) in enumerate(zip(outs[0]["digests"], out["digests"])) if a != b), None)
+        if d is not None:
+            bad.append((f"read step {d}", out["rank"], "interned ids differ from rank 0's", None, out["digests"][d], outs[0]["digests"][d]))
+    stats["ranks"] = [{k: v for k, v in out.items() if k not in ("bad", "calls", "digests")} for out in outs]
+    stats["calls"] = outs[0]["calls"]  # (step, kind, follows a write, levels, retries, entries_exchanged, host_syncs, export_capacity) of rank 0's native calls
+    stats["calls_equal_on_every_rank"] = all([c[:5] + c[7:] for c in out["calls"]] == [c[:5] + c[7:] for c in outs[0]["calls"]] for out in outs)
+    if bad:
+        bad.sort(key=lambda b: (b[0] if isinstance(b[0], int) else 1 << 30, b[1]))
+        raise AssertionError(f"{len(bad)} records; the first: step {bad[0][0]}, rank {bad[0][1]}, {bad[0][2]}: request {bad[0][3]}: got {bad[0][4]}, want {bad[0][5]}")
+    return stats
+
+
 def run_expiry(seed: int, steps: int, verbose: bool = True) -> dict:
     """The reference's own schema (pkg/spicedb/bootstrap.yaml) under the dual write's shapes: lock tuples created behind MUST_NOT_MATCH and deleted
     again (workflow.go:392-462), idempotency keys that EXPIRE (activity.go:81-102), payload relationships -- while the clock moves forwards in
@@ -1096,9 +1571,15 @@ if __name__ == "__main__":
     ap.add_argument("--dry", action="store_true", help="with --reads: the oracle's half alone, no engine and no GPU")
     ap.add_argument("--depth-case", action="store_true", help="with --reads: LookupSubjects and multi-target lookups only, four LookupSubjects targets in all (cyclic combine graphs)")
     ap.add_argument("--universe", type=int, default=1, help="scale of the object universe (x 160 users, 48 groups, 8 namespaces, 240 pods)")
+    ap.add_argument("--sharded", type=int, default=0, metavar="W", help="the sharded campaign (run_sharded): the stream's script replayed on W logical shards of one GPU; with --dry on W store-only engines")
+    ap.add_argument("--exchange", choices=["allgather", "alltoall"], default="allgather", help="with --sharded: how the host-driven protocol's Check frontiers cross shards")
+    ap.add_argument("--xcap", type=int, default=0, help="with --sharded: ACL_SHARD_XCAP around the replay (a first export block of that many entries)")
+    ap.add_argument("--read-share", type=float, default=0.75, help="with --sharded: the share of steps with a read round behind the write")
     a = ap.parse_args()
     try:
-        print(run_patcher(a.seed, a.steps, a.universe, a.burst, schema=a.schema) if a.patcher else run_expiry(a.seed, a.steps) if a.expiry
+        print(run_sharded(a.seed, a.steps, a.sharded, schema=a.schema, acyclic=a.acyclic, recycle=a.recycle, compact_early=a.compact_early, universe=a.universe,
+                          engine=not a.dry, depth_case=a.depth_case, read_share=a.read_share, exchange=a.exchange, xcap=a.xcap) if a.sharded
+              else run_patcher(a.seed, a.steps, a.universe, a.burst, schema=a.schema) if a.patcher else run_expiry(a.seed, a.steps) if a.expiry
               else run_reads(a.seed, a.steps, schema=a.schema, acyclic=a.acyclic, recycle=a.recycle, compact_early=a.compact_early, universe=a.universe, engine=not a.dry,
                              depth_case=a.depth_case) if a.reads
               else run(a.seed, a.steps, burst=a.burst, universe=a.universe, compact_early=a.compact_early, schema=a.schema, recycle=a.recycle, acyclic=a.acyclic))

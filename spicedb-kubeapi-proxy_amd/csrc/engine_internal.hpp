@@ -589,7 +589,7 @@ struct ShardCall {
     ShardCall(const ShardCall &) = delete;
     ShardCall &operator=(const ShardCall &) = delete;
     ~ShardCall();
-    int begin(acl_engine *h_, bool fresh, bool need_reverse, bool combine_ok = false /* the caller evaluates schemas with `&` / `-` (the native Check loop) */,
+    int begin(acl_engine *h_, bool fresh, bool need_reverse, bool combine_ok = false /* the caller evaluates schemas with `&` / `-` (the native loops) */,
               bool need_subjects = false /* the subject rows of LookupSubjects must be current too (ensure_subjects) */);
 };
 DevShard dev_shard(acl_engine *h, PassCtx *c, void *d_export, size_t cap);

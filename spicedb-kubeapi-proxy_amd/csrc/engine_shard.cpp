@@ -1,8 +1,9 @@
 // engine_shard.cpp -- acl_shard_*: one engine = one shard of the type-hash partitioned graph.  Two ways to drive it:
 //   * step protocol (acl_shard_check_begin/step/import/finish, acl_shard_lookup_*): the HOST moves the exported frontier
 //     entries between shards (aclgpu/sharded.py over torch.distributed / gloo in the CPU tests);
-//   * native loop (engine_shard_rccl.cpp, acl_shard_check_bulk): the whole level loop inside this library over an RCCL
-//     communicator -- one fixed-capacity exchange per level, termination decided on the device.
+//   * native loops (engine_shard_native.cpp: acl_shard_check_bulk, acl_shard_lookup_bulk; engine_shard_subjects.cpp: acl_shard_subjects_bulk):
+//     the whole level loop inside this library over a communicator's callbacks (RCCL built in) -- one fixed-capacity exchange per level,
+//     termination decided on the device; the cycle they share is Exchange::walk (engine_shard_exchange.hpp).
 // The protocol keeps state across calls, so it owns a context of its own (h->shard_ctx, never pooled) and serialises on shard_mu.
 #include "engine_shard_exchange.hpp"
 
@@ -37,8 +38,9 @@ int ShardCall::begin(acl_engine *h_, bool fresh, bool need_reverse, bool combine
         if (rc == ACL_OK && need_subjects) rc = ensure_subjects(h);  // (a shard's subject rows: the transpose of the classes it holds)
         if (rc) return rc;
     }
-    // Schemas with `&` / `-` / `.all()`: Check through the native loop (acl_shard_check_bulk: cells in per-shard ranges of one global cell space,
-    // round 5).  The host-driven step protocol and LookupResources on the sharded graph still refuse them.
+    // Schemas with `&` / `-` / `.all()`: the three native loops evaluate them (acl_shard_check_bulk: cells in per-shard ranges of one global cell space,
+    // round 5; acl_shard_lookup_bulk and acl_shard_subjects_bulk walk the positive relaxation and confirm the candidates by one such Check).  Only the
+    // host-driven step protocol, Check and LookupResources alike, still refuses them.
     if (h->store.schema().has_combine && !combine_ok)
         return fail(ACL_ERR_FAILED_PRECONDITION, "a schema with intersection / exclusion is evaluated on the sharded graph by acl_shard_check_bulk only (LookupResources and the step protocol: use replicas)");
     if (!h->shard_ctx) {

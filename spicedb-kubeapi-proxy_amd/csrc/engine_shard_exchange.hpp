@@ -1,11 +1,18 @@
 // engine_shard_exchange.hpp -- what the native sharded loops share (engine_shard_native.cpp: Check and LookupResources; engine_shard_subjects.cpp:
-// LookupSubjects): one batch's exchange machinery and the Check loop the lookups confirm their candidates with.
+// LookupSubjects): one batch's exchange machinery with the attempt / burst / settle / grow cycle that drives it (Exchange::walk), the statistics fold, and
+// the Check loop the lookups confirm their candidates with.
 #pragma once
 #include "engine_internal.hpp"
 
 namespace aclint {
 
 constexpr uint32_t kCtrlWords = 4;  // per level: total exported, any produced, overflow code, largest block
+
+// The iterations of one walk: first, first + step, ... up to `last`; bursts are counted in exchanges (a level of Check and LookupSubjects, a VISIT / EXPAND
+// pair of LookupResources): `burst` of them before the first host synchronisation, `burst_next` before every further one
+struct WalkShape {
+    uint32_t first, step, last, burst, burst_next;
+};
 
 // One batch's exchange machinery: buffers, the per-level "are entries expected?" plan, the collectives.
 //   headers  ALWAYS travel (16 bytes per peer): they carry the counts, the produced flag and the overflow code, so termination and
@@ -64,7 +71,7 @@ struct Exchange {
         import(c->d_xhrecv.p, c->d_xrecv.p, data, c->d_xctrl.p + (size_t)it * kCtrlWords);
         return ACL_OK;
     }
-    // reads the control records of iterations [first, last] (step 1 or 2) after a burst; returns 0 = go on, 1 = done at *done_at, 2 = redo
+    // reads the control records of iterations first, first + step, ... last after a burst; returns 0 = go on, 1 = done at *done_at, 2 = redo
     int settle(uint32_t first, uint32_t last, uint32_t step, uint32_t *done_at, uint32_t *redo_code, uint32_t *redo_max, std::vector<uint8_t> *seen) {
         const uint32_t *hc = (const uint32_t *)c->h_xctrl.p;
         for (uint32_t it = first; it <= last; it += step) {
@@ -106,6 +113,52 @@ struct Exchange {
         }
         return alloc_frontier(h, c, c->frontier_entries * 4);
     }
+    // The cycle the three native walks share, in the style of level_loop (engine_internal.hpp): size and allocate the blocks, zero the control records,
+    // begin(); then bursts of iterations -- per iteration the export counters are zeroed and level(it) enqueues the walk's launches around its run(it, import)
+    // -- with ONE host synchronisation per burst, until settle() finds the iteration that neither produced nor exported (or w.last is reached).  A burst that
+    // asks for a redo is put to redo(code, max, attempt): 0 = grow() and walk again from begin(), anything else ends the walk with that value.  The next
+    // call's plan is what this walk exported where; *done_at is the iteration it ended at.
+    template <typename Begin, typename Level, typename Redo>
+    int walk(const WalkShape &w, Begin begin, Level level, Redo redo, uint32_t *done_at) {
+        std::vector<uint8_t> seen;
+        for (int attempt = 0;; attempt++) {
+            size_blocks();
+            int rc = alloc();
+            if (rc) return rc;
+            HIP_TRY(hipMemsetAsync(c->d_xctrl.p, 0, (size_t)kLevelSlots * kCtrlWords * sizeof(uint32_t), c->stream));
+            rc = begin();
+            if (rc) return rc;
+            uint32_t next = w.first, burst = w.burst, redo_max = 0, redo_code = 0;
+            int verdict = 0;
+            seen.clear();
+            while (!verdict) {
+                const uint32_t last = std::min<uint32_t>(w.last, next + w.step * (burst - 1));
+                for (uint32_t it = next; it <= last; it += w.step) {
+                    HIP_TRY(hipMemsetAsync(c->d_status.p + 2 * kLevelSlots + 1, 0, (1 + kMaxShards) * sizeof(uint32_t), c->stream));
+                    rc = level(it);
+                    if (rc) return rc;
+                }
+                HIP_TRY(hipMemcpyAsync(c->h_xctrl.p, c->d_xctrl.p, (size_t)kLevelSlots * kCtrlWords * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+                HIP_TRY(hipStreamSynchronize(c->stream));
+                ev_collect(c);
+                st->host_syncs++;
+                verdict = settle(next, last, w.step, done_at, &redo_code, &redo_max, &seen);
+                if (!verdict && last == w.last) {
+                    *done_at = w.last;
+                    verdict = 1;
+                }
+                next = last + w.step;
+                burst = w.burst_next;
+            }
+            if (verdict == 1) break;
+            rc = redo(redo_code, redo_max, attempt);
+            if (rc) return rc;
+            rc = grow(redo_code, redo_max, attempt);
+            if (rc) return rc;
+        }
+        *plan = seen;  // the next batch exchanges entries where this one exported some (iterations beyond: always)
+        return ACL_OK;
+    }
 };
 
 // (The sharded level loops merge duplicates like check_pass does -- dedup_table, engine_internal.hpp.  Merging is local to a shard: the entries struck
@@ -118,9 +171,23 @@ inline uint32_t first_xcap(PassCtx *c) {
     return c->xcap;
 }
 
+// the counters of a call that sum over its passes, chunks and confirming Checks (levels and export_capacity: each caller has its own rule)
+inline void add_stats(acl_shard_bulk_stats_t *dst, const acl_shard_bulk_stats_t &src) {
+    dst->exchanges += src.exchanges;
+    dst->data_exchanges += src.data_exchanges;
+    dst->entries_exchanged += src.entries_exchanged;
+    dst->exchanged_bytes += src.exchanged_bytes;
+    dst->host_syncs += src.host_syncs;
+    dst->retries += src.retries;
+}
+
 // the native Check loop on context c (the caller holds the shard call's locks; engine_shard_native.cpp)
 int shard_check_core(acl_engine_t *h, PassCtx *c, const acl_shard_comm_t *comm, const void *d_items, size_t n, void *d_perm_out, void *d_err_out,
                      acl_shard_bulk_stats_t *stats_out);
+// one sharded Check over `items` (the same on every shard), as the lookups confirm the candidates of a permission with `&` / `-` / `.all()`: answers and
+// per-item errors by index, the Check's own statistics in *check_stats
+int check_candidates(acl_engine_t *h, PassCtx *c, const acl_shard_comm_t *comm, const std::vector<acl_item_t> &items, std::vector<uint8_t> *perm, std::vector<int32_t> *err,
+                     acl_shard_bulk_stats_t *check_stats);
 // the built-in RCCL communicator of an engine after acl_shard_rccl_init (else ACL_ERR_FAILED_PRECONDITION, naming `who`)
 int shard_rccl_comm(acl_engine_t *h, const char *who, acl_shard_comm_t *out);
 

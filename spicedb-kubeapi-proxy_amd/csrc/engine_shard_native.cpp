@@ -131,14 +131,13 @@ int shard_check_pass(acl_engine_t *h, PassCtx *c, const acl_shard_comm_t *comm, 
         if (rc) return rc;
     }
     first_xcap(c);
-    std::vector<uint8_t> seen;
     bool grown = false;  // this pass grew the frontier or the pools already
-    for (int attempt = 0;; attempt++) {
-        X.size_blocks();
-        rc = X.alloc();
-        if (rc) return rc;
-        uint32_t *hc = (uint32_t *)c->h_xctrl.p;
-        DevGraph g = h->dev_graph(c);
+    DevGraph g;
+    DevFrontier f;
+    DevShard sh;
+    uint32_t dedup_bits = 0, done_at = 0;
+    auto begin = [&]() -> int {
+        g = h->dev_graph(c);
         if (combine) {
             // (the cell space is memset and max-reduced whole, per batch and shard -- world x 4 x node_cap bytes twice -- whatever the batch creates.  It starts a
             //  quarter of round 5's size; a shard that runs out raises kOverflowPools and the batch is redone with pools x 4 (shard_pool_shift += 2); a batch that used
@@ -161,70 +160,50 @@ int shard_check_pass(acl_engine_t *h, PassCtx *c, const acl_shard_comm_t *comm, 
             g.cell0 = (uint32_t)(n + (size_t)X.rank * cell_cap);
             g.ccount = c->d_ccount.p;
         }
-        DevFrontier f = h->dev_frontier(*c);
-        DevShard sh = X.shard();
-        uint32_t dedup_bits = 0;
+        f = h->dev_frontier(*c);
+        sh = X.shard();
         if (merging) {
-            rc = dedup_table(c, combine, &dedup_bits);
+            int rc = dedup_table(c, combine, &dedup_bits);
             if (rc) return rc;
         }
-        HIP_TRY(hipMemsetAsync(c->d_xctrl.p, 0, (size_t)kLevelSlots * kCtrlWords * sizeof(uint32_t), c->stream));
         ev_begin(c, 0);
         launch_seed(c->stream, g, f, (const uint4 *)d_items, (uint32_t)n, c->d_has.p, c->d_err.p, sh);  // also resets the status block
         ev_end(c);
-        uint32_t next = 1, burst = std::max<uint32_t>(c->levels_hint, 2), done_at = 0, redo_max = 0, redo_code = 0;
-        int verdict = 0;
-        seen.clear();
-        while (!verdict) {
-            const uint32_t last = std::min<uint32_t>(kMaxLevels, next + burst - 1);
-            for (uint32_t it = next; it <= last; it++) {
-                HIP_TRY(hipMemsetAsync(c->d_status.p + 2 * kLevelSlots + 1, 0, (1 + kMaxShards) * sizeof(uint32_t), c->stream));
-                ev_begin(c, 1);
-                launch_expand(c->stream, g, f, it, c->d_has.p, c->d_err.p, sh);
-                ev_end(c);
-                rc = X.run(it, [&](const uint4 *hdrs, const uint4 *data, bool have, uint32_t *ctrl) {
-                    launch_import_gathered(c->stream, g, f, it, hdrs, data, X.world, X.rank, X.cap, have, ctrl);
-                });
-                if (rc) return rc;
-                if (merging) launch_dedup(c->stream, f, it, c->d_dedup.p, dedup_bits, combine);  // (this level's entries, the imported ones among them)
-                c->stats.expand_launches++;
-            }
-            HIP_TRY(hipMemcpyAsync(hc, c->d_xctrl.p, (size_t)kLevelSlots * kCtrlWords * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            ev_collect(c);
-            st.host_syncs++;
-            verdict = X.settle(next, last, 1, &done_at, &redo_code, &redo_max, &seen);
-            if (!verdict && last == kMaxLevels) {
-                done_at = kMaxLevels;
-                verdict = 1;
-            }
-            next = last + 1;
-            burst = 4;
+        return ACL_OK;
+    };
+    auto level = [&](uint32_t it) -> int {
+        ev_begin(c, 1);
+        launch_expand(c->stream, g, f, it, c->d_has.p, c->d_err.p, sh);
+        ev_end(c);
+        int rc = X.run(it, [&](const uint4 *hdrs, const uint4 *data, bool have, uint32_t *ctrl) {
+            launch_import_gathered(c->stream, g, f, it, hdrs, data, X.world, X.rank, X.cap, have, ctrl);
+        });
+        if (rc) return rc;
+        if (merging) launch_dedup(c->stream, f, it, c->d_dedup.p, dedup_bits, combine);  // (this level's entries, the imported ones among them)
+        c->stats.expand_launches++;
+        return ACL_OK;
+    };
+    auto redo = [&](uint32_t redo_code, uint32_t redo_max, int attempt) -> int {
+        // the frontier (or, on a cyclic graph under `&` / `-`, the combine pools) ran out: a batch of one merge slice that outgrew a frontier sized for
+        // thousands of entries per item is exploding, a larger one gets one growth first -- then, before growing further, duplicates are merged.
+        // An outgrown export block alone (kOverflowExport) is grown by X.grow and the pass redone as it was -- unless the block is what shows the
+        // explosion first: where every hop crosses shards a level's exports are its frontier, and a block of 2^16 entries is outgrown ten levels before
+        // a frontier of 2^25 is, one redo a level.  So: one level exporting what the default frontier holds per item of a full slice (2^25 / 2^14
+        // entries) for every item of a one-slice batch, or a block outgrown for the sixth time (a graph without such cycles outgrows it once per level
+        // whose exports exceed all before, a handful), is taken for the same explosion.
+        const bool ran_out = redo_code == kOverflowPools || redo_code == 1u;
+        const bool block_explodes = redo_code == kOverflowExport && ((n <= kDedupBatch && redo_max >= 2048ull * std::max<size_t>(n, 1)) || attempt >= 5);
+        if (!merging && (block_explodes || (ran_out && (n <= kDedupBatch || grown)))) {
+            if (stats_out) *stats_out = st;
+            return kRetryMerging;
         }
-        if (verdict == 2) {
-            // the frontier (or, on a cyclic graph under `&` / `-`, the combine pools) ran out: a batch of one merge slice that outgrew a frontier sized for
-            // thousands of entries per item is exploding, a larger one gets one growth first -- then, before growing further, duplicates are merged.
-            // An outgrown export block alone (kOverflowExport) is grown by X.grow and the pass redone as it was -- unless the block is what shows the
-            // explosion first: where every hop crosses shards a level's exports are its frontier, and a block of 2^16 entries is outgrown ten levels before
-            // a frontier of 2^25 is, one redo a level.  So: one level exporting what the default frontier holds per item of a full slice (2^25 / 2^14
-            // entries) for every item of a one-slice batch, or a block outgrown for the sixth time (a graph without such cycles outgrows it once per level
-            // whose exports exceed all before, a handful), is taken for the same explosion.
-            const bool ran_out = redo_code == kOverflowPools || redo_code == 1u;
-            const bool block_explodes = redo_code == kOverflowExport && ((n <= kDedupBatch && redo_max >= 2048ull * std::max<size_t>(n, 1)) || attempt >= 5);
-            if (!merging && (block_explodes || (ran_out && (n <= kDedupBatch || grown)))) {
-                if (stats_out) *stats_out = st;
-                return kRetryMerging;
-            }
-            grown |= ran_out && (redo_code == kOverflowPools || redo_max <= X.cap);  // (X.grow: an outgrown block comes before the frontier)
-            rc = X.grow(redo_code, redo_max, attempt);
-            if (rc) return rc;
-            continue;
-        }
-        c->levels_hint = done_at;
-        st.levels = done_at;
-        c->xplan_fwd = seen;  // the next batch exchanges entries where this one exported some (levels beyond: always)
-        break;
-    }
+        grown |= ran_out && (redo_code == kOverflowPools || redo_max <= X.cap);  // (X.grow: an outgrown block comes before the frontier)
+        return 0;
+    };
+    rc = X.walk(WalkShape{1, 1, kMaxLevels, std::max<uint32_t>(c->levels_hint, 2), 4}, begin, level, redo, &done_at);
+    if (rc) return rc;
+    c->levels_hint = done_at;
+    st.levels = done_at;
     // HAS beats error beats NO: a byte-wise max across shards, then the answers on every shard
     if (n) {
         rc = comm->all_reduce_max_u8(comm->user, c->d_has.p, n + cells, (void *)c->stream);
@@ -273,17 +252,6 @@ int shard_check_pass(acl_engine_t *h, PassCtx *c, const acl_shard_comm_t *comm, 
     return ACL_OK;
 }
 
-void add_pass_stats(acl_shard_bulk_stats_t *a, const acl_shard_bulk_stats_t &b) {
-    a->levels = std::max(a->levels, b.levels);
-    a->exchanges += b.exchanges;
-    a->host_syncs += b.host_syncs;
-    a->retries += b.retries;
-    a->exchanged_bytes += b.exchanged_bytes;
-    a->entries_exchanged += b.entries_exchanged;
-    a->export_capacity = std::max(a->export_capacity, b.export_capacity);
-    a->data_exchanges += b.data_exchanges;
-}
-
 }  // namespace
 
 // the native Check loop on context c (the caller holds the shard call's locks): acl_shard_check_bulk, and the forward half of LookupResources over
@@ -305,9 +273,28 @@ int aclint::shard_check_core(acl_engine_t *h, PassCtx *c, const acl_shard_comm_t
         acl_shard_bulk_stats_t pst{};
         rc = shard_check_pass(h, c, comm, (const uint4 *)d_items + off, m, (uint8_t *)d_perm_out + off, d_err_out ? (int32_t *)d_err_out + off : nullptr, &pst, true);
         if (rc) return rc;
-        add_pass_stats(&st, pst);
+        add_stats(&st, pst);
+        st.levels = std::max(st.levels, pst.levels);
+        st.export_capacity = std::max(st.export_capacity, pst.export_capacity);
     }
     if (stats_out) *stats_out = st;
+    return ACL_OK;
+}
+
+int aclint::check_candidates(acl_engine_t *h, PassCtx *c, const acl_shard_comm_t *comm, const std::vector<acl_item_t> &items, std::vector<uint8_t> *perm,
+                             std::vector<int32_t> *err, acl_shard_bulk_stats_t *check_stats) {
+    perm->assign(items.size(), 0);
+    err->assign(items.size(), 0);
+    *check_stats = acl_shard_bulk_stats_t{};
+    if (items.empty()) return ACL_OK;
+    HIP_TRY(c->d_items.ensure(items.size()));
+    HIP_TRY(c->d_perm.ensure(items.size()));
+    HIP_TRY(c->d_errout.ensure(items.size()));
+    HIP_TRY(hipMemcpy(c->d_items.p, items.data(), items.size() * sizeof(acl_item_t), hipMemcpyHostToDevice));
+    int rc = shard_check_core(h, c, comm, c->d_items.p, items.size(), c->d_perm.p, c->d_errout.p, check_stats);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(perm->data(), c->d_perm.p, items.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(err->data(), c->d_errout.p, items.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
     return ACL_OK;
 }
 
@@ -369,64 +356,43 @@ int acl_shard_lookup_bulk(acl_engine_t *h, const acl_shard_comm_t *comm, int rty
     if (n) std::memcpy(c->h_in.p, sids, n * sizeof(uint32_t));
     HIP_TRY(hipMemcpyAsync(c->d_sids.p, c->h_in.p, std::max<size_t>(n, 1) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     first_xcap(c);
-    std::vector<uint8_t> seen;
     constexpr uint32_t kMaxIter = 2 * (kMaxLevels + 1);  // (iteration slots: kLevelSlots = 128)
-    for (int attempt = 0;; attempt++) {
-        X.size_blocks();
-        rc = X.alloc();
-        if (rc) return rc;
-        uint32_t *hc = (uint32_t *)c->h_xctrl.p;
-        DevFrontier f = h->dev_frontier(*c);
-        DevReverse r = h->dev_reverse(c, (uint32_t)vwords);
-        DevShard sh = X.shard();
-        HIP_TRY(hipMemsetAsync(c->d_xctrl.p, 0, (size_t)kLevelSlots * kCtrlWords * sizeof(uint32_t), c->stream));
-        HIP_TRY(hipMemsetAsync(c->d_visited.p, 0, std::max<size_t>(n, 1) * vwords * 4, c->stream));
-        launch_rev_seed(c->stream, f, c->d_sids.p, (uint32_t)n, key);  // seeds + status block
-        ev_begin(c, 1);
-        launch_rev_expand(c->stream, r, f, 1, REV_EXPAND, sh);  // iteration 1: the seeds
-        ev_end(c);
-        c->stats.expand_launches++;
-        uint32_t next = 2, pairs = std::max<uint32_t>(c->rev_levels_hint, 2), done_at = 0, redo_max = 0, redo_code = 0;
-        int verdict = 0;
-        seen.clear();
-        while (!verdict) {
-            const uint32_t last = std::min<uint32_t>(kMaxIter, next + 2 * pairs - 2);  // VISIT iterations next, next + 2, ..., last
-            for (uint32_t it = next; it <= last; it += 2) {
-                HIP_TRY(hipMemsetAsync(c->d_status.p + 2 * kLevelSlots + 1, 0, (1 + kMaxShards) * sizeof(uint32_t), c->stream));
-                ev_begin(c, 1);
-                launch_rev_expand(c->stream, r, f, it, REV_VISIT, sh);
-                ev_end(c);
-                rc = X.run(it, [&](const uint4 *hdrs, const uint4 *data, bool have, uint32_t *ctrl) {
-                    launch_rev_import_gathered(c->stream, r, f, it, hdrs, data, X.world, X.rank, X.cap, have, ctrl);
-                });
-                if (rc) return rc;
-                ev_begin(c, 1);
-                launch_rev_expand(c->stream, r, f, it + 1, REV_EXPAND, sh);
-                ev_end(c);
-                c->stats.expand_launches += 2;
-            }
-            HIP_TRY(hipMemcpyAsync(hc, c->d_xctrl.p, (size_t)kLevelSlots * kCtrlWords * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            ev_collect(c);
-            st.host_syncs++;
-            verdict = X.settle(next, last, 2, &done_at, &redo_code, &redo_max, &seen);
-            if (!verdict && last >= kMaxIter) {
-                done_at = kMaxIter;
-                verdict = 1;
-            }
-            next = last + 2;
-            pairs = 3;
-        }
-        if (verdict == 2) {
-            rc = X.grow(redo_code, redo_max, attempt);
+    DevFrontier f;
+    DevReverse r;
+    DevShard sh;
+    uint32_t done_at = 0;
+    rc = X.walk(
+        WalkShape{2, 2, kMaxIter, std::max<uint32_t>(c->rev_levels_hint, 2), 3},  // VISIT iterations 2, 4, ...: a burst is so many VISIT / EXPAND pairs
+        [&]() -> int {
+            f = h->dev_frontier(*c);
+            r = h->dev_reverse(c, (uint32_t)vwords);
+            sh = X.shard();
+            HIP_TRY(hipMemsetAsync(c->d_visited.p, 0, std::max<size_t>(n, 1) * vwords * 4, c->stream));
+            launch_rev_seed(c->stream, f, c->d_sids.p, (uint32_t)n, key);  // seeds + status block
+            ev_begin(c, 1);
+            launch_rev_expand(c->stream, r, f, 1, REV_EXPAND, sh);  // iteration 1: the seeds
+            ev_end(c);
+            c->stats.expand_launches++;
+            return ACL_OK;
+        },
+        [&](uint32_t it) -> int {
+            ev_begin(c, 1);
+            launch_rev_expand(c->stream, r, f, it, REV_VISIT, sh);
+            ev_end(c);
+            int rc = X.run(it, [&](const uint4 *hdrs, const uint4 *data, bool have, uint32_t *ctrl) {
+                launch_rev_import_gathered(c->stream, r, f, it, hdrs, data, X.world, X.rank, X.cap, have, ctrl);
+            });
             if (rc) return rc;
-            continue;
-        }
-        c->rev_levels_hint = std::max<uint32_t>(1, done_at / 2);
-        st.levels = done_at / 2;
-        c->xplan_rev = seen;
-        break;
-    }
+            ev_begin(c, 1);
+            launch_rev_expand(c->stream, r, f, it + 1, REV_EXPAND, sh);
+            ev_end(c);
+            c->stats.expand_launches += 2;
+            return ACL_OK;
+        },
+        [](uint32_t, uint32_t, int) { return 0; }, &done_at);
+    if (rc) return rc;
+    c->rev_levels_hint = std::max<uint32_t>(1, done_at / 2);
+    st.levels = done_at / 2;
     // result rows: the resource type's owner holds them; everybody else contributes zeros to a byte-wise max
     if (n) {
         const size_t woff = h->snap.slot_bit_base[target] / 32;
@@ -456,28 +422,16 @@ int acl_shard_lookup_bulk(acl_engine_t *h, const acl_shard_comm_t *comm, int rty
                     items.push_back(acl_item_t{(uint16_t)rtype, (uint16_t)perm, (uint32_t)(w * 32 + (size_t)__builtin_ctz(m)), (uint16_t)stype, sr, sids[i]});
         if (items.size() > 0xFFFFFFF0ull) return fail(ACL_ERR_RESOURCE_EXHAUSTED, "lookup over a non-monotone permission: too many candidates for one Check");
         if (!items.empty()) {
-            HIP_TRY(c->d_items.ensure(items.size()));
-            HIP_TRY(c->d_perm.ensure(items.size()));
-            HIP_TRY(hipMemcpy(c->d_items.p, items.data(), items.size() * sizeof(acl_item_t), hipMemcpyHostToDevice));
+            std::vector<uint8_t> ans;
+            std::vector<int32_t> errs;
             acl_shard_bulk_stats_t cst{};
-            const bool strict = !h->lenient_lookup;  // (a candidate whose Check errs fails the call, as on the unsharded graph: lookup_refine)
-            if (strict) HIP_TRY(c->d_errout.ensure(items.size()));
-            rc = shard_check_core(h, c, comm, c->d_items.p, items.size(), c->d_perm.p, strict ? c->d_errout.p : nullptr, &cst);
+            rc = check_candidates(h, c, comm, items, &ans, &errs, &cst);
             if (rc) return rc;
-            if (strict) {  // (every shard holds the same answers: all of them fail, or none)
-                std::vector<int32_t> errs(items.size());
-                HIP_TRY(hipMemcpy(errs.data(), c->d_errout.p, errs.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+            if (!h->lenient_lookup)  // (a candidate whose Check errs fails the call, as on the unsharded graph: lookup_refine; every shard holds the same answers: all of them fail, or none)
                 for (size_t k = 0; k < errs.size(); k++)
                     if (errs[k]) return lookup_candidate_error(h, errs[k], items[k].resource_id, items[k].subject_id);
-            }
-            st.retries += cst.retries;
+            add_stats(&st, cst);
             export_cap = std::max<uint64_t>(export_cap, cst.export_capacity);
-            st.exchanges += cst.exchanges;
-            st.entries_exchanged += cst.entries_exchanged;
-            st.exchanged_bytes += cst.exchanged_bytes;
-            st.host_syncs += cst.host_syncs;
-            std::vector<uint8_t> ans(items.size());
-            HIP_TRY(hipMemcpy(ans.data(), c->d_perm.p, ans.size(), hipMemcpyDeviceToHost));
             size_t k = 0;
             for (size_t i = 0; i < n; i++)
                 for (size_t w = 0; w < bitmap_words; w++) {
@@ -540,15 +494,17 @@ int acl_shard_rccl_destroy(acl_engine_t *h) {
 }
 
 int acl_shard_check_bulk_rccl(acl_engine_t *h, const void *d_items, size_t n, void *d_perm_out, void *d_err_out, acl_shard_bulk_stats_t *stats_out) {
-    if (!h->rccl_comm) return fail(ACL_ERR_FAILED_PRECONDITION, "acl_shard_check_bulk_rccl without acl_shard_rccl_init");
-    acl_shard_comm_t comm{h->rccl_comm, rccl_all_gather, rccl_all_reduce_max, rccl_all_to_all};
+    acl_shard_comm_t comm{};
+    int rc = shard_rccl_comm(h, "acl_shard_check_bulk_rccl", &comm);
+    if (rc) return rc;
     return acl_shard_check_bulk(h, &comm, d_items, n, d_perm_out, d_err_out, stats_out);
 }
 
 int acl_shard_lookup_bulk_rccl(acl_engine_t *h, int rtype, int perm, int stype, int srel, const uint32_t *sids, size_t n, void *d_bitmaps_out, size_t bitmap_words,
                                acl_shard_bulk_stats_t *stats_out) {
-    if (!h->rccl_comm) return fail(ACL_ERR_FAILED_PRECONDITION, "acl_shard_lookup_bulk_rccl without acl_shard_rccl_init");
-    acl_shard_comm_t comm{h->rccl_comm, rccl_all_gather, rccl_all_reduce_max, rccl_all_to_all};
+    acl_shard_comm_t comm{};
+    int rc = shard_rccl_comm(h, "acl_shard_lookup_bulk_rccl", &comm);
+    if (rc) return rc;
     return acl_shard_lookup_bulk(h, &comm, rtype, perm, stype, srel, sids, n, d_bitmaps_out, bitmap_words, stats_out);
 }
 

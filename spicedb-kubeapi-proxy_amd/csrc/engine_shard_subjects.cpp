@@ -3,7 +3,7 @@
 // The unsharded walk (kernels.hip k_subj_local) is one block's private log and needs every row it can reach in that device's HBM.  Here the walk is
 // level-synchronous and chip-wide (k_subj_expand): a state is expanded on the shard that owns its slot's type, over that shard's subject rows (the
 // transpose of the classes it holds: plan_subjects.cpp), and a child of another shard's type crosses in the level's exchange -- the same Exchange, the
-// same communicator callbacks and the same burst / settle / grow-and-redo cycle as the Check and LookupResources loops (engine_shard_native.cpp).
+// same communicator callbacks and the same cycle, Exchange::walk (engine_shard_exchange.hpp), as the Check and LookupResources loops (engine_shard_native.cpp).
 //   * visited bits live on the owner only; every visit decision for level L is taken during iteration L - 1 (kernels.hip, above k_subj_expand);
 //   * every shard marks the subjects ITS rows name into a partial row; the partial rows are all-gathered and OR-ed (k_subj_fold) -- not max-reduced
 //     byte-wise: several shards set different bits of one byte.  Wildcard flags are one 0/1 byte per lookup: those are max-reduced;
@@ -17,34 +17,6 @@
 namespace {
 
 constexpr size_t kSubjChunkWords = (size_t)1 << 28;  // <= 1 GiB of visited bits + partial rows per chunk (engine_subjects.cpp subjects_walk), and of gathered rows
-
-void add_stats(acl_shard_bulk_stats_t *st, const acl_shard_bulk_stats_t &x) {
-    st->exchanges += x.exchanges;
-    st->data_exchanges += x.data_exchanges;
-    st->entries_exchanged += x.entries_exchanged;
-    st->exchanged_bytes += x.exchanged_bytes;
-    st->host_syncs += x.host_syncs;
-    st->retries += x.retries;
-}
-
-// one sharded Check over `items` (the same on every shard): answers and per-item errors by index
-int check_candidates(acl_engine_t *h, PassCtx *c, const acl_shard_comm_t *comm, const std::vector<acl_item_t> &items, std::vector<uint8_t> *perm, std::vector<int32_t> *err,
-                     acl_shard_bulk_stats_t *st) {
-    perm->assign(items.size(), 0);
-    err->assign(items.size(), 0);
-    if (items.empty()) return ACL_OK;
-    HIP_TRY(c->d_items.ensure(items.size()));
-    HIP_TRY(c->d_perm.ensure(items.size()));
-    HIP_TRY(c->d_errout.ensure(items.size()));
-    HIP_TRY(hipMemcpy(c->d_items.p, items.data(), items.size() * sizeof(acl_item_t), hipMemcpyHostToDevice));
-    acl_shard_bulk_stats_t cst{};
-    int rc = shard_check_core(h, c, comm, c->d_items.p, items.size(), c->d_perm.p, c->d_errout.p, &cst);
-    if (rc) return rc;
-    add_stats(st, cst);
-    HIP_TRY(hipMemcpy(perm->data(), c->d_perm.p, items.size(), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(err->data(), c->d_errout.p, items.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return ACL_OK;
-}
 
 }  // namespace
 
@@ -87,7 +59,6 @@ int acl_shard_subjects_bulk(acl_engine_t *h, const acl_shard_comm_t *comm, int r
     first_xcap(c);
     HIP_TRY(c->d_subj_flags.ensure((std::max<size_t>(n, 1) + 3) / 4));
     uint8_t *d_flags = reinterpret_cast<uint8_t *>(c->d_subj_flags.p);
-    std::vector<uint8_t> seen;
     for (size_t b = 0; b < n;) {
         const size_t m = std::min(n - b, mmax);
         if (m > c->frontier_entries) {
@@ -100,59 +71,39 @@ int acl_shard_subjects_bulk(acl_engine_t *h, const acl_shard_comm_t *comm, int r
         HIP_TRY(c->h_in.ensure(m * sizeof(uint32_t)));
         std::memcpy(c->h_in.p, rids + b, m * sizeof(uint32_t));
         HIP_TRY(hipMemcpyAsync(c->d_sids.p, c->h_in.p, m * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-        for (int attempt = 0;; attempt++) {
-            X.size_blocks();
-            rc = X.alloc();
-            if (rc) return rc;
-            uint32_t *hc = (uint32_t *)c->h_xctrl.p;
-            const DevFrontier f = h->dev_frontier(*c);
-            const DevShard sh = X.shard();
-            const DevSubjLevel s{g, c->d_subj_visited.p, c->d_subj_rows.p, d_flags + b, (uint32_t)need, key};
-            HIP_TRY(hipMemsetAsync(c->d_xctrl.p, 0, (size_t)kLevelSlots * kCtrlWords * sizeof(uint32_t), c->stream));
-            HIP_TRY(hipMemsetAsync(c->d_subj_visited.p, 0, m * vwords * 4, c->stream));
-            if (need) HIP_TRY(hipMemsetAsync(c->d_subj_rows.p, 0, m * need * 4, c->stream));
-            HIP_TRY(hipMemsetAsync(d_flags + b, 0, m, c->stream));
-            ev_begin(c, 0);
-            launch_subj_seed(c->stream, s, f, c->d_sids.p, (uint32_t)m, target, sh);  // seeds + status block
-            ev_end(c);
-            uint32_t next = 1, burst = std::max<uint32_t>(c->subj_levels_hint, 2), done_at = 0, redo_max = 0, redo_code = 0;
-            int verdict = 0;
-            seen.clear();
-            while (!verdict) {
-                const uint32_t last = std::min<uint32_t>(kMaxLevels, next + burst - 1);
-                for (uint32_t it = next; it <= last; it++) {
-                    HIP_TRY(hipMemsetAsync(c->d_status.p + 2 * kLevelSlots + 1, 0, (1 + kMaxShards) * sizeof(uint32_t), c->stream));
-                    ev_begin(c, 1);
-                    launch_subj_expand(c->stream, s, f, it, sh);
-                    ev_end(c);
-                    rc = X.run(it, [&](const uint4 *hdrs, const uint4 *data, bool have, uint32_t *ctrl) {
-                        launch_subj_import_gathered(c->stream, s, f, it, hdrs, data, X.world, X.rank, X.cap, have, ctrl);
-                    });
-                    if (rc) return rc;
-                    c->stats.expand_launches++;
-                }
-                HIP_TRY(hipMemcpyAsync(hc, c->d_xctrl.p, (size_t)kLevelSlots * kCtrlWords * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-                HIP_TRY(hipStreamSynchronize(c->stream));
-                ev_collect(c);
-                st.host_syncs++;
-                verdict = X.settle(next, last, 1, &done_at, &redo_code, &redo_max, &seen);
-                if (!verdict && last == kMaxLevels) {
-                    done_at = kMaxLevels;
-                    verdict = 1;
-                }
-                next = last + 1;
-                burst = 4;
-            }
-            if (verdict == 2) {
-                rc = X.grow(redo_code, redo_max, attempt);
+        DevFrontier f;
+        DevShard sh;
+        DevSubjLevel s;
+        uint32_t done_at = 0;
+        rc = X.walk(
+            WalkShape{1, 1, kMaxLevels, std::max<uint32_t>(c->subj_levels_hint, 2), 4},
+            [&]() -> int {
+                f = h->dev_frontier(*c);
+                sh = X.shard();
+                s = DevSubjLevel{g, c->d_subj_visited.p, c->d_subj_rows.p, d_flags + b, (uint32_t)need, key};
+                HIP_TRY(hipMemsetAsync(c->d_subj_visited.p, 0, m * vwords * 4, c->stream));
+                if (need) HIP_TRY(hipMemsetAsync(c->d_subj_rows.p, 0, m * need * 4, c->stream));
+                HIP_TRY(hipMemsetAsync(d_flags + b, 0, m, c->stream));
+                ev_begin(c, 0);
+                launch_subj_seed(c->stream, s, f, c->d_sids.p, (uint32_t)m, target, sh);  // seeds + status block
+                ev_end(c);
+                return ACL_OK;
+            },
+            [&](uint32_t it) -> int {
+                ev_begin(c, 1);
+                launch_subj_expand(c->stream, s, f, it, sh);
+                ev_end(c);
+                int rc = X.run(it, [&](const uint4 *hdrs, const uint4 *data, bool have, uint32_t *ctrl) {
+                    launch_subj_import_gathered(c->stream, s, f, it, hdrs, data, X.world, X.rank, X.cap, have, ctrl);
+                });
                 if (rc) return rc;
-                continue;
-            }
-            c->subj_levels_hint = done_at;
-            st.levels = std::max(st.levels, done_at);
-            c->xplan_subj = seen;  // the next chunk / call exchanges entries where this one exported some
-            break;
-        }
+                c->stats.expand_launches++;
+                return ACL_OK;
+            },
+            [](uint32_t, uint32_t, int) { return 0; }, &done_at);
+        if (rc) return rc;
+        c->subj_levels_hint = done_at;
+        st.levels = std::max(st.levels, done_at);
         // result rows: every shard marked what ITS rows name; gathered and OR-ed, the same on every shard
         uint32_t *out = reinterpret_cast<uint32_t *>(d_bitmaps_out) + b * bitmap_words;
         if (need) {
@@ -186,6 +137,7 @@ int acl_shard_subjects_bulk(acl_engine_t *h, const acl_shard_comm_t *comm, int r
     std::vector<acl_item_t> items;
     std::vector<uint8_t> ans;
     std::vector<int32_t> err;
+    acl_shard_bulk_stats_t cst{};
     if (n && nonmono) {
         std::vector<uint32_t> rows(n * bitmap_words);
         if (!rows.empty()) HIP_TRY(hipMemcpy(rows.data(), d_bitmaps_out, rows.size() * 4, hipMemcpyDeviceToHost));
@@ -201,8 +153,9 @@ int acl_shard_subjects_bulk(acl_engine_t *h, const acl_shard_comm_t *comm, int r
                         items.push_back(acl_item_t{(uint16_t)rtype, (uint16_t)perm, rids[i1], (uint16_t)stype, srl, (uint32_t)(w * 32 + (size_t)__builtin_ctz(mm))});
                 if (wild[i1]) items.push_back(acl_item_t{(uint16_t)rtype, (uint16_t)perm, rids[i1], (uint16_t)stype, srl, kFreshSubject});
             }
-            rc = check_candidates(h, c, comm, items, &ans, &err, &st);
+            rc = check_candidates(h, c, comm, items, &ans, &err, &cst);
             if (rc) return rc;
+            add_stats(&st, cst);
             size_t k = 0;
             for (size_t i = i0; i < i1; i++) {  // (every shard holds the same answers: all of them fail, or none)
                 uint32_t *row = rows.data() + i * bitmap_words;
@@ -233,8 +186,9 @@ int acl_shard_subjects_bulk(acl_engine_t *h, const acl_shard_comm_t *comm, int r
                 const size_t m = std::min<size_t>(chunk, nobj - s0);
                 items.resize(m);
                 for (size_t j = 0; j < m; j++) items[j] = acl_item_t{(uint16_t)rtype, (uint16_t)perm, rids[i], (uint16_t)stype, srl, (uint32_t)(s0 + j)};
-                rc = check_candidates(h, c, comm, items, &ans, &err, &st);
+                rc = check_candidates(h, c, comm, items, &ans, &err, &cst);
                 if (rc) return rc;
+                add_stats(&st, cst);
                 for (size_t j = 0; j < m; j++) {
                     if (s0 + j == wid) continue;
                     if (err[j] && strict) return subjects_error(err[j], rids[i], (uint32_t)(s0 + j));

@@ -2700,99 +2700,8 @@ __global__ __launch_bounds__(256) void k_rev_rows(DevReverse r, uint32_t target_
 }
 
 // ------------------------------------------------------------------ import
-// Appends entries of an exchanged export buffer to the frontier iteration `iter` produced (dynamic chunks only:
-// the static chunks belong to that iteration's expand waves).  FWD: keep the entries whose slot this shard owns.
-// Reverse: keep foreign states for which this shard holds parent rows.
-template <bool FWD>
-__global__ __launch_bounds__(256) void k_import(DevFrontier f, uint32_t iter, const uint4 *__restrict__ in, uint32_t n, const SlotProg *progs,
-                                                const RevProg *rprogs, uint32_t rank) {
-    const uint32_t lane = lane_id();
-    const uint32_t wave = blockIdx.x * 4 + (threadIdx.x >> 6), nw = gridDim.x * 4;
-    uint4 *__restrict__ out = f.buf[iter & 1u];
-    uint32_t *out_counts = f.counts[iter & 1u];
-    uint32_t *out_nchunks = f.nchunks + iter;
-    uint32_t cur = kNoSpace, fill = kChunk, produced = 0;
-    for (uint32_t x = wave; (uint64_t)x * 64 < n; x += nw) {
-        const uint32_t i = x * 64 + lane;
-        const uint4 e = i < n ? in[i] : make_uint4(0, 0, kDeadMeta, 0);
-        bool mine = i < n && e.z != kDeadMeta;
-        if (mine) mine = FWD ? progs[meta_slot(e.z)].owner == rank : (rprogs[e.z & 0x1FFFu].n & ~kRevRemoteBit) != 0;
-        const uint64_t b = __ballot(mine);
-        if (!b) continue;
-        const uint32_t need = (uint32_t)__popcll(b);
-        if (fill + need > kChunk) {
-            if (lane == 0 && cur != kNoSpace) out_counts[cur] = fill;
-            uint32_t c = 0;
-            if (lane == 0) c = atomicAdd(out_nchunks, 1u);
-            c = uniform(c) + f.nwaves;
-            if (c >= f.max_chunks) {
-                if (lane == 0) *f.overflow = 1u;
-                cur = kNoSpace;
-                break;
-            }
-            cur = c;
-            fill = 0;
-        }
-        if (mine) out[(size_t)cur * kChunk + fill + lanes_below(b)] = e;
-        fill += need;
-        produced += need;
-    }
-    if (lane == 0) {
-        if (cur != kNoSpace) out_counts[cur] = fill;
-        if (produced) f.any[iter] = 1u;
-    }
-}
-
-// ---------------------------------------------------------------- native sharded loop (engine_shard_native.cpp)
-// Exchange blocks, one per (shard, level) in the all-gather form and one per (shard, destination, level) in the all-to-all form: a 16-byte
-// HEADER and up to `cap` entries.  header = {x: entries in this block, y: this shard produced local work | overflow code << 1,
-// z: the largest block this shard filled this level, w: entries this shard exported this level in all}.  Written on the device, so the host
-// never waits between levels; headers and entries travel in separate collectives (the entries' one is skipped on levels that are known
-// to export nothing).  exp_count = [0] all-gather form; [1 + d] per destination.
-__global__ __launch_bounds__(64) void k_xhdr(uint4 *hdr, uint32_t nblocks, const uint32_t *exp_count, const uint32_t *any_iter, const uint32_t *overflow) {
-    const uint32_t d = threadIdx.x;
-    if (d >= nblocks) return;
-    const uint32_t flags = (*any_iter ? 1u : 0u) | (*overflow << 1);
-    if (nblocks == 1) {
-        const uint32_t c = exp_count[0];
-        hdr[0] = make_uint4(c, flags, c, c);
-        return;
-    }
-    uint32_t mx = 0, tot = 0;
-    for (uint32_t k = 0; k < nblocks; k++) {
-        const uint32_t c = exp_count[1 + k];
-        mx = max(mx, c);
-        tot += c;
-    }
-    hdr[d] = make_uint4(exp_count[1 + d], flags, mx, tot);
-}
-
-// What the gathered imports share.  fold_headers: the own row's first wave folds all headers into the level's control record {total exported, any shard
-// produced, overflow code, largest block} (call with the first 64 threads of one block).  ImportOut: a wave's append cursor into the dynamic chunks of the
-// frontier iteration `iter` produced (the static chunks belong to that iteration's expand waves).
-__device__ __forceinline__ void fold_headers(const uint4 *__restrict__ hdrs, uint32_t world, uint32_t cap, uint32_t have_data, uint32_t *ctrl, uint32_t lane) {
-    uint32_t total = 0, anyp = 0, over = 0, mx = 0;
-    for (uint32_t r = lane; r < world; r += 64) {
-        const uint4 h = hdrs[r];
-        total += h.w;
-        anyp |= h.y & 1u;
-        over |= (h.y >> 1) | (h.z > cap ? kOverflowExport : 0u) | ((!have_data && h.w) ? 4u : 0u);  // (h.w, every shard's own included: the same verdict on every shard)
-        mx = max(mx, h.z);
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        total += (uint32_t)__shfl_xor((int)total, d, 64);
-        anyp |= (uint32_t)__shfl_xor((int)anyp, d, 64);
-        over |= (uint32_t)__shfl_xor((int)over, d, 64);
-        mx = max(mx, (uint32_t)__shfl_xor((int)mx, d, 64));
-    }
-    if (lane == 0) {
-        ctrl[0] = total;
-        ctrl[1] = anyp;
-        ctrl[2] = over;
-        ctrl[3] = mx;
-    }
-}
+// ImportOut: a wave's append cursor into the dynamic chunks of the frontier iteration `iter` produced (the static chunks belong to that iteration's
+// expand waves) -- the step protocol's k_import and the native loops' gathered imports, below.
 struct ImportOut {
     uint4 *__restrict__ out;
     uint32_t *counts, *nchunks, *overflow, *any;
@@ -2831,6 +2740,88 @@ struct ImportOut {
     }
 };
 
+// Appends entries of an exchanged export buffer to the frontier iteration `iter` produced.  FWD: keep the entries whose slot this shard owns.
+// Reverse: keep foreign states for which this shard holds parent rows.
+template <bool FWD>
+__global__ __launch_bounds__(256) void k_import(DevFrontier f, uint32_t iter, const uint4 *__restrict__ in, uint32_t n, const SlotProg *progs,
+                                                const RevProg *rprogs, uint32_t rank) {
+    const uint32_t lane = lane_id();
+    const uint32_t wave = blockIdx.x * 4 + (threadIdx.x >> 6), nw = gridDim.x * 4;
+    ImportOut io(f, iter);
+    for (uint32_t x = wave; (uint64_t)x * 64 < n; x += nw) {
+        const uint32_t i = x * 64 + lane;
+        const uint4 e = i < n ? in[i] : make_uint4(0, 0, kDeadMeta, 0);
+        bool mine = i < n && e.z != kDeadMeta;
+        if (mine) mine = FWD ? progs[meta_slot(e.z)].owner == rank : (rprogs[e.z & 0x1FFFu].n & ~kRevRemoteBit) != 0;
+        if (!io.append(mine, e, lane)) break;
+    }
+    io.close(lane);
+}
+
+// ---------------------------------------------------------------- native sharded loop (engine_shard_native.cpp)
+// Exchange blocks, one per (shard, level) in the all-gather form and one per (shard, destination, level) in the all-to-all form: a 16-byte
+// HEADER and up to `cap` entries.  header = {x: entries in this block, y: this shard produced local work | overflow code << 1,
+// z: the largest block this shard filled this level, w: entries this shard exported this level in all}.  Written on the device, so the host
+// never waits between levels; headers and entries travel in separate collectives (the entries' one is skipped on levels that are known
+// to export nothing).  exp_count = [0] all-gather form; [1 + d] per destination.
+__global__ __launch_bounds__(64) void k_xhdr(uint4 *hdr, uint32_t nblocks, const uint32_t *exp_count, const uint32_t *any_iter, const uint32_t *overflow) {
+    const uint32_t d = threadIdx.x;
+    if (d >= nblocks) return;
+    const uint32_t flags = (*any_iter ? 1u : 0u) | (*overflow << 1);
+    if (nblocks == 1) {
+        const uint32_t c = exp_count[0];
+        hdr[0] = make_uint4(c, flags, c, c);
+        return;
+    }
+    uint32_t mx = 0, tot = 0;
+    for (uint32_t k = 0; k < nblocks; k++) {
+        const uint32_t c = exp_count[1 + k];
+        mx = max(mx, c);
+        tot += c;
+    }
+    hdr[d] = make_uint4(exp_count[1 + d], flags, mx, tot);
+}
+
+// What the gathered imports share.  fold_headers: the own row's first wave folds all headers into the level's control record {total exported, any shard
+// produced, overflow code, largest block} (call with the first 64 threads of one block).  They append through ImportOut, above.
+__device__ __forceinline__ void fold_headers(const uint4 *__restrict__ hdrs, uint32_t world, uint32_t cap, uint32_t have_data, uint32_t *ctrl, uint32_t lane) {
+    uint32_t total = 0, anyp = 0, over = 0, mx = 0;
+    for (uint32_t r = lane; r < world; r += 64) {
+        const uint4 h = hdrs[r];
+        total += h.w;
+        anyp |= h.y & 1u;
+        over |= (h.y >> 1) | (h.z > cap ? kOverflowExport : 0u) | ((!have_data && h.w) ? 4u : 0u);  // (h.w, every shard's own included: the same verdict on every shard)
+        mx = max(mx, h.z);
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        total += (uint32_t)__shfl_xor((int)total, d, 64);
+        anyp |= (uint32_t)__shfl_xor((int)anyp, d, 64);
+        over |= (uint32_t)__shfl_xor((int)over, d, 64);
+        mx = max(mx, (uint32_t)__shfl_xor((int)mx, d, 64));
+    }
+    if (lane == 0) {
+        ctrl[0] = total;
+        ctrl[1] = anyp;
+        ctrl[2] = over;
+        ctrl[3] = mx;
+    }
+}
+// The gathered imports' opening (blockIdx.y = source shard): the own row's first wave folds the headers and the row is done; without entries so is every
+// other row; else *in / *n are what the block's source shard sent, the count read from its header.  false: nothing to import, return.
+__device__ __forceinline__ bool gathered_input(const uint4 *__restrict__ hdrs, const uint4 *__restrict__ data, uint32_t world, uint32_t rank, uint32_t cap, uint32_t have_data,
+                                               uint32_t *ctrl, uint32_t lane, const uint4 *__restrict__ *in, uint32_t *n) {
+    const uint32_t src = blockIdx.y;
+    if (src == rank) {
+        if (blockIdx.x == 0 && threadIdx.x < 64) fold_headers(hdrs, world, cap, have_data, ctrl, lane);
+        return false;
+    }
+    if (!have_data) return false;
+    *in = data + (size_t)src * cap;
+    *n = min(hdrs[src].x, cap);
+    return true;
+}
+
 // After the exchange: blockIdx.y = source shard.  Rows of other shards import what they sent (FWD: the entries whose slot this shard owns;
 // reverse: foreign states for which this shard holds parent rows), the count read from the source's header; the own row's first wave folds all
 // headers into the level's control record {total exported, any shard produced, overflow code, largest block} -- identical on every shard, so
@@ -2841,14 +2832,9 @@ __global__ __launch_bounds__(256) void k_import_gathered(DevFrontier f, uint32_t
                                                          uint32_t rank, uint32_t cap, uint32_t have_data, const SlotProg *progs, const RevProg *rprogs,
                                                          uint32_t *ctrl) {
     const uint32_t lane = lane_id();
-    const uint32_t src = blockIdx.y;
-    if (src == rank) {
-        if (blockIdx.x == 0 && threadIdx.x < 64) fold_headers(hdrs, world, cap, have_data, ctrl, lane);
-        return;
-    }
-    if (!have_data) return;
-    const uint4 *__restrict__ in = data + (size_t)src * cap;
-    const uint32_t n = min(hdrs[src].x, cap);
+    const uint4 *__restrict__ in;
+    uint32_t n;
+    if (!gathered_input(hdrs, data, world, rank, cap, have_data, ctrl, lane, &in, &n)) return;
     const uint32_t wave = blockIdx.x * 4 + (threadIdx.x >> 6), nw = gridDim.x * 4;
     ImportOut io(f, iter);
     for (uint32_t x = wave; (uint64_t)x * 64 < n; x += nw) {
@@ -3027,6 +3013,9 @@ static uint32_t import_blocks(uint32_t n) {  // ~one 1024-entry chunk of input p
     const uint32_t b = (n + 4095) / 4096;
     return b < 1 ? 1 : (b > 256 ? 256 : b);
 }
+// grid x of the gathered imports (grid y = the source shards): ~one 1024-entry chunk of a block of `cap` entries per wave, at most 64 blocks a source; one
+// where no entries travelled (the own row's header fold is all there is to do)
+static uint32_t import_gathered_blocks(uint32_t cap, bool have_data) { return have_data ? std::max<uint32_t>(1, std::min<uint32_t>(64, (cap + 4095) / 4096)) : 1u; }
 void launch_import(hipStream_t s, const DevGraph &g, const DevFrontier &f, uint32_t iter, const uint4 *in, uint32_t n, const DevShard &sh) {
     if (!n) return;
     hipLaunchKernelGGL(k_import<true>, dim3(import_blocks(n)), dim3(256), 0, s, f, iter, in, n, g.progs, (const RevProg *)nullptr, sh.rank);
@@ -3036,12 +3025,12 @@ void launch_xhdr(hipStream_t s, uint4 *hdr, uint32_t nblocks, const uint32_t *ex
 }
 void launch_import_gathered(hipStream_t s, const DevGraph &g, const DevFrontier &f, uint32_t iter, const uint4 *hdrs, const uint4 *data, uint32_t world, uint32_t rank,
                             uint32_t cap, bool have_data, uint32_t *ctrl) {
-    const uint32_t bx = have_data ? std::max<uint32_t>(1, std::min<uint32_t>(64, (cap + 4095) / 4096)) : 1u;
+    const uint32_t bx = import_gathered_blocks(cap, have_data);
     hipLaunchKernelGGL(k_import_gathered<true>, dim3(bx, world), dim3(256), 0, s, f, iter, hdrs, data, world, rank, cap, have_data ? 1u : 0u, g.progs, (const RevProg *)nullptr, ctrl);
 }
 void launch_rev_import_gathered(hipStream_t s, const DevReverse &r, const DevFrontier &f, uint32_t iter, const uint4 *hdrs, const uint4 *data, uint32_t world, uint32_t rank,
                                 uint32_t cap, bool have_data, uint32_t *ctrl) {
-    const uint32_t bx = have_data ? std::max<uint32_t>(1, std::min<uint32_t>(64, (cap + 4095) / 4096)) : 1u;
+    const uint32_t bx = import_gathered_blocks(cap, have_data);
     hipLaunchKernelGGL(k_import_gathered<false>, dim3(bx, world), dim3(256), 0, s, f, iter, hdrs, data, world, rank, cap, have_data ? 1u : 0u, (const SlotProg *)nullptr, r.rprogs, ctrl);
 }
 void launch_rev_import(hipStream_t s, const DevReverse &r, const DevFrontier &f, uint32_t iter, const uint4 *in, uint32_t n) {
@@ -3771,14 +3760,9 @@ __global__ __launch_bounds__(kBlock) void k_subj_expand(DevSubjLevel s, DevFront
 __global__ __launch_bounds__(256) void k_subj_import_gathered(DevSubjLevel s, DevFrontier f, uint32_t iter, const uint4 *__restrict__ hdrs, const uint4 *__restrict__ data,
                                                               uint32_t world, uint32_t rank, uint32_t cap, uint32_t have_data, uint32_t *ctrl) {
     const uint32_t lane = lane_id();
-    const uint32_t src = blockIdx.y;
-    if (src == rank) {
-        if (blockIdx.x == 0 && threadIdx.x < 64) fold_headers(hdrs, world, cap, have_data, ctrl, lane);
-        return;
-    }
-    if (!have_data) return;
-    const uint4 *__restrict__ in = data + (size_t)src * cap;
-    const uint32_t n = min(hdrs[src].x, cap);
+    const uint4 *__restrict__ in;
+    uint32_t n;
+    if (!gathered_input(hdrs, data, world, rank, cap, have_data, ctrl, lane, &in, &n)) return;
     const uint32_t wave = blockIdx.x * 4 + (threadIdx.x >> 6), nw = gridDim.x * 4;
     ImportOut io(f, iter);
     for (uint32_t x = wave; (uint64_t)x * 64 < n; x += nw) {
@@ -3821,7 +3805,7 @@ void launch_subj_expand(hipStream_t st, const DevSubjLevel &s, const DevFrontier
 }
 void launch_subj_import_gathered(hipStream_t st, const DevSubjLevel &s, const DevFrontier &f, uint32_t iter, const uint4 *hdrs, const uint4 *data, uint32_t world,
                                  uint32_t rank, uint32_t cap, bool have_data, uint32_t *ctrl) {
-    const uint32_t bx = have_data ? std::max<uint32_t>(1, std::min<uint32_t>(64, (cap + 4095) / 4096)) : 1u;
+    const uint32_t bx = import_gathered_blocks(cap, have_data);
     hipLaunchKernelGGL(k_subj_import_gathered, dim3(bx, world), dim3(256), 0, st, s, f, iter, hdrs, data, world, rank, cap, have_data ? 1u : 0u, ctrl);
 }
 void launch_subj_fold(hipStream_t st, const uint32_t *gathered, uint32_t world, uint32_t m, uint32_t row_words, uint32_t *out, uint32_t out_stride) {

@@ -892,105 +892,84 @@ class Engine:
         return set(self.bitmap_names(st, a)), wild, (set(self.bitmap_names(st, e)) if e is not None else set())
 
     # ---- Explain
-    def explain_ids(self, items: np.ndarray, cancel=None, timeout_s=None):
-        """acl_explain_bulk_ids: Check + a witness per granted item -> (perm u8[n], err i32[n], flags u8[n], hop_off u32[n + 1], hops HOP_DTYPE[]);
-        item i's witness is hops[hop_off[i]:hop_off[i + 1]], a chain of stored relationships from its resource to its subject."""
+    @staticmethod
+    def _records(ptr, total, dtype):
+        """A copy of the `total` records of `dtype` behind the engine's block `ptr` (the caller releases the block)."""
+        return np.frombuffer(C.string_at(ptr, total * dtype.itemsize), dtype=dtype).copy() if total else np.zeros(0, dtype=dtype)
+
+    def _explain_ids(self, fn, items, cancel, timeout_s, *record_ptrs):
+        """One acl_explain*_bulk_ids call: `record_ptrs` receive the engine's blocks, one per offsets / records pair of the form, and stay the caller's to
+        release -> (perm u8[n], err i32[n], flags u8[n], offsets u32[n + 1] per pair ...)."""
         items = np.ascontiguousarray(items, dtype=ITEM_DTYPE)
         n = items.size
         perm = np.zeros(max(1, n), dtype=np.uint8)
         err = np.zeros(max(1, n), dtype=np.int32)
         flags = np.zeros(max(1, n), dtype=np.uint8)
-        off = np.zeros(n + 1, dtype=np.uint32)
-        hp = C.POINTER(ExplainHop)()
+        offs = [np.zeros(n + 1, dtype=np.uint32) for _ in record_ptrs]
+        outs = [a for off, ptr in zip(offs, record_ptrs) for a in (off.ctypes.data, C.byref(ptr))]
         o = self._opts(cancel, timeout_s)
-        self._check(self._L.acl_explain_bulk_ids(self._h, items.ctypes.data, n, perm.ctypes.data, err.ctypes.data, flags.ctypes.data, off.ctypes.data, C.byref(hp),
-                                                 C.byref(o) if o else None))
-        try:
-            total = int(off[n])
-            hops = np.frombuffer(C.string_at(hp, total * HOP_DTYPE.itemsize), dtype=HOP_DTYPE).copy() if total else np.zeros(0, dtype=HOP_DTYPE)
-        finally:
-            self._L.acl_free(hp)
-        return perm[:n], err[:n], flags[:n], off, hops
+        self._check(fn(self._h, items.ctypes.data, n, perm.ctypes.data, err.ctypes.data, flags.ctypes.data, *outs, C.byref(o) if o else None))
+        return (perm[:n], err[:n], flags[:n], *offs)
 
-    def explain(self, rt, rid, perm, st, sid, srel=""):
-        """acl_explain: (permissionship, error code, flags, [relationship strings in the tuple grammar of aclgpu/text.py])."""
+    def _explain_one(self, fn, rt, rid, perm, st, sid, srel):
+        """One acl_explain* call about one item in strings -> (permissionship, error code, flags, [the text's lines])."""
         it = CheckItem(*[_b(x if x is not None else "") for x in (rt, rid, perm, st, sid, srel)])
         p, e, f, txt = C.c_uint8(), C.c_int32(), C.c_uint32(), C.c_void_p()
-        self._check(self._L.acl_explain(self._h, C.byref(it), C.byref(p), C.byref(e), C.byref(f), C.byref(txt), None))
+        self._check(fn(self._h, C.byref(it), C.byref(p), C.byref(e), C.byref(f), C.byref(txt), None))
         try:
             lines = C.string_at(txt).decode().splitlines() if txt.value else []
         finally:
             self._L.acl_free(txt)
         return p.value, e.value, f.value, lines
+
+    def explain_ids(self, items: np.ndarray, cancel=None, timeout_s=None):
+        """acl_explain_bulk_ids: Check + a witness per granted item -> (perm u8[n], err i32[n], flags u8[n], hop_off u32[n + 1], hops HOP_DTYPE[]);
+        item i's witness is hops[hop_off[i]:hop_off[i + 1]], a chain of stored relationships from its resource to its subject."""
+        hp = C.POINTER(ExplainHop)()
+        perm, err, flags, off = self._explain_ids(self._L.acl_explain_bulk_ids, items, cancel, timeout_s, hp)
+        try:
+            return perm, err, flags, off, self._records(hp, int(off[-1]), HOP_DTYPE)
+        finally:
+            self._L.acl_free(hp)
+
+    def explain(self, rt, rid, perm, st, sid, srel=""):
+        """acl_explain: (permissionship, error code, flags, [relationship strings in the tuple grammar of aclgpu/text.py])."""
+        return self._explain_one(self._L.acl_explain, rt, rid, perm, st, sid, srel)
 
     def explain_proof_ids(self, items: np.ndarray, cancel=None, timeout_s=None):
         """acl_explain_proof_bulk_ids: Check + a proof per granted item, permissions with `-`, `&` and `.all()` included ->
         (perm u8[n], err i32[n], flags u8[n], hop_off u32[n + 1], hops HOP_DTYPE[], absent_off u32[n + 1], absent ITEM_DTYPE[]); item i rests on the stored
         relationships hops[hop_off[i]:hop_off[i + 1]] and on the Check items absent[absent_off[i]:absent_off[i + 1]], each of which answers NO."""
-        items = np.ascontiguousarray(items, dtype=ITEM_DTYPE)
-        n = items.size
-        perm = np.zeros(max(1, n), dtype=np.uint8)
-        err = np.zeros(max(1, n), dtype=np.int32)
-        flags = np.zeros(max(1, n), dtype=np.uint8)
-        off = np.zeros(n + 1, dtype=np.uint32)
-        aoff = np.zeros(n + 1, dtype=np.uint32)
         hp, ap = C.POINTER(ExplainHop)(), C.c_void_p()
-        o = self._opts(cancel, timeout_s)
-        self._check(self._L.acl_explain_proof_bulk_ids(self._h, items.ctypes.data, n, perm.ctypes.data, err.ctypes.data, flags.ctypes.data, off.ctypes.data, C.byref(hp),
-                                                       aoff.ctypes.data, C.byref(ap), C.byref(o) if o else None))
+        perm, err, flags, off, aoff = self._explain_ids(self._L.acl_explain_proof_bulk_ids, items, cancel, timeout_s, hp, ap)
         try:
-            nh, na = int(off[n]), int(aoff[n])
-            hops = np.frombuffer(C.string_at(hp, nh * HOP_DTYPE.itemsize), dtype=HOP_DTYPE).copy() if nh else np.zeros(0, dtype=HOP_DTYPE)
-            absent = np.frombuffer(C.string_at(ap, na * ITEM_DTYPE.itemsize), dtype=ITEM_DTYPE).copy() if na else np.zeros(0, dtype=ITEM_DTYPE)
+            return perm, err, flags, off, self._records(hp, int(off[-1]), HOP_DTYPE), aoff, self._records(ap, int(aoff[-1]), ITEM_DTYPE)
         finally:
             self._L.acl_free(hp)
             self._L.acl_free(ap)
-        return perm[:n], err[:n], flags[:n], off, hops, aoff, absent
 
     def explain_proof(self, rt, rid, perm, st, sid, srel=""):
         """acl_explain_proof: (permissionship, error code, flags, [lines]): the hops in the tuple grammar of aclgpu/text.py, then `not <goal>` per absence."""
-        it = CheckItem(*[_b(x if x is not None else "") for x in (rt, rid, perm, st, sid, srel)])
-        p, e, f, txt = C.c_uint8(), C.c_int32(), C.c_uint32(), C.c_void_p()
-        self._check(self._L.acl_explain_proof(self._h, C.byref(it), C.byref(p), C.byref(e), C.byref(f), C.byref(txt), None))
-        try:
-            lines = C.string_at(txt).decode().splitlines() if txt.value else []
-        finally:
-            self._L.acl_free(txt)
-        return p.value, e.value, f.value, lines
+        return self._explain_one(self._L.acl_explain_proof, rt, rid, perm, st, sid, srel)
 
     def explain_denial_ids(self, items: np.ndarray, cancel=None, timeout_s=None):
         """acl_explain_denial_bulk_ids: Check + the single writes that would grant each denied item -> (perm u8[n], err i32[n], flags u8[n],
         grant_off u32[n + 1], grants GRANT_DTYPE[]); writing grants[k] for k in grant_off[i]:grant_off[i + 1] with item i's subject grants item i."""
-        items = np.ascontiguousarray(items, dtype=ITEM_DTYPE)
-        n = items.size
-        perm = np.zeros(max(1, n), dtype=np.uint8)
-        err = np.zeros(max(1, n), dtype=np.int32)
-        flags = np.zeros(max(1, n), dtype=np.uint8)
-        off = np.zeros(n + 1, dtype=np.uint32)
         gp = C.POINTER(Grant)()
-        o = self._opts(cancel, timeout_s)
-        self._check(self._L.acl_explain_denial_bulk_ids(self._h, items.ctypes.data, n, perm.ctypes.data, err.ctypes.data, flags.ctypes.data, off.ctypes.data,
-                                                        C.byref(gp), C.byref(o) if o else None))
-        total = int(off[n])
+        perm, err, flags, off = self._explain_ids(self._L.acl_explain_denial_bulk_ids, items, cancel, timeout_s, gp)
+        total = int(off[-1])
         if not total:
             self._L.acl_free(gp)
-            return perm[:n], err[:n], flags[:n], off, np.zeros(0, dtype=GRANT_DTYPE)
+            return perm, err, flags, off, np.zeros(0, dtype=GRANT_DTYPE)
         # No copy: the array reads the engine's allocation, which is released (acl_free) when the last array over it goes away -- 4 096 items about one
         # resource return 4 096 lists, tens of megabytes.
         buf = (C.c_char * (total * GRANT_DTYPE.itemsize)).from_address(C.addressof(gp.contents))
         weakref.finalize(buf, self._L.acl_free, C.c_void_p(C.addressof(gp.contents)))
-        return perm[:n], err[:n], flags[:n], off, np.frombuffer(buf, dtype=GRANT_DTYPE)
+        return perm, err, flags, off, np.frombuffer(buf, dtype=GRANT_DTYPE)
 
     def explain_denial(self, rt, rid, perm, st, sid, srel=""):
         """acl_explain_denial: (permissionship, error code, flags, [relationships to write, in the tuple grammar of aclgpu/text.py])."""
-        it = CheckItem(*[_b(x if x is not None else "") for x in (rt, rid, perm, st, sid, srel)])
-        p, e, f, txt = C.c_uint8(), C.c_int32(), C.c_uint32(), C.c_void_p()
-        self._check(self._L.acl_explain_denial(self._h, C.byref(it), C.byref(p), C.byref(e), C.byref(f), C.byref(txt), None))
-        try:
-            lines = C.string_at(txt).decode().splitlines() if txt.value else []
-        finally:
-            self._L.acl_free(txt)
-        return p.value, e.value, f.value, lines
+        return self._explain_one(self._L.acl_explain_denial, rt, rid, perm, st, sid, srel)
 
     def selfcheck_denial_grants(self, rtype: str, member: str, stype: str, srel: str, states) -> np.ndarray:
         """Test hook (any engine): the host half of Explain denial on states [(object id, slot | level << 16)] -> GRANT_DTYPE records."""
@@ -999,7 +978,7 @@ class Engine:
         self._check(self._L.acl_selfcheck_denial_grants(self._h, self.type_id(rtype), self.relation_id(rtype, member), self.type_id(stype), self.relation_id(stype, srel),
                                                         st.ctypes.data, st.shape[0], C.byref(gp), C.byref(n)))
         try:
-            return np.frombuffer(C.string_at(gp, n.value * GRANT_DTYPE.itemsize), dtype=GRANT_DTYPE).copy() if n.value else np.zeros(0, dtype=GRANT_DTYPE)
+            return self._records(gp, n.value, GRANT_DTYPE)
         finally:
             self._L.acl_free(gp)
 

@@ -394,11 +394,7 @@ int acl_check_bulk_ids(acl_engine_t *h, const acl_item_t *items, size_t n, uint8
 
 int acl_check_bulk_ids_opts(acl_engine_t *h, const acl_item_t *items, size_t n, uint8_t *perm_out, int32_t *err_out, const acl_call_opts_t *o) {
     if (n && (!items || !perm_out)) return fail(ACL_ERR_INVALID_ARGUMENT, "acl_check_bulk_ids: NULL buffer");
-    CallOpts opts;
-    if (o) {
-        opts.cancel = o->cancel;
-        if (o->timeout_ns > 0) opts.deadline_ns = mono_ns() + o->timeout_ns;
-    }
+    const CallOpts opts = call_opts(o);
     if (!n) return h->store_only ? fail(ACL_ERR_UNAVAILABLE, "engine was opened store-only (no GPU): Check / LookupResources are unavailable") : ACL_OK;
     Eval ev;
     int rc = ev.begin(h, false, opts);
@@ -467,29 +463,25 @@ int acl_lookup_resources_alloc(acl_engine_t *h, const char *rtype, const char *p
     if (!bitmap_out || !words_out) return fail(ACL_ERR_INVALID_ARGUMENT, "acl_lookup_resources_alloc: NULL output");
     *bitmap_out = nullptr;
     *words_out = 0;
-    CallOpts opts;
-    if (o) {
-        opts.cancel = o->cancel;
-        if (o->timeout_ns > 0) opts.deadline_ns = mono_ns() + o->timeout_ns;
-    }
+    const CallOpts opts = call_opts(o);
     int rt, pm, st, sr;
     uint32_t sub;
     int rc = resolve_lookup(h, rtype, perm, stype, sid, srel, &rt, &pm, &st, &sr, &sub);
     if (rc) return rc;
-    for (int attempt = 0; attempt < 8; attempt++) {
-        const size_t words = ((size_t)acl_object_count(h, rt) + 31) / 32 + 64;  // slack: objects interned while the walk runs
-        uint32_t *bm = (uint32_t *)std::malloc(std::max<size_t>(words, 1) * sizeof(uint32_t));
-        if (!bm) return fail(ACL_ERR_RESOURCE_EXHAUSTED, "out of host memory for the result bitmap");
+    return owned_bitmap_retry("lookup: the object table kept growing faster than the result bitmap", [&]() -> int {
+        const size_t words = owned_bitmap_words(h, rt);
+        uint32_t *bm = nullptr;
+        int rc = result_block(words, "out of host memory for the result bitmap", &bm);
+        if (rc) return rc;
         rc = lookup_one_routed(h, rt, pm, st, sr, sub, bm, words, count_out, opts);
         if (rc == ACL_OK) {
             *bitmap_out = bm;
             *words_out = words;
-            return ACL_OK;
+        } else {
+            std::free(bm);
         }
-        std::free(bm);
-        if (rc != ACL_ERR_INVALID_ARGUMENT || g_last_detail != kDetailBitmapTooSmall) return rc;  // (a typed detail, not the message's wording: ADVICE r2)
-    }
-    return fail(ACL_ERR_UNAVAILABLE, "lookup: the object table kept growing faster than the result bitmap");
+        return rc;
+    });
 }
 void acl_free(void *p) { std::free(p); }
 

@@ -393,15 +393,6 @@ unsigned usable_cores() {
     return c;
 }
 
-CallOpts to_opts(const acl_call_opts_t *o) {
-    CallOpts opts;
-    if (o) {
-        opts.cancel = o->cancel;
-        if (o->timeout_ns > 0) opts.deadline_ns = mono_ns() + o->timeout_ns;
-    }
-    return opts;
-}
-
 }  // namespace
 
 namespace aclint {
@@ -538,11 +529,7 @@ int acl_watch_poll(acl_engine_t *h, uint64_t after_revision, const int *types, i
 // or with ACL_ERR_DEADLINE_EXCEEDED / ACL_ERR_CANCELLED by `opts`.  A condition variable on the write path: no sleeping poll per stream.
 int acl_watch_wait(acl_engine_t *h, uint64_t after_revision, const int *types, int ntypes, const acl_call_opts_t *o, uint64_t *revision_out) {
     if (ntypes < 0 || (ntypes && !types)) return fail(ACL_ERR_INVALID_ARGUMENT, "acl_watch_wait: bad argument");
-    CallOpts opts;
-    if (o) {
-        opts.cancel = o->cancel;
-        if (o->timeout_ns > 0) opts.deadline_ns = mono_ns() + o->timeout_ns;
-    }
+    const CallOpts opts = call_opts(o);
     std::vector<int> tv(types, types + ntypes);
     for (;;) {
         uint64_t gen;
@@ -752,7 +739,7 @@ int acl_batcher_lookup_stats(acl_engine_t *h, uint64_t *walks, uint64_t *lookups
 int acl_lookup_one_opts(acl_engine_t *h, const char *rtype, const char *perm, const char *stype, const char *sid, const char *srel, uint32_t *bitmap_out,
                         size_t bitmap_words, uint64_t *count_out, const acl_call_opts_t *o) {
     if (!bitmap_out && bitmap_words) return fail(ACL_ERR_INVALID_ARGUMENT, "acl_lookup_one: NULL bitmap");
-    const CallOpts opts = to_opts(o);
+    const CallOpts opts = call_opts(o);
     int rt, pm, st, sr;
     uint32_t sub;
     int rc = resolve_lookup(h, rtype, perm, stype, sid, srel, &rt, &pm, &st, &sr, &sub);
@@ -775,7 +762,7 @@ int acl_check_one_opts(acl_engine_t *h, const acl_check_item_t *item, uint8_t *p
         *err_out = intern_check_item(h, *item, &it);
         if (*err_out) return ACL_OK;
     }
-    const CallOpts opts = to_opts(o);
+    const CallOpts opts = call_opts(o);
     size_t idx = 0;
     Batch *b = enqueue(h, &it, nullptr, &idx);
     if (!b) return acl_check_bulk_ids_opts(h, &it, 1, perm_out, err_out, o);  // no batcher: a device pass of its own

@@ -70,15 +70,6 @@ static int cursor_live(acl_engine *h, const acl_lookup_cursor *cur) {
     return ACL_OK;
 }
 
-static CallOpts cursor_opts(const acl_call_opts_t *o) {
-    CallOpts opts;
-    if (o) {
-        opts.cancel = o->cancel;
-        if (o->timeout_ns > 0) opts.deadline_ns = mono_ns() + o->timeout_ns;
-    }
-    return opts;
-}
-
 // What an open and a derive share around the making of the rows.  reserve: the cursor's shape, its share of the engine's budget (given back by the guard unless
 // the cursor is published), its stream and its rows.  counts_from_index: the rows' counts are the rank index at the row boundaries (the index is 8 bytes per
 // 16 KiB of rows: it crosses whole, in one copy on the cursor's own stream).  publish: the cursor becomes one of the engine's open cursors.
@@ -157,7 +148,7 @@ static int cursor_open(acl_engine *h, int rtype, int perm, const std::vector<Cur
         for (const CursorRun &r : runs)
             if (r.srel >= 0 && !subjects) key_slots.push_back(h->store.schema().slot(r.stype, r.srel));
     }
-    const CallOpts opts = cursor_opts(o);
+    const CallOpts opts = call_opts(o);
     auto cur = std::make_unique<acl_lookup_cursor>();
     cur->rtype = rtype;
     cur->perm = perm;
@@ -564,7 +555,7 @@ int acl_lookup_cursor_pages(acl_engine_t *h, acl_lookup_cursor_t *cur, const acl
     std::lock_guard<std::mutex> lk(cur->mu);
     rc = page_rows_ok(cur, reqs, m);
     if (rc == ACL_OK) rc = cursor_live(h, cur);
-    if (rc == ACL_OK) rc = check_opts(cursor_opts(o));
+    if (rc == ACL_OK) rc = check_opts(call_opts(o));
     if (rc || !m) return rc;
     return cursor_pages(h, cur, reqs, m, sum, ids_out, n_out, more_out);
 }

@@ -190,11 +190,8 @@ int reach_walk(acl_engine *h, PassCtx *c, const std::vector<uint2> &roots, OnRoo
 // caller holds an Eval with the subject rows current
 int denial_batch(acl_engine *h, PassCtx *c, const acl_item_t *items, size_t n, uint8_t *perm, int32_t *err, uint8_t *flags, uint32_t *grant_off, acl_grant_t **grants_out) {
     const Schema &sc = h->store.schema();
-    const size_t chunk = std::max<size_t>(h->max_sub_batch, 1);
-    for (size_t b = 0; b < n; b += chunk) {
-        int rc = check_ids_host(h, c, items + b, std::min(chunk, n - b), perm + b, err + b);
-        if (rc) return rc;
-    }
+    int rc = check_ids_chunked(h, c, items, n, perm, err);
+    if (rc) return rc;
     // ---- the denied items of monotone slots, grouped: one walk per (resource type, resource id, permission), one grant list per (walk, subject class)
     std::map<std::pair<uint32_t, uint32_t>, uint32_t> root_of;             // {slot, resource id} -> root
     std::vector<uint2> roots;
@@ -202,20 +199,9 @@ int denial_batch(acl_engine *h, PassCtx *c, const acl_item_t *items, size_t n, u
     std::vector<std::pair<int, int>> list_class;                            // [list] (stype, srel)
     std::vector<std::vector<uint32_t>> root_lists;                          // [root] its lists
     std::vector<uint32_t> item_list(n, 0xFFFFFFFFu);
-    for (size_t i = 0; i < n; i++) {
-        flags[i] = 0;
-        const acl_item_t &it = items[i];
-        if (err[i] || perm[i] != ACL_PERM_NO_PERMISSION) continue;
-        // (a denied item without error passed the device's validation; the host reads the same fields, so it checks them again before it indexes with them)
-        if (it.resource_type >= sc.defs.size() || it.subject_type >= sc.defs.size() || it.permission >= sc.defs[it.resource_type].members.size() ||
-            (it.subject_relation != ACL_NO_RELATION && it.subject_relation >= sc.defs[it.subject_type].members.size()))
-            return fail(ACL_ERR_INTERNAL, "Explain denial: Check answers the ill-formed " + explain_item_text(it, i));
-        const uint32_t slot = (uint32_t)sc.slot(it.resource_type, it.permission);
-        if (slot < h->snap.slot_nonmono.size() && h->snap.slot_nonmono[slot]) {
-            flags[i] = ACL_EXPLAIN_UNSUPPORTED;
-            continue;
-        }
-        flags[i] = ACL_EXPLAIN_DENIAL;
+    rc = explain_classify(h, "Explain denial", ACL_PERM_NO_PERMISSION, items, n, perm, err, flags, [&](size_t i, const acl_item_t &it, uint32_t slot, bool nonmono) {
+        flags[i] = nonmono ? ACL_EXPLAIN_UNSUPPORTED : ACL_EXPLAIN_DENIAL;
+        if (nonmono) return;
         auto r = root_of.emplace(std::make_pair(slot, it.resource_id), (uint32_t)roots.size());
         if (r.second) {
             roots.push_back(make_uint2(it.resource_id, slot));
@@ -230,9 +216,10 @@ int denial_batch(acl_engine *h, PassCtx *c, const acl_item_t *items, size_t n, u
             root_lists[root].push_back(l.first->second);
         }
         item_list[i] = l.first->second;
-    }
+    });
+    if (rc) return rc;
     std::vector<std::vector<acl_grant_t>> lists(list_class.size());
-    int rc = reach_walk(h, c, roots, [&](size_t root, const uint2 *recs, size_t cnt) {
+    rc = reach_walk(h, c, roots, [&](size_t root, const uint2 *recs, size_t cnt) {
         for (uint32_t l : root_lists[root]) denial_grants(sc, recs, cnt, list_class[l].first, list_class[l].second, &lists[l]);
     });
     if (rc) return rc;
@@ -243,8 +230,9 @@ int denial_batch(acl_engine *h, PassCtx *c, const acl_item_t *items, size_t n, u
         if (total > 0xFFFFFFFFull) return fail(ACL_ERR_RESOURCE_EXHAUSTED, "Explain denial: more than 2^32 grants in one call: ask about fewer items");
         grant_off[i + 1] = (uint32_t)total;
     }
-    acl_grant_t *out = (acl_grant_t *)std::malloc(std::max<size_t>(total, 1) * sizeof(acl_grant_t));
-    if (!out) return fail(ACL_ERR_RESOURCE_EXHAUSTED, "out of host memory for the grants");
+    acl_grant_t *out = nullptr;
+    rc = result_block(total, "out of host memory for the grants", &out);
+    if (rc) return rc;
     // (every item gets its own copy of its list -- 4 096 items about one resource are 4 096 copies: the pages are touched and filled by several threads)
     host_parallel(h, n, 64, [&](size_t i0, size_t i1) {
         for (size_t i = i0; i < i1; i++) {
@@ -257,112 +245,51 @@ int denial_batch(acl_engine *h, PassCtx *c, const acl_item_t *items, size_t n, u
     return ACL_OK;
 }
 
-int denial_call(acl_engine_t *h, const acl_item_t *items, size_t n, uint8_t *perm_out, int32_t *err_out, uint8_t *flags_out, uint32_t *grant_off_out,
-                acl_grant_t **grants_out, const acl_call_opts_t *o) {
-    if (!grant_off_out || !grants_out || (n && (!items || !perm_out))) return fail(ACL_ERR_INVALID_ARGUMENT, "acl_explain_denial_bulk_ids: NULL buffer");
-    *grants_out = nullptr;
-    grant_off_out[0] = 0;
-    if (n >= 0xFFFFFFFFull) return fail(ACL_ERR_INVALID_ARGUMENT, "acl_explain_denial_bulk_ids: too many items");
-    CallOpts opts;
-    if (o) {
-        opts.cancel = o->cancel;
-        if (o->timeout_ns > 0) opts.deadline_ns = mono_ns() + o->timeout_ns;
-    }
-    if (h->store_only) return fail(ACL_ERR_UNAVAILABLE, "engine was opened store-only (no GPU): Explain is unavailable");
-    {
-        std::shared_lock<RwLock> slk(h->state_mu);
-        if (!h->store.has_schema()) return fail(ACL_ERR_FAILED_PRECONDITION, "no schema loaded");
-        int rc = not_sharded(h);
-        if (rc) return rc;
-    }
-    if (!n) return ACL_OK;
-    std::vector<int32_t> err_local;
-    std::vector<uint8_t> flags_local;
-    if (!err_out) {
-        err_local.assign(n, 0);
-        err_out = err_local.data();
-    }
-    if (!flags_out) {
-        flags_local.assign(n, 0);
-        flags_out = flags_local.data();
-    }
-    Eval ev;
-    int rc = ev.begin(h, false, opts, -1, -1, true);
-    if (rc) return rc;
-    rc = not_sharded(h);
-    if (rc) return rc;
-    return denial_batch(h, ev.c, items, n, perm_out, err_out, flags_out, grant_off_out, grants_out);
-}
-
 }  // namespace
 
 }  // namespace aclint
 
 int acl_explain_denial_bulk_ids(acl_engine_t *h, const acl_item_t *items, size_t n, uint8_t *perm_out, int32_t *err_out, uint8_t *flags_out, uint32_t *grant_off_out,
                                 acl_grant_t **grants_out, const acl_call_opts_t *opts) {
-    return denial_call(h, items, n, perm_out, err_out, flags_out, grant_off_out, grants_out, opts);
+    return explain_front(
+        h, "acl_explain_denial_bulk_ids", items, n, perm_out, err_out, flags_out, opts,
+        [&](PassCtx *c, int32_t *err, uint8_t *flags) { return denial_batch(h, c, items, n, perm_out, err, flags, grant_off_out, grants_out); },
+        ExplainOut<acl_grant_t>{grant_off_out, grants_out});
+}
+
+// The subject of a grant is spelled as the item spelled it, and so is the item's own resource (neither needs a name in the tables: an unknown object is a
+// valid one to write about); every other object of a grant takes part in relationships, so its name stays -- read under the names lock, as a witness's.
+static int denial_grants_text(acl_engine_t *h, const acl_check_item_t &item, const acl_item_t &it, const acl_grant_t *grants, uint32_t k0, uint32_t k1, std::string *text) {
+    std::shared_lock<std::shared_mutex> nlk(h->names_mu);
+    const Schema &sc = h->store.schema();
+    for (uint32_t k = k0; k < k1; k++) {
+        const acl_grant_t &g = grants[k];
+        if (g.rtype >= sc.defs.size() || it.subject_type >= sc.defs.size() || g.relation >= sc.defs[g.rtype].members.size() ||
+            (it.subject_relation != ACL_NO_RELATION && it.subject_relation >= sc.defs[it.subject_type].members.size()))
+            return fail(ACL_ERR_UNAVAILABLE, "acl_explain_denial: the schema changed while the grants were named");
+        const bool own = g.rtype == it.resource_type && g.rid == it.resource_id;
+        const std::string *rn = own ? nullptr : h->store.objects(g.rtype).name(g.rid);
+        if (!own && !rn)
+            return fail(ACL_ERR_UNAVAILABLE, "acl_explain_denial: an object of the grants has no name (loaded by id, or renamed by a write since the walk): use acl_explain_denial_bulk_ids, or ask again");
+        relationship_line(sc, g.rtype, own ? std::string(item.resource_id) : *rn, g.relation, it.subject_type, item.subject_id, it.subject_relation, text);
+    }
+    return ACL_OK;
 }
 
 int acl_explain_denial(acl_engine_t *h, const acl_check_item_t *item, uint8_t *perm_out, int32_t *err_out, uint32_t *flags_out, char **text_out,
                        const acl_call_opts_t *opts) {
-    if (!item || !perm_out || !err_out || !text_out) return fail(ACL_ERR_INVALID_ARGUMENT, "acl_explain_denial: NULL argument");
-    *perm_out = ACL_PERM_UNSPECIFIED;
-    *err_out = 0;
-    *text_out = nullptr;
-    if (flags_out) *flags_out = 0;
-    acl_item_t it{};
-    int32_t code;
-    {
-        std::shared_lock<RwLock> slk(h->state_mu);
-        std::shared_lock<std::shared_mutex> nlk(h->names_mu);
-        if (!h->store.has_schema()) return fail(ACL_ERR_FAILED_PRECONDITION, "no schema loaded");
-        code = intern_check_item(h, *item, &it);
-    }
-    // as acl_explain: a request the API's validation refuses fails as a whole, an unknown type / permission / relation is the item's own error
-    if (code == ACL_ERR_INVALID_ARGUMENT && !h->per_item_validation) return fail(ACL_ERR_INVALID_ARGUMENT, "invalid CheckPermissionRequest: a field is empty or does not match the API's pattern");
-    if (h->store_only) return fail(ACL_ERR_UNAVAILABLE, "engine was opened store-only (no GPU): Explain is unavailable");
-    std::string text;
-    if (code) {
-        *err_out = code;
-    } else {
-        uint8_t fl = 0;
-        uint32_t off[2] = {0, 0};
-        acl_grant_t *grants = nullptr;
-        const int rc = denial_call(h, &it, 1, perm_out, err_out, &fl, off, &grants, opts);
-        if (rc) return rc;
-        if (flags_out) *flags_out = fl;
-        // The subject is spelled as the item spelled it, and so is the item's own resource (neither needs a name in the tables: an unknown object is a valid
-        // one to write about); every other object of a grant takes part in relationships, so its name stays -- read under the names lock, as a witness's.
-        bool unnamed = false, stale = false;
-        {
-            std::shared_lock<std::shared_mutex> nlk(h->names_mu);
-            const Schema &sc = h->store.schema();
-            for (uint32_t k = off[0]; k < off[1] && !unnamed && !stale; k++) {
-                const acl_grant_t &g = grants[k];
-                if (g.rtype >= sc.defs.size() || it.subject_type >= sc.defs.size() || g.relation >= sc.defs[g.rtype].members.size() ||
-                    (it.subject_relation != ACL_NO_RELATION && it.subject_relation >= sc.defs[it.subject_type].members.size())) {
-                    stale = true;
-                    break;
-                }
-                const bool own = g.rtype == it.resource_type && g.rid == it.resource_id;
-                const std::string *rn = own ? nullptr : h->store.objects(g.rtype).name(g.rid);
-                if (!own && !rn) {
-                    unnamed = true;
-                    break;
-                }
-                relationship_line(sc, g.rtype, own ? std::string(item->resource_id) : *rn, g.relation, it.subject_type, item->subject_id, it.subject_relation, &text);
-            }
-        }
-        std::free(grants);
-        if (stale) return fail(ACL_ERR_UNAVAILABLE, "acl_explain_denial: the schema changed while the grants were named");
-        if (unnamed)
-            return fail(ACL_ERR_UNAVAILABLE, "acl_explain_denial: an object of the grants has no name (loaded by id, or renamed by a write since the walk): use acl_explain_denial_bulk_ids, or ask again");
-    }
-    char *out = (char *)std::malloc(text.size() + 1);
-    if (!out) return fail(ACL_ERR_RESOURCE_EXHAUSTED, "out of host memory for the grants");
-    std::memcpy(out, text.c_str(), text.size() + 1);
-    *text_out = out;
-    return ACL_OK;
+    return explain_one_front(h, "acl_explain_denial", "out of host memory for the grants", item, perm_out, err_out, flags_out, text_out,
+                             [&](const acl_item_t &it, uint8_t *flag, std::string *text) {
+                                 uint8_t fl = 0;
+                                 uint32_t off[2] = {0, 0};
+                                 acl_grant_t *grants = nullptr;
+                                 int rc = acl_explain_denial_bulk_ids(h, &it, 1, perm_out, err_out, &fl, off, &grants, opts);
+                                 if (rc) return rc;
+                                 *flag = fl;
+                                 rc = denial_grants_text(h, *item, it, grants, off[0], off[1], text);
+                                 std::free(grants);
+                                 return rc;
+                             });
 }
 
 // Test hook: the host half alone (denial_grants) on a caller-supplied list of states.  Reads nothing but the schema: any engine will do.
@@ -384,10 +311,7 @@ int acl_selfcheck_denial_grants(acl_engine_t *h, int rtype, int member, int styp
     }
     std::vector<acl_grant_t> grants;
     denial_grants(sc, recs.data(), n, stype, srel < 0 ? kNoRelation : srel, &grants);
-    acl_grant_t *out = (acl_grant_t *)std::malloc(std::max<size_t>(grants.size(), 1) * sizeof(acl_grant_t));
-    if (!out) return fail(ACL_ERR_RESOURCE_EXHAUSTED, "out of host memory for the grants");
-    if (!grants.empty()) std::memcpy(out, grants.data(), grants.size() * sizeof(acl_grant_t));
-    *grants_out = out;
-    *n_out = grants.size();
-    return ACL_OK;
+    const int rc = result_copy(grants.data(), grants.size(), "out of host memory for the grants", grants_out);
+    if (!rc) *n_out = grants.size();
+    return rc;
 }

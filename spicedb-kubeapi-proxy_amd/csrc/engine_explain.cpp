@@ -91,62 +91,39 @@ int explain_walk(acl_engine *h, PassCtx *c, const acl_item_t *items, const std::
         });
 }
 
-namespace {
+// ---- the call front the three forms share (engine_internal.hpp)
+static int explain_unavailable() { return fail(ACL_ERR_UNAVAILABLE, "engine was opened store-only (no GPU): Explain is unavailable"); }
 
-// caller holds an Eval with the subject rows current
-int explain_batch(acl_engine *h, PassCtx *c, const acl_item_t *items, size_t n, uint8_t *perm, int32_t *err, uint8_t *flags, uint32_t *hop_off,
-                  acl_explain_hop_t **hops_out) {
-    const Schema &sc = h->store.schema();
+int check_ids_chunked(acl_engine *h, PassCtx *c, const acl_item_t *items, size_t n, uint8_t *perm, int32_t *err) {
     const size_t chunk = std::max<size_t>(h->max_sub_batch, 1);
     for (size_t b = 0; b < n; b += chunk) {
         int rc = check_ids_host(h, c, items + b, std::min(chunk, n - b), perm + b, err + b);
         if (rc) return rc;
     }
-    std::vector<uint32_t> pick;
-    for (size_t i = 0; i < n; i++) {
-        flags[i] = 0;
-        const acl_item_t &it = items[i];
-        if (err[i] || perm[i] != ACL_PERM_HAS_PERMISSION) continue;
-        // (a granted item passed the device's validation; the host reads the same fields, so it checks them again before it indexes with them)
-        if (it.resource_type >= sc.defs.size() || it.subject_type >= sc.defs.size() || it.permission >= sc.defs[it.resource_type].members.size() ||
-            (it.subject_relation != ACL_NO_RELATION && it.subject_relation >= sc.defs[it.subject_type].members.size()))
-            return fail(ACL_ERR_INTERNAL, "Explain: Check grants the ill-formed " + explain_item_text(it, i));
-        const size_t slot = (size_t)sc.slot(it.resource_type, it.permission);
-        if (slot < h->snap.slot_nonmono.size() && h->snap.slot_nonmono[slot]) {
-            flags[i] = ACL_EXPLAIN_UNSUPPORTED;
-            continue;
-        }
-        pick.push_back((uint32_t)i);
-    }
-    std::vector<acl_explain_hop_t> hops;
-    std::vector<uint32_t> count;
-    int rc = explain_walk(h, c, items, pick, &hops, &count);
-    if (rc) return rc;
-    std::fill(hop_off, hop_off + n + 1, 0u);
-    for (size_t k = 0; k < pick.size(); k++) {
-        flags[pick[k]] = ACL_EXPLAIN_WITNESS;
-        hop_off[pick[k] + 1] = count[k];
-    }
-    for (size_t i = 0; i < n; i++) hop_off[i + 1] += hop_off[i];
-    acl_explain_hop_t *out = (acl_explain_hop_t *)std::malloc(std::max<size_t>(hops.size(), 1) * sizeof(acl_explain_hop_t));
-    if (!out) return fail(ACL_ERR_RESOURCE_EXHAUSTED, "out of host memory for the witness");
-    if (!hops.empty()) std::memcpy(out, hops.data(), hops.size() * sizeof(acl_explain_hop_t));
-    *hops_out = out;
     return ACL_OK;
 }
 
-int explain_call(acl_engine_t *h, const acl_item_t *items, size_t n, uint8_t *perm_out, int32_t *err_out, uint8_t *flags_out, uint32_t *hop_off_out,
-                 acl_explain_hop_t **hops_out, const acl_call_opts_t *o) {
-    if (!hop_off_out || !hops_out || (n && (!items || !perm_out))) return fail(ACL_ERR_INVALID_ARGUMENT, "acl_explain_bulk_ids: NULL buffer");
-    *hops_out = nullptr;
-    hop_off_out[0] = 0;
-    if (n >= 0xFFFFFFFFull) return fail(ACL_ERR_INVALID_ARGUMENT, "acl_explain_bulk_ids: too many items");
-    CallOpts opts;
-    if (o) {
-        opts.cancel = o->cancel;
-        if (o->timeout_ns > 0) opts.deadline_ns = mono_ns() + o->timeout_ns;
+int explain_classify(acl_engine *h, const char *form, uint8_t want, const acl_item_t *items, size_t n, const uint8_t *perm, const int32_t *err, uint8_t *flags,
+                     const std::function<void(size_t, const acl_item_t &, uint32_t, bool)> &on_item) {
+    const Schema &sc = h->store.schema();
+    for (size_t i = 0; i < n; i++) {
+        flags[i] = 0;
+        const acl_item_t &it = items[i];
+        if (err[i] || perm[i] != want) continue;
+        // (an item answered without error passed the device's validation; the host reads the same fields, so it checks them again before it indexes with them)
+        if (it.resource_type >= sc.defs.size() || it.subject_type >= sc.defs.size() || it.permission >= sc.defs[it.resource_type].members.size() ||
+            (it.subject_relation != ACL_NO_RELATION && it.subject_relation >= sc.defs[it.subject_type].members.size()))
+            return fail(ACL_ERR_INTERNAL, std::string(form) + (want == ACL_PERM_HAS_PERMISSION ? ": Check grants" : ": Check answers") + " the ill-formed " + explain_item_text(it, i));
+        const uint32_t slot = (uint32_t)sc.slot(it.resource_type, it.permission);
+        on_item(i, it, slot, slot < h->snap.slot_nonmono.size() && h->snap.slot_nonmono[slot]);
     }
-    if (h->store_only) return fail(ACL_ERR_UNAVAILABLE, "engine was opened store-only (no GPU): Explain is unavailable");
+    return ACL_OK;
+}
+
+int explain_front_run(acl_engine_t *h, const std::string &fn, size_t n, int32_t *err_out, uint8_t *flags_out, const acl_call_opts_t *o, const ExplainBatch &batch) {
+    if (n >= 0xFFFFFFFFull) return fail(ACL_ERR_INVALID_ARGUMENT, fn + ": too many items");
+    const CallOpts opts = call_opts(o);
+    if (h->store_only) return explain_unavailable();
     {
         std::shared_lock<RwLock> slk(h->state_mu);
         if (!h->store.has_schema()) return fail(ACL_ERR_FAILED_PRECONDITION, "no schema loaded");
@@ -167,9 +144,65 @@ int explain_call(acl_engine_t *h, const acl_item_t *items, size_t n, uint8_t *pe
     Eval ev;
     int rc = ev.begin(h, false, opts, -1, -1, true);
     if (rc) return rc;
-    rc = not_sharded(h);
+    rc = not_sharded(h);  // (again, now that the evaluation holds the lock: the first test let go of it)
     if (rc) return rc;
-    return explain_batch(h, ev.c, items, n, perm_out, err_out, flags_out, hop_off_out, hops_out);
+    return batch(ev.c, err_out, flags_out);
+}
+
+int explain_one_front(acl_engine_t *h, const char *fn, const char *out_of_memory, const acl_check_item_t *item, uint8_t *perm_out, int32_t *err_out, uint32_t *flags_out,
+                      char **text_out, const std::function<int(const acl_item_t &, uint8_t *, std::string *)> &answer) {
+    if (!item || !perm_out || !err_out || !text_out) return fail(ACL_ERR_INVALID_ARGUMENT, std::string(fn) + ": NULL argument");
+    *perm_out = ACL_PERM_UNSPECIFIED;
+    *err_out = 0;
+    *text_out = nullptr;
+    if (flags_out) *flags_out = 0;
+    acl_item_t it{};
+    int32_t code;
+    {
+        std::shared_lock<RwLock> slk(h->state_mu);
+        std::shared_lock<std::shared_mutex> nlk(h->names_mu);
+        if (!h->store.has_schema()) return fail(ACL_ERR_FAILED_PRECONDITION, "no schema loaded");
+        code = intern_check_item(h, *item, &it);
+    }
+    // as acl_check_bulk: a request the API's validation refuses fails as a whole, an unknown type / permission / relation is the item's own error
+    if (code == ACL_ERR_INVALID_ARGUMENT && !h->per_item_validation) return fail(ACL_ERR_INVALID_ARGUMENT, "invalid CheckPermissionRequest: a field is empty or does not match the API's pattern");
+    if (h->store_only) return explain_unavailable();
+    std::string text;
+    if (code) {
+        *err_out = code;
+    } else {
+        uint8_t fl = 0;
+        const int rc = answer(it, &fl, &text);
+        if (flags_out) *flags_out = fl;
+        if (rc) return rc;
+    }
+    return result_copy(text.c_str(), text.size() + 1, out_of_memory, text_out);
+}
+
+namespace {
+
+// caller holds an Eval with the subject rows current
+int explain_batch(acl_engine *h, PassCtx *c, const acl_item_t *items, size_t n, uint8_t *perm, int32_t *err, uint8_t *flags, uint32_t *hop_off,
+                  acl_explain_hop_t **hops_out) {
+    int rc = check_ids_chunked(h, c, items, n, perm, err);
+    if (rc) return rc;
+    std::vector<uint32_t> pick;
+    rc = explain_classify(h, "Explain", ACL_PERM_HAS_PERMISSION, items, n, perm, err, flags, [&](size_t i, const acl_item_t &, uint32_t, bool nonmono) {
+        if (nonmono) flags[i] = ACL_EXPLAIN_UNSUPPORTED;
+        else pick.push_back((uint32_t)i);
+    });
+    if (rc) return rc;
+    std::vector<acl_explain_hop_t> hops;
+    std::vector<uint32_t> count;
+    rc = explain_walk(h, c, items, pick, &hops, &count);
+    if (rc) return rc;
+    std::fill(hop_off, hop_off + n + 1, 0u);
+    for (size_t k = 0; k < pick.size(); k++) {
+        flags[pick[k]] = ACL_EXPLAIN_WITNESS;
+        hop_off[pick[k] + 1] = count[k];
+    }
+    for (size_t i = 0; i < n; i++) hop_off[i + 1] += hop_off[i];
+    return result_copy(hops.data(), hops.size(), "out of host memory for the witness", hops_out);
 }
 
 }  // namespace
@@ -203,45 +236,25 @@ int explain_hops_text(acl_engine *h, const char *fn, const acl_explain_hop_t *ho
 
 int acl_explain_bulk_ids(acl_engine_t *h, const acl_item_t *items, size_t n, uint8_t *perm_out, int32_t *err_out, uint8_t *flags_out, uint32_t *hop_off_out,
                          acl_explain_hop_t **hops_out, const acl_call_opts_t *opts) {
-    return explain_call(h, items, n, perm_out, err_out, flags_out, hop_off_out, hops_out, opts);
+    return explain_front(
+        h, "acl_explain_bulk_ids", items, n, perm_out, err_out, flags_out, opts,
+        [&](PassCtx *c, int32_t *err, uint8_t *flags) { return explain_batch(h, c, items, n, perm_out, err, flags, hop_off_out, hops_out); },
+        ExplainOut<acl_explain_hop_t>{hop_off_out, hops_out});
 }
 
 int acl_explain(acl_engine_t *h, const acl_check_item_t *item, uint8_t *perm_out, int32_t *err_out, uint32_t *flags_out, char **text_out, const acl_call_opts_t *opts) {
-    if (!item || !perm_out || !err_out || !text_out) return fail(ACL_ERR_INVALID_ARGUMENT, "acl_explain: NULL argument");
-    *perm_out = ACL_PERM_UNSPECIFIED;
-    *err_out = 0;
-    *text_out = nullptr;
-    if (flags_out) *flags_out = 0;
-    acl_item_t it{};
-    int32_t code;
-    {
-        std::shared_lock<RwLock> slk(h->state_mu);
-        std::shared_lock<std::shared_mutex> nlk(h->names_mu);
-        if (!h->store.has_schema()) return fail(ACL_ERR_FAILED_PRECONDITION, "no schema loaded");
-        code = intern_check_item(h, *item, &it);
-    }
-    // as acl_check_bulk: a request the API's validation refuses fails as a whole, an unknown type / permission / relation is the item's own error
-    if (code == ACL_ERR_INVALID_ARGUMENT && !h->per_item_validation) return fail(ACL_ERR_INVALID_ARGUMENT, "invalid CheckPermissionRequest: a field is empty or does not match the API's pattern");
-    if (h->store_only) return fail(ACL_ERR_UNAVAILABLE, "engine was opened store-only (no GPU): Explain is unavailable");
-    std::string text;
-    if (code) {
-        *err_out = code;
-    } else {
-        uint8_t fl = 0;
-        uint32_t off[2] = {0, 0};
-        acl_explain_hop_t *hops = nullptr;
-        const int rc = explain_call(h, &it, 1, perm_out, err_out, &fl, off, &hops, opts);
-        if (rc) return rc;
-        if (flags_out) *flags_out = fl;
-        const int trc = explain_hops_text(h, "acl_explain", hops, off[0], off[1], &text);
-        std::free(hops);
-        if (trc) return trc;
-    }
-    char *out = (char *)std::malloc(text.size() + 1);
-    if (!out) return fail(ACL_ERR_RESOURCE_EXHAUSTED, "out of host memory for the witness");
-    std::memcpy(out, text.c_str(), text.size() + 1);
-    *text_out = out;
-    return ACL_OK;
+    return explain_one_front(h, "acl_explain", "out of host memory for the witness", item, perm_out, err_out, flags_out, text_out,
+                             [&](const acl_item_t &it, uint8_t *flag, std::string *text) {
+                                 uint8_t fl = 0;
+                                 uint32_t off[2] = {0, 0};
+                                 acl_explain_hop_t *hops = nullptr;
+                                 int rc = acl_explain_bulk_ids(h, &it, 1, perm_out, err_out, &fl, off, &hops, opts);
+                                 if (rc) return rc;
+                                 *flag = fl;
+                                 rc = explain_hops_text(h, "acl_explain", hops, off[0], off[1], text);
+                                 std::free(hops);
+                                 return rc;
+                             });
 }
 
 // Test hook: the per-op side table of the current programs (plan.hpp ExplainOp), one acl_explain_op_t per FwdOp.  Store-only engines only: it brings the

@@ -321,11 +321,7 @@ void intern_items(acl_engine_t *h, const Items &its, size_t n, acl_item_t *out, 
 template <class Items>
 int check_bulk_strings(acl_engine_t *h, const Items &its, size_t n, uint8_t *perm_out, int32_t *err_out, const acl_call_opts_t *o) {
     if (!n) return h->store_only ? fail(ACL_ERR_UNAVAILABLE, "engine was opened store-only (no GPU): Check / LookupResources are unavailable") : ACL_OK;
-    CallOpts opts;  // (cancellation / deadline: honoured while the call waits for an evaluation context, as in acl_check_bulk_ids_opts)
-    if (o) {
-        opts.cancel = o->cancel;
-        if (o->timeout_ns > 0) opts.deadline_ns = mono_ns() + o->timeout_ns;
-    }
+    const CallOpts opts = call_opts(o);  // (cancellation / deadline: honoured while the call waits for an evaluation context, as in acl_check_bulk_ids_opts)
     // A request whose pairs all name ONE plain subject, one type and one permission -- what filterItemsWithBulkPermissions sends for a list
     // (postfilter.go:67-134) -- is answered by one reverse walk + bit tests when the permission allows it (keep_by_reverse_walk, pair form); anything else
     // comes back here before a byte was written.

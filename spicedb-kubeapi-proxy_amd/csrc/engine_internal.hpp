@@ -217,6 +217,15 @@ struct CallOpts {
 int64_t mono_ns();
 // ACL_OK, ACL_ERR_CANCELLED or ACL_ERR_DEADLINE_EXCEEDED
 int check_opts(const CallOpts &o);
+// the ABI's per-call options as the library carries them: a timeout counts from the moment the entry point is entered
+inline CallOpts call_opts(const acl_call_opts_t *o) {
+    CallOpts opts;
+    if (o) {
+        opts.cancel = o->cancel;
+        if (o->timeout_ns > 0) opts.deadline_ns = mono_ns() + o->timeout_ns;
+    }
+    return opts;
+}
 
 // Device state of ONE in-flight evaluation.
 struct PassCtx {
@@ -627,6 +636,47 @@ int check_ids_host(acl_engine *h, PassCtx *c, const acl_item_t *items, size_t n,
 int explain_walk(acl_engine *h, PassCtx *c, const acl_item_t *items, const std::vector<uint32_t> &pick, std::vector<acl_explain_hop_t> *hops, std::vector<uint32_t> *count);
 std::string explain_item_text(const acl_item_t &it, size_t i);
 int explain_hops_text(acl_engine *h, const char *fn, const acl_explain_hop_t *hops, uint32_t k0, uint32_t k1, std::string *text);
+// A result the caller releases with acl_free: a block of at least one T, for n of them (result_block: the caller fills it), or a copy of src[0, n)
+template <typename T>
+int result_block(size_t n, const char *out_of_memory, T **out) {
+    *out = (T *)std::malloc(std::max<size_t>(n, 1) * sizeof(T));
+    return *out ? (int)ACL_OK : fail(ACL_ERR_RESOURCE_EXHAUSTED, out_of_memory);
+}
+template <typename T>
+int result_copy(const T *src, size_t n, const char *out_of_memory, T **out) {
+    const int rc = result_block(n, out_of_memory, out);
+    if (!rc && n) std::memcpy(*out, src, n * sizeof(T));
+    return rc;
+}
+// The call front of the three forms of Explain (engine_explain.cpp; engine_proof.cpp and engine_denial.cpp are its other callers).
+// check_ids_chunked: Check of items[0, n) through c, max_sub_batch items at a time (LookupSubjects confirms its candidates through it too).
+int check_ids_chunked(acl_engine *h, PassCtx *c, const acl_item_t *items, size_t n, uint8_t *perm, int32_t *err);
+// explain_classify: after the Check, flags[i] = 0 for every item and on_item(i, item, slot, nonmono) for those answered `want` without error, in order;
+// `form` ("Explain", "Explain proof", ...) opens the message of an answered item the schema cannot index.
+int explain_classify(acl_engine *h, const char *form, uint8_t want, const acl_item_t *items, size_t n, const uint8_t *perm, const int32_t *err, uint8_t *flags,
+                     const std::function<void(size_t, const acl_item_t &, uint32_t, bool)> &on_item);
+// explain_front: acl_explain*_bulk_ids `fn` around its batch.  Refuses, in this order: a NULL buffer (the outputs are reset behind that test), 2^32 items,
+// a store-only engine, no schema, a sharded engine; n == 0 is answered here; batch(c, err, flags) runs under an Eval with the subject rows current, err and
+// flags never NULL (the caller's, or the front's own where the caller passed none).
+template <typename T>
+struct ExplainOut {  // one offsets / records pair of a form's answer
+    uint32_t *off;
+    T **recs;
+};
+using ExplainBatch = std::function<int(PassCtx *, int32_t *, uint8_t *)>;
+int explain_front_run(acl_engine_t *h, const std::string &fn, size_t n, int32_t *err_out, uint8_t *flags_out, const acl_call_opts_t *o, const ExplainBatch &batch);
+template <typename... T>
+int explain_front(acl_engine_t *h, const char *fn, const acl_item_t *items, size_t n, uint8_t *perm_out, int32_t *err_out, uint8_t *flags_out, const acl_call_opts_t *o,
+                  const ExplainBatch &batch, ExplainOut<T>... outs) {
+    if ((... || (!outs.off || !outs.recs)) || (n && (!items || !perm_out))) return fail(ACL_ERR_INVALID_ARGUMENT, std::string(fn) + ": NULL buffer");
+    ((*outs.recs = nullptr, outs.off[0] = 0), ...);
+    return explain_front_run(h, fn, n, err_out, flags_out, o, batch);
+}
+// explain_one_front: the one-item text form `fn` (acl_explain, acl_explain_proof, acl_explain_denial) around answer(interned item, flag, text), which runs
+// the form's bulk call on the one item, sets *flag once that call has succeeded and appends the rendering to *text.  The front interns the item, refuses
+// what the API's validation refuses before the store-only engine, and hands the text over.
+int explain_one_front(acl_engine_t *h, const char *fn, const char *out_of_memory, const acl_check_item_t *item, uint8_t *perm_out, int32_t *err_out, uint32_t *flags_out,
+                      char **text_out, const std::function<int(const acl_item_t &, uint8_t *, std::string *)> &answer);
 // one relationship in the tuple grammar of aclgpu/text.py + a newline, appended to *text (srel: ACL_NO_RELATION = none; the indices are the caller's to check)
 void relationship_line(const Schema &sc, uint16_t rtype, const std::string &rid, uint16_t relation, uint16_t stype, const std::string &sid, uint16_t srel, std::string *text);
 // Explain denial (engine_denial.cpp): the host half, a pure function of the schema -- the grants that the states recs[0, n) = {object id, slot | level << 16}
@@ -687,6 +737,18 @@ void batcher_create(acl_engine_t *h);
 void batcher_destroy(acl_engine_t *h);  // after acl_batcher_stop
 int lookup_opts_call(acl_engine_t *h, const char *rtype, const char *perm, const char *stype, const char *sid, const char *srel, uint32_t *bitmap_out,
                      size_t bitmap_words, uint64_t *count_out, const CallOpts &opts);
+// A result bitmap the ENGINE sizes: a row over the type's ids as they are now plus slack for objects interned while the walk runs.  try_once() sizes
+// (owned_bitmap_words), allocates, calls and frees what it does not hand over; a call that found its rows too small all the same (kDetailBitmapTooSmall:
+// a typed detail, not the message's wording) is tried again, 8 times in all, and then fails with `kept_growing`.
+inline size_t owned_bitmap_words(acl_engine_t *h, int type) { return ((size_t)acl_object_count(h, type) + 31) / 32 + 64; }
+template <typename TryOnce>
+int owned_bitmap_retry(const char *kept_growing, TryOnce try_once) {
+    for (int attempt = 0; attempt < 8; attempt++) {
+        const int rc = try_once();
+        if (rc != ACL_ERR_INVALID_ARGUMENT || g_last_detail != kDetailBitmapTooSmall) return rc;
+    }
+    return fail(ACL_ERR_UNAVAILABLE, kept_growing);
+}
 
 // Runs iterations 1.. of a level loop until the frontier is empty.  `launch(iter)` enqueues
 // one expansion.  Returns ACL_OK, or ACL_ERR_RESOURCE_EXHAUSTED when the frontier overflowed.

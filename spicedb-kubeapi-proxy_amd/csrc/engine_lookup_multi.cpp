@@ -220,34 +220,29 @@ int access_review_call(acl_engine_t *h, const char *stype, const char *sid, cons
     if (!rows) return fail(ACL_ERR_RESOURCE_EXHAUSTED, "out of host memory for the review's rows");
     std::vector<size_t> words(T);
     std::vector<uint64_t> counts(T);
-    for (int attempt = 0; attempt < 8; attempt++) {
+    rc = owned_bitmap_retry("access review: the object tables kept growing faster than the result bitmaps", [&]() -> int {
         size_t stride = 0;
         for (size_t j = 0; j < T; j++) {
-            words[j] = ((size_t)acl_object_count(h, tg[j].rtype) + 31) / 32 + 64;  // slack: objects interned while the walk runs
+            words[j] = owned_bitmap_words(h, tg[j].rtype);
             rows[j] = acl_review_row_t{tg[j].rtype, tg[j].permission, 0, stride, words[j]};
             stride += words[j];
         }
-        uint32_t *bm = (uint32_t *)std::malloc(std::max<size_t>(stride, 1) * sizeof(uint32_t));
-        if (!bm) {
-            std::free(rows);
-            return fail(ACL_ERR_RESOURCE_EXHAUSTED, "out of host memory for the result bitmaps");
-        }
-        rc = lookup_multi_call(h, tg.data(), T, st, sr, &sub, 1, bm, words.data(), counts.data(), opts);
-        if (rc == ACL_OK) {
+        uint32_t *bm = nullptr;
+        int brc = result_block(stride, "out of host memory for the result bitmaps", &bm);
+        if (brc) return brc;
+        brc = lookup_multi_call(h, tg.data(), T, st, sr, &sub, 1, bm, words.data(), counts.data(), opts);
+        if (brc == ACL_OK) {
             for (size_t j = 0; j < T; j++) rows[j].count = counts[j];
             *rows_out = rows;
             *n_rows_out = T;
             *bitmaps_out = bm;
-            return ACL_OK;
+        } else {
+            std::free(bm);
         }
-        std::free(bm);
-        if (rc != ACL_ERR_INVALID_ARGUMENT || g_last_detail != kDetailBitmapTooSmall) {
-            std::free(rows);
-            return rc;
-        }
-    }
-    std::free(rows);
-    return fail(ACL_ERR_UNAVAILABLE, "access review: the object tables kept growing faster than the result bitmaps");
+        return brc;
+    });
+    if (rc) std::free(rows);
+    return rc;
 }
 
 }  // namespace aclint
@@ -272,21 +267,13 @@ int64_t acl_schema_name_copy(acl_engine_t *h, int type, int member, char *buf, s
 
 int acl_lookup_resources_multi(acl_engine_t *h, const acl_target_t *targets, size_t n_targets, int stype, int srel, const uint32_t *subject_ids, size_t n, uint32_t *bitmaps_out,
                                const size_t *row_words, uint64_t *counts_out, const acl_call_opts_t *o) {
-    CallOpts opts;
-    if (o) {
-        opts.cancel = o->cancel;
-        if (o->timeout_ns > 0) opts.deadline_ns = mono_ns() + o->timeout_ns;
-    }
+    const CallOpts opts = call_opts(o);
     return lookup_multi_call(h, targets, n_targets, stype, srel, subject_ids, n, bitmaps_out, row_words, counts_out, opts);
 }
 
 int acl_access_review(acl_engine_t *h, const char *subject_type, const char *subject_id, const char *subject_relation, const acl_target_t *targets, size_t n_targets,
                       const acl_call_opts_t *o, acl_review_row_t **rows_out, size_t *n_rows_out, uint32_t **bitmaps_out) {
-    CallOpts opts;
-    if (o) {
-        opts.cancel = o->cancel;
-        if (o->timeout_ns > 0) opts.deadline_ns = mono_ns() + o->timeout_ns;
-    }
+    const CallOpts opts = call_opts(o);
     return access_review_call(h, subject_type, subject_id, subject_relation, targets, n_targets, opts, rows_out, n_rows_out, bitmaps_out);
 }
 }

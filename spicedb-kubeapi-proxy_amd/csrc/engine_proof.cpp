@@ -589,11 +589,8 @@ int proof_pass(acl_engine *h, PassCtx *c, std::vector<std::unique_ptr<Prover>> &
 int proof_batch(acl_engine *h, PassCtx *c, const acl_item_t *items, size_t n, uint8_t *perm, int32_t *err, uint8_t *flags, uint32_t *hop_off, acl_explain_hop_t **hops_out,
                 uint32_t *absent_off, acl_item_t **absent_out) {
     const Schema &sc = h->store.schema();
-    const size_t chunk = std::max<size_t>(h->max_sub_batch, 1);
-    for (size_t b = 0; b < n; b += chunk) {
-        int rc = check_ids_host(h, c, items + b, std::min(chunk, n - b), perm + b, err + b);
-        if (rc) return rc;
-    }
+    int rc = check_ids_chunked(h, c, items, n, perm, err);
+    if (rc) return rc;
     std::vector<uint32_t> mono;
     std::vector<Pending> pend;
     std::vector<std::unique_ptr<Prover>> provers;
@@ -616,21 +613,14 @@ int proof_batch(acl_engine *h, PassCtx *c, const acl_item_t *items, size_t n, ui
     if (h->snap.valid_hi > h->snap.valid_lo) now = std::min(std::max(now, h->snap.valid_lo), h->snap.valid_hi - 1);
     uint32_t &region = c->proof_region;  // (kept across calls: a graph whose rows outgrew the first region once does not pay the redo again)
     if (region < kProofRegionFirst) region = kProofRegionFirst;
-    for (size_t i = 0; i < n; i++) {
-        flags[i] = 0;
-        const acl_item_t &it = items[i];
-        if (err[i] || perm[i] != ACL_PERM_HAS_PERMISSION) continue;
-        // (a granted item passed the device's validation; the host reads the same fields, so it checks them again before it indexes with them)
-        if (it.resource_type >= sc.defs.size() || it.subject_type >= sc.defs.size() || it.permission >= sc.defs[it.resource_type].members.size() ||
-            (it.subject_relation != ACL_NO_RELATION && it.subject_relation >= sc.defs[it.subject_type].members.size()))
-            return fail(ACL_ERR_INTERNAL, "Explain proof: Check grants the ill-formed " + explain_item_text(it, i));
-        const size_t slot = (size_t)sc.slot(it.resource_type, it.permission);
-        if (slot < h->snap.slot_nonmono.size() && h->snap.slot_nonmono[slot]) provers.emplace_back(new Prover(h, now, (uint32_t)provers.size(), i, it, &rowrefs));
+    rc = explain_classify(h, "Explain proof", ACL_PERM_HAS_PERMISSION, items, n, perm, err, flags, [&](size_t i, const acl_item_t &it, uint32_t, bool nonmono) {
+        if (nonmono) provers.emplace_back(new Prover(h, now, (uint32_t)provers.size(), i, it, &rowrefs));
         else mono.push_back((uint32_t)i);
-    }
+    });
+    if (rc) return rc;
     std::vector<acl_explain_hop_t> mhops;
     std::vector<uint32_t> mcount;
-    int rc = explain_walk(h, c, items, mono, &mhops, &mcount);
+    rc = explain_walk(h, c, items, mono, &mhops, &mcount);
     if (rc) return rc;
     // rounds: every unfinished search runs against what is known, then one device pass (or a few, by size) answers what they asked
     std::vector<uint32_t> active(provers.size());
@@ -708,12 +698,13 @@ int proof_batch(acl_engine *h, PassCtx *c, const acl_item_t *items, size_t n, ui
     }
     if (nh >= 0xFFFFFFFFull || na >= 0xFFFFFFFFull) return fail(ACL_ERR_RESOURCE_EXHAUSTED, "Explain proof: more than 2^32 records in one call");
     for (size_t i = 0; i < n; i++) hop_off[i + 1] += hop_off[i], absent_off[i + 1] += absent_off[i];
-    acl_explain_hop_t *out = (acl_explain_hop_t *)std::malloc(std::max<size_t>(nh, 1) * sizeof(acl_explain_hop_t));
-    acl_item_t *aout = (acl_item_t *)std::malloc(std::max<size_t>(na, 1) * sizeof(acl_item_t));
-    if (!out || !aout) {
-        std::free(out);
-        std::free(aout);
-        return fail(ACL_ERR_RESOURCE_EXHAUSTED, "out of host memory for the proofs");
+    acl_explain_hop_t *out = nullptr;
+    acl_item_t *aout = nullptr;
+    rc = result_block(nh, "out of host memory for the proofs", &out);
+    if (!rc) rc = result_block(na, "out of host memory for the proofs", &aout);
+    if (rc) {
+        std::free(out);  // (the hops' block is the only one that can be held here)
+        return rc;
     }
     size_t mh = 0;
     for (size_t k = 0; k < mono.size(); k++) {  // (explain_walk appends in pick order)
@@ -734,101 +725,38 @@ int proof_batch(acl_engine *h, PassCtx *c, const acl_item_t *items, size_t n, ui
     return ACL_OK;
 }
 
-int proof_call(acl_engine_t *h, const acl_item_t *items, size_t n, uint8_t *perm_out, int32_t *err_out, uint8_t *flags_out, uint32_t *hop_off_out,
-               acl_explain_hop_t **hops_out, uint32_t *absent_off_out, acl_item_t **absent_out, const acl_call_opts_t *o) {
-    if (!hop_off_out || !hops_out || !absent_off_out || !absent_out || (n && (!items || !perm_out)))
-        return fail(ACL_ERR_INVALID_ARGUMENT, "acl_explain_proof_bulk_ids: NULL buffer");
-    *hops_out = nullptr;
-    *absent_out = nullptr;
-    hop_off_out[0] = 0;
-    absent_off_out[0] = 0;
-    if (n >= 0xFFFFFFFFull) return fail(ACL_ERR_INVALID_ARGUMENT, "acl_explain_proof_bulk_ids: too many items");
-    CallOpts opts;
-    if (o) {
-        opts.cancel = o->cancel;
-        if (o->timeout_ns > 0) opts.deadline_ns = mono_ns() + o->timeout_ns;
-    }
-    if (h->store_only) return fail(ACL_ERR_UNAVAILABLE, "engine was opened store-only (no GPU): Explain is unavailable");
-    {
-        std::shared_lock<RwLock> slk(h->state_mu);
-        if (!h->store.has_schema()) return fail(ACL_ERR_FAILED_PRECONDITION, "no schema loaded");
-        int rc = not_sharded(h);
-        if (rc) return rc;
-    }
-    if (!n) return ACL_OK;
-    std::vector<int32_t> err_local;
-    std::vector<uint8_t> flags_local;
-    if (!err_out) {
-        err_local.assign(n, 0);
-        err_out = err_local.data();
-    }
-    if (!flags_out) {
-        flags_local.assign(n, 0);
-        flags_out = flags_local.data();
-    }
-    Eval ev;
-    int rc = ev.begin(h, false, opts, -1, -1, true);
-    if (rc) return rc;
-    rc = not_sharded(h);
-    if (rc) return rc;
-    return proof_batch(h, ev.c, items, n, perm_out, err_out, flags_out, hop_off_out, hops_out, absent_off_out, absent_out);
-}
-
 }  // namespace
 
 }  // namespace aclint
 
 int acl_explain_proof_bulk_ids(acl_engine_t *h, const acl_item_t *items, size_t n, uint8_t *perm_out, int32_t *err_out, uint8_t *flags_out, uint32_t *hop_off_out,
                                acl_explain_hop_t **hops_out, uint32_t *absent_off_out, acl_item_t **absent_out, const acl_call_opts_t *opts) {
-    return proof_call(h, items, n, perm_out, err_out, flags_out, hop_off_out, hops_out, absent_off_out, absent_out, opts);
+    return explain_front(
+        h, "acl_explain_proof_bulk_ids", items, n, perm_out, err_out, flags_out, opts,
+        [&](PassCtx *c, int32_t *err, uint8_t *flags) { return proof_batch(h, c, items, n, perm_out, err, flags, hop_off_out, hops_out, absent_off_out, absent_out); },
+        ExplainOut<acl_explain_hop_t>{hop_off_out, hops_out}, ExplainOut<acl_item_t>{absent_off_out, absent_out});
 }
 
 int acl_explain_proof(acl_engine_t *h, const acl_check_item_t *item, uint8_t *perm_out, int32_t *err_out, uint32_t *flags_out, char **text_out, const acl_call_opts_t *opts) {
-    if (!item || !perm_out || !err_out || !text_out) return fail(ACL_ERR_INVALID_ARGUMENT, "acl_explain_proof: NULL argument");
-    *perm_out = ACL_PERM_UNSPECIFIED;
-    *err_out = 0;
-    *text_out = nullptr;
-    if (flags_out) *flags_out = 0;
-    acl_item_t it{};
-    int32_t code;
-    {
-        std::shared_lock<RwLock> slk(h->state_mu);
-        std::shared_lock<std::shared_mutex> nlk(h->names_mu);
-        if (!h->store.has_schema()) return fail(ACL_ERR_FAILED_PRECONDITION, "no schema loaded");
-        code = intern_check_item(h, *item, &it);
-    }
-    // as acl_explain: a request the API's validation refuses fails as a whole, an unknown type / permission / relation is the item's own error
-    if (code == ACL_ERR_INVALID_ARGUMENT && !h->per_item_validation) return fail(ACL_ERR_INVALID_ARGUMENT, "invalid CheckPermissionRequest: a field is empty or does not match the API's pattern");
-    if (h->store_only) return fail(ACL_ERR_UNAVAILABLE, "engine was opened store-only (no GPU): Explain is unavailable");
-    std::string text;
-    if (code) {
-        *err_out = code;
-    } else {
-        uint8_t fl = 0;
-        uint32_t off[2] = {0, 0}, aoff[2] = {0, 0};
-        acl_explain_hop_t *hops = nullptr;
-        acl_item_t *absent = nullptr;
-        int rc = proof_call(h, &it, 1, perm_out, err_out, &fl, off, &hops, aoff, &absent, opts);
-        if (rc) return rc;
-        if (flags_out) *flags_out = fl;
-        rc = explain_hops_text(h, "acl_explain_proof", hops, off[0], off[1], &text);
-        if (!rc) {  // an absence names its goal as a hop names a relationship: the object, the relation or permission, the item's subject
-            std::vector<acl_explain_hop_t> goals;
-            for (uint32_t k = aoff[0]; k < aoff[1]; k++)
-                goals.push_back(acl_explain_hop_t{absent[k].resource_type, absent[k].permission, absent[k].resource_id, absent[k].subject_type, absent[k].subject_relation,
-                                                  absent[k].subject_id, 0u});
-            for (uint32_t k = 0; k < goals.size() && !rc; k++) {
-                text += "not ";
-                rc = explain_hops_text(h, "acl_explain_proof", goals.data(), k, k + 1, &text);
+    return explain_one_front(
+        h, "acl_explain_proof", "out of host memory for the proof", item, perm_out, err_out, flags_out, text_out, [&](const acl_item_t &it, uint8_t *flag, std::string *text) {
+            uint8_t fl = 0;
+            uint32_t off[2] = {0, 0}, aoff[2] = {0, 0};
+            acl_explain_hop_t *hops = nullptr;
+            acl_item_t *absent = nullptr;
+            int rc = acl_explain_proof_bulk_ids(h, &it, 1, perm_out, err_out, &fl, off, &hops, aoff, &absent, opts);
+            if (rc) return rc;
+            *flag = fl;
+            rc = explain_hops_text(h, "acl_explain_proof", hops, off[0], off[1], text);
+            // an absence names its goal as a hop names a relationship: the object, the relation or permission, the item's subject
+            for (uint32_t k = aoff[0]; k < aoff[1] && !rc; k++) {
+                const acl_explain_hop_t goal{absent[k].resource_type, absent[k].permission, absent[k].resource_id, absent[k].subject_type, absent[k].subject_relation,
+                                             absent[k].subject_id, 0u};
+                *text += "not ";
+                rc = explain_hops_text(h, "acl_explain_proof", &goal, 0, 1, text);
             }
-        }
-        std::free(hops);
-        std::free(absent);
-        if (rc) return rc;
-    }
-    char *out = (char *)std::malloc(text.size() + 1);
-    if (!out) return fail(ACL_ERR_RESOURCE_EXHAUSTED, "out of host memory for the proof");
-    std::memcpy(out, text.c_str(), text.size() + 1);
-    *text_out = out;
-    return ACL_OK;
+            std::free(hops);
+            std::free(absent);
+            return rc;
+        });
 }

@@ -84,12 +84,7 @@ int subjects_walk(acl_engine *h, PassCtx *c, uint32_t target, uint32_t key, cons
 int check_items(acl_engine *h, PassCtx *c, std::vector<acl_item_t> &items, std::vector<uint8_t> *perm, std::vector<int32_t> *err) {
     perm->assign(items.size(), 0);
     err->assign(items.size(), 0);
-    const size_t chunk = std::max<size_t>(h->max_sub_batch, 1);
-    for (size_t b = 0; b < items.size(); b += chunk) {
-        int rc = check_ids_host(h, c, items.data() + b, std::min(chunk, items.size() - b), perm->data() + b, err->data() + b);
-        if (rc) return rc;
-    }
-    return ACL_OK;
+    return check_ids_chunked(h, c, items.data(), items.size(), perm->data(), err->data());
 }
 
 }  // namespace
@@ -194,15 +189,6 @@ int subjects_args_ok(acl_engine *h, int rt, int pm, int st, int srel) {
         srel >= (int)sc.defs[st].members.size())
         return fail(ACL_ERR_FAILED_PRECONDITION, "lookup_subjects: unknown type, permission or subject relation");
     return ACL_OK;
-}
-
-CallOpts call_opts(const acl_call_opts_t *o) {
-    CallOpts opts;
-    if (o) {
-        opts.cancel = o->cancel;
-        if (o->timeout_ns > 0) opts.deadline_ns = mono_ns() + o->timeout_ns;
-    }
-    return opts;
 }
 
 int subjects_batch_call(acl_engine_t *h, int rt, int pm, int st, int srel, const uint32_t *rids, size_t n, uint32_t *bitmaps, size_t words, uint64_t *counts,
@@ -328,8 +314,8 @@ int acl_lookup_subjects(acl_engine_t *h, const char *rtype, const char *rid, con
         if (known) h->store.touch(rt, res);
     }
     const bool want_ex = excluded_out != nullptr;
-    for (int attempt = 0; attempt < 8; attempt++) {
-        const size_t words = ((size_t)acl_object_count(h, st) + 31) / 32 + 64;  // slack: objects interned while the walk runs
+    return owned_bitmap_retry("lookup_subjects: the object table kept growing faster than the result bitmap", [&]() -> int {
+        const size_t words = owned_bitmap_words(h, st);
         uint32_t *bm = (uint32_t *)std::calloc(std::max<size_t>(words, 1), sizeof(uint32_t));
         uint32_t *ex = want_ex ? (uint32_t *)std::calloc(std::max<size_t>(words, 1), sizeof(uint32_t)) : nullptr;
         if (!bm || (want_ex && !ex)) {
@@ -354,7 +340,6 @@ int acl_lookup_subjects(acl_engine_t *h, const char *rtype, const char *rid, con
         }
         std::free(bm);
         std::free(ex);
-        if (rc != ACL_ERR_INVALID_ARGUMENT || g_last_detail != kDetailBitmapTooSmall) return rc;
-    }
-    return fail(ACL_ERR_UNAVAILABLE, "lookup_subjects: the object table kept growing faster than the result bitmap");
+        return rc;
+    });
 }

@@ -440,11 +440,7 @@ int acl_watch_set_poll(acl_engine_t *h, acl_watch_set_t *s, const acl_call_opts_
     if (!changes_out || !n_out) return fail(ACL_ERR_INVALID_ARGUMENT, "acl_watch_set_poll: NULL output");
     *changes_out = nullptr;
     *n_out = 0;
-    CallOpts opts;
-    if (o) {
-        opts.cancel = o->cancel;
-        if (o->timeout_ns > 0) opts.deadline_ns = mono_ns() + o->timeout_ns;
-    }
+    const CallOpts opts = call_opts(o);
     return set_poll(h, s, opts, changes_out, n_out, revision_out);
 }
 

@@ -502,6 +502,37 @@ int acl_explain_denial_bulk_ids(acl_engine_t *h, const acl_item_t *items, size_t
 int acl_explain_denial(acl_engine_t *h, const acl_check_item_t *item, uint8_t *perm_out, int32_t *err_out, uint32_t *flags_out, char **text_out,
                        const acl_call_opts_t *opts);
 
+/* ---- Explain for revocation: the single deletes that would revoke a Check ----
+ * perm_out / err_out per item are exactly what acl_check_bulk_ids answers for the same items on the same snapshot (one evaluation holds the Check and
+ * all walks; nothing is written and the snapshot does not change).  An item that answers HAS_PERMISSION on a permission built from `+`, `->` and
+ * references alone gets ACL_EXPLAIN_REVOKE and the cuts [cut_off_out[i], cut_off_out[i + 1]) of *cuts_out, possibly none: ALL stored relationships whose
+ * delete, alone, takes the grant away.
+ *   - a cut is a stored relationship, live at the call's revision and `now`, in the record Explain returns its hops in; a `T:*` relationship carries
+ *     ACL_HOP_WILDCARD, with sid the wildcard's id;
+ *   - sound: delete any one of them, nothing else changed, and the item's Check no longer answers HAS_PERMISSION -- it answers NO_PERMISSION or a
+ *     per-item error.  That includes the case where the only chain left is longer than the 50 dispatches of a Check;
+ *   - complete: deleting any other single relationship leaves the answer at HAS_PERMISSION.  An empty list says "no single delete revokes it": the grant
+ *     is redundant (two disjoint chains, a direct grant beside a group's).  A smallest SET of deletes is not looked for;
+ *   - an item granted by zero hops (`group:g#member @ group:g#member`) has no cuts;
+ *   - masking is by relationship, not by the place that reads it: under `view = viewer + edit`, `edit = viewer` a lone `pod:p#viewer@user:a` is read on
+ *     several routes, is ONE relationship, and IS a cut.  A relationship is listed once;
+ *   - order: the cuts of an item come in the order of the witness the call found (acl_explain_bulk_ids' order: the resource's end first).  The SET is
+ *     determined by the snapshot; which witness was found is not, but every witness holds every cut.
+ * Every other item gets no cuts: a granted item on a permission that holds `-`, `&` or `.all()` anywhere beneath gets ACL_EXPLAIN_UNSUPPORTED (revoking
+ * there may mean WRITING a ban); a denied item gets flag 0 (acl_explain_denial's business), and so does an item with a per-item error.  Items may mix
+ * resource types, permissions and subject classes.
+ * The answer is never truncated: a walk that outgrows 2^24 states, or a row beyond the enumeration limit (as in LookupSubjects), fails the call with
+ * ACL_ERR_RESOURCE_EXHAUSTED.  Validation, refusals and their order are acl_explain_bulk_ids': sharded engines answer ACL_ERR_FAILED_PRECONDITION,
+ * store-only engines ACL_ERR_UNAVAILABLE; n == 0 succeeds.  err_out and flags_out may be NULL.  *cuts_out is the engine's (one allocation, release with
+ * acl_free; NULL when the call fails or n == 0); cut_off_out holds n + 1 offsets. */
+#define ACL_EXPLAIN_REVOKE 16u /* per item: cuts [cut_off[i], cut_off[i+1]) are ALL single relationships whose delete revokes it */
+int acl_explain_revoke_bulk_ids(acl_engine_t *h, const acl_item_t *items, size_t n, uint8_t *perm_out, int32_t *err_out, uint8_t *flags_out,
+                                uint32_t *cut_off_out, acl_explain_hop_t **cuts_out, const acl_call_opts_t *opts);
+/* string form, one item: *text_out = one relationship to delete per line, in the tuple grammar and in the order above (the engine's: acl_free; an empty
+ * string when there are none).  Names, validation and refusals are acl_explain's. */
+int acl_explain_revoke(acl_engine_t *h, const acl_check_item_t *item, uint8_t *perm_out, int32_t *err_out, uint32_t *flags_out, char **text_out,
+                       const acl_call_opts_t *opts);
+
 /* ---- the callers either side of the kernels ----
  * PostFilter: filterItemsWithBulkPermissions (postfilter.go:58-182).  The K list items' resolved pairs are ONE bulk
  * check; pairs [item_off[i], item_off[i+1]) belong to list item i (itemToRequestMap, postfilter.go:65,117-119);

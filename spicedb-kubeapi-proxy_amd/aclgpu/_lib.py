@@ -35,6 +35,7 @@ SYMBOLS = [
     "acl_explain_bulk_ids", "acl_explain", "acl_selfcheck_explain_ops",
     "acl_explain_proof_bulk_ids", "acl_explain_proof",
     "acl_explain_denial_bulk_ids", "acl_explain_denial", "acl_selfcheck_denial_grants",
+    "acl_explain_revoke_bulk_ids", "acl_explain_revoke",
     "acl_lookup_resources_multi", "acl_access_review", "acl_schema_name_copy",
     "acl_lookup_cursor_open", "acl_lookup_cursor_open_subjects", "acl_lookup_cursor_info", "acl_lookup_cursor_pages", "acl_lookup_cursor_page_names",
     "acl_lookup_cursor_close", "acl_lookup_cursor_stats",
@@ -294,6 +295,8 @@ def load():
     L.acl_explain_proof.argtypes = [H, C.POINTER(CheckItem), C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_void_p), C.POINTER(CallOpts)]
     L.acl_explain_denial_bulk_ids.argtypes = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.POINTER(Grant)), C.POINTER(CallOpts)]
     L.acl_explain_denial.argtypes = [H, C.POINTER(CheckItem), C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_void_p), C.POINTER(CallOpts)]
+    L.acl_explain_revoke_bulk_ids.argtypes = [H, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.POINTER(ExplainHop)), C.POINTER(CallOpts)]
+    L.acl_explain_revoke.argtypes = [H, C.POINTER(CheckItem), C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_void_p), C.POINTER(CallOpts)]
     L.acl_selfcheck_denial_grants.argtypes = [H, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.POINTER(Grant)), C.POINTER(C.c_size_t)]
     L.acl_watch_set_open.argtypes = [H, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     L.acl_watch_set_open_subjects.argtypes = [H, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]

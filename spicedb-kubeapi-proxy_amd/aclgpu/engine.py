@@ -41,6 +41,7 @@ assert EXPLAIN_OP_DTYPE.itemsize == C.sizeof(ExplainOpRec) == 20
 GRANT_DTYPE = np.dtype([("rtype", "<u2"), ("relation", "<u2"), ("rid", "<u4"), ("level", "<u4")])  # acl_grant_t
 assert GRANT_DTYPE.itemsize == C.sizeof(Grant) == 12
 EXPLAIN_DENIAL = 8                              # ACL_EXPLAIN_DENIAL: the item's grants are ALL single relationships whose write grants it
+EXPLAIN_REVOKE = 16                             # ACL_EXPLAIN_REVOKE: the item's cuts are ALL single relationships whose delete revokes it
 HOP_WILDCARD = 1                                # ACL_HOP_WILDCARD
 EXPLAIN_WITNESS, EXPLAIN_UNSUPPORTED = 1, 2     # per-item flags of Explain
 HOP_SEGMENT = 2                                 # ACL_HOP_SEGMENT: the hop starts a new chain of a proof
@@ -970,6 +971,21 @@ class Engine:
     def explain_denial(self, rt, rid, perm, st, sid, srel=""):
         """acl_explain_denial: (permissionship, error code, flags, [relationships to write, in the tuple grammar of aclgpu/text.py])."""
         return self._explain_one(self._L.acl_explain_denial, rt, rid, perm, st, sid, srel)
+
+    def explain_revoke_ids(self, items: np.ndarray, cancel=None, timeout_s=None):
+        """acl_explain_revoke_bulk_ids: Check + the single deletes that would revoke each granted item -> (perm u8[n], err i32[n], flags u8[n],
+        cut_off u32[n + 1], cuts HOP_DTYPE[]); deleting cuts[k] for any one k in cut_off[i]:cut_off[i + 1] takes item i's grant away, no other single
+        delete does."""
+        cp = C.POINTER(ExplainHop)()
+        perm, err, flags, off = self._explain_ids(self._L.acl_explain_revoke_bulk_ids, items, cancel, timeout_s, cp)
+        try:
+            return perm, err, flags, off, self._records(cp, int(off[-1]), HOP_DTYPE)
+        finally:
+            self._L.acl_free(cp)
+
+    def explain_revoke(self, rt, rid, perm, st, sid, srel=""):
+        """acl_explain_revoke: (permissionship, error code, flags, [relationships to delete, in the tuple grammar of aclgpu/text.py])."""
+        return self._explain_one(self._L.acl_explain_revoke, rt, rid, perm, st, sid, srel)
 
     def selfcheck_denial_grants(self, rtype: str, member: str, stype: str, srel: str, states) -> np.ndarray:
         """Test hook (any engine): the host half of Explain denial on states [(object id, slot | level << 16)] -> GRANT_DTYPE records."""

@@ -3040,7 +3040,9 @@ void launch_rev_import(hipStream_t s, const DevReverse &r, const DevFrontier &f,
 
 // ---- the forward walk of LookupSubjects and Explain (plan.hpp SubjectRows).  A walk starts at one resource's state and follows the FORWARD programs: the
 // positive relaxation of the Check they encode -- ops inside the subtracted operand of an exclusion are skipped (SubjOp kSubjSkip), both sides of `&` and the
-// tupleset of `.all()` are walked.  Four kernels share it:
+// tupleset of `.all()` are walked.  Five kernels share it:
+//   k_revoke_local   one block per (item, stored relationship) of an Explain-for-revocation call, Explain's walk with RevokePolicy -- the same tests with that
+//                    one relationship left out of every row that holds it; one word comes back: is the subject still found
 //   k_subj_local     one block per lookup, every level in one launch: subj_block_walk with SubjectsPolicy -- reached rows of the subject class are EMITTED
 //   k_explain_local  one block per item, the same walk with ExplainPolicy -- reached rows are TESTED for the item's one subject, every state remembers its parent
 //   k_subj_expand    one launch per level over the chunked frontier (the sharded graph): its own loop, the same decode
@@ -3063,6 +3065,7 @@ constexpr uint32_t kSubjMaxRow = 1u << 21;        // ids of one row a task may e
 constexpr uint32_t kSubjMarked = 0x80000000u;     // log entry: its visit was decided when it was appended
 constexpr uint32_t kSubjDead = 0x40000000u;       // log entry: a second visit, or moved behind the current level: not expanded here
 constexpr uint32_t kSubjEmitEdges = 1u << 30, kSubjEmitIds = 2u << 30, kSubjChild = 3u << 30;  // task kinds (tag bits 30-31)
+constexpr uint32_t kSubjTagMasked = 1u << 22;  // task tag (bits 22-29 are free): the row is the one that holds the relationship left out (RevokePolicy)
 namespace {
 // ORs bit `id` into the result row; lanes holding the same 32-bit word (ascending ids of one row) fold their bits first and one lane issues the atomic.
 // Call in wave-uniform control flow.
@@ -3125,22 +3128,39 @@ struct SubjStep {  // what one (state, op) pair asks of the walk
 struct SubjEmit {
     static constexpr bool kTest = false, kReach = false;
     __device__ __forceinline__ bool is(uint32_t) const { return true; }
-    __device__ __forceinline__ bool hashed_has(const FwdOp &, uint32_t) const { return false; }
-    __device__ __forceinline__ bool sorted_has(const uint2 &) const { return false; }
+    __device__ __forceinline__ bool hashed_has(const FwdOp &, uint32_t, uint32_t) const { return false; }
+    __device__ __forceinline__ bool sorted_has(const uint2 &, uint32_t, uint32_t) const { return false; }
 };
 struct SubjReach {
     static constexpr bool kTest = false, kReach = true;
     __device__ __forceinline__ bool is(uint32_t) const { return false; }
-    __device__ __forceinline__ bool hashed_has(const FwdOp &, uint32_t) const { return false; }
-    __device__ __forceinline__ bool sorted_has(const uint2 &) const { return false; }
+    __device__ __forceinline__ bool hashed_has(const FwdOp &, uint32_t, uint32_t) const { return false; }
+    __device__ __forceinline__ bool sorted_has(const uint2 &, uint32_t, uint32_t) const { return false; }
 };
 struct SubjTest {
     static constexpr bool kTest = true, kReach = false;
     const DevGraph *dg;  // what subject_row_contains reads: the forward row descriptors and the hashed buckets
     uint32_t sid;
     __device__ __forceinline__ bool is(uint32_t id) const { return id == sid; }
-    __device__ __forceinline__ bool hashed_has(const FwdOp &op, uint32_t id) const { return subject_row_contains(*dg, op, id, sid); }
-    __device__ __forceinline__ bool sorted_has(const uint2 &md) const { return row_contains(dg->edges, md.x, md.y, sid); }
+    __device__ __forceinline__ bool hashed_has(const FwdOp &op, uint32_t, uint32_t id) const { return subject_row_contains(*dg, op, id, sid); }
+    __device__ __forceinline__ bool sorted_has(const uint2 &md, uint32_t, uint32_t) const { return row_contains(dg->edges, md.x, md.y, sid); }
+};
+// Explain for revocation: SubjTest with ONE stored relationship left out (engine_revoke.cpp).  The relationship is {class, resource id, subject id}; `cls`
+// numbers the class of relationships every op reads (one word per FwdOp; a `T:*` class has a number of its own, so an OP_WILD op's class says that the
+// row tested is the wildcard's).  A terminal hit of an op of the mask's class at the mask's resource does not count when the subject it tests is the mask's:
+// the item's own, or -- the class being a wildcard's -- `T:*`, whoever asks.
+struct SubjMask {
+    uint32_t cls, rid, sid, wild;
+};
+struct SubjTestMasked {
+    static constexpr bool kTest = true, kReach = false;
+    SubjTest t;
+    const uint32_t *__restrict__ cls;
+    SubjMask m;
+    __device__ __forceinline__ bool is(uint32_t id) const { return t.is(id); }
+    __device__ __forceinline__ bool masked(uint32_t opi, uint32_t id) const { return gld(cls, opi) == m.cls && id == m.rid && (m.wild != 0u || t.sid == m.sid); }
+    __device__ __forceinline__ bool hashed_has(const FwdOp &op, uint32_t opi, uint32_t id) const { return t.hashed_has(op, opi, id) && !masked(opi, id); }
+    __device__ __forceinline__ bool sorted_has(const uint2 &md, uint32_t opi, uint32_t id) const { return t.sorted_has(md, opi, id) && !masked(opi, id); }
 };
 // Op j of the `nops` ops of program p that count for the state (p's slot, id) at `level`, looking for subjects of `key` (nops: n_total when the subject
 // carries a relation -- REFLEX ops count -- else n_main; 0 for a lane without a state).  Side effects are the caller's: it turns `wild` and `too_long` into
@@ -3166,7 +3186,7 @@ __device__ __forceinline__ SubjStep subj_decode(const SubjTables &T, const SlotP
     } else if (op.flags & OP_PROBE_HASH) {
         if (REACH || op.key != key) return d;
         if (TEST) {
-            if (mode.hashed_has(op, id)) d.flags = SubjStep::kOneEmit;
+            if (mode.hashed_has(op, p.first + j, id)) d.flags = SubjStep::kOneEmit;
             return d;
         }
         const SubjOp so = T.sops[p.first + j];
@@ -3187,7 +3207,7 @@ __device__ __forceinline__ SubjStep subj_decode(const SubjTables &T, const SlotP
         if (md.y > md.x) {
             const bool probe = !REACH && (op.flags & OP_PROBE) && op.key == key;
             const bool enm = (op.flags & OP_ENUM) && L + 1u <= kMaxLevels;
-            if (TEST && probe && mode.sorted_has(md)) d.flags = SubjStep::kOneEmit;
+            if (TEST && probe && mode.sorted_has(md, p.first + j, id)) d.flags = SubjStep::kOneEmit;
             if (md.y - md.x > kSubjMaxRow) {
                 if (enm || (!TEST && probe)) d.flags |= SubjStep::kTooLong;
             } else if (enm) {
@@ -3238,8 +3258,10 @@ struct SubjWalkLds {  // the walk's static LDS, declared alignas(16).  The kerne
 // Returns true when the policy's end-of-level test ended the walk, false when the log ran dry, the depth limit was reached or the walk stopped.
 // The policy P supplies (its hooks run in wave-uniform control flow and contain no barrier):
 //   Entry, entry(id, y, par, opi)   the log entry type; a child's entry from its producer (log index `par` of the parent state, op index `opi`)
-//   Tasks, keep_producer, producer  the task list, and what a row's task remembers of its producer for its children
-//   probe                           the decode's mode (SubjEmit / SubjTest)
+//   Tasks, keep_producer, producer  the task list, and what a row's task remembers of its producer (log index, op index, object id) for its children
+//   left_out(tag, v)                child v of the row whose task carries `tag` is not a child at all (Explain for revocation: the relationship left out,
+//                                   which keep_producer marked in the tag); false for every other policy, where it compiles to nothing
+//   probe                           the decode's mode (SubjEmit / SubjTest / SubjTestMasked / SubjReach)
 //   state(step, id, me, opi, lane)  the one-lane results of a pair: `wild`, and `one_emit` -- the state's own id is a subject / the op finds the subject
 //   element(v, emit, lane)          one id of an emitted row
 //   level_done(stop)                tested behind the last round of a level, before the stop
@@ -3315,7 +3337,7 @@ __device__ __forceinline__ bool subj_block_walk(P &pol, const DevSubjects &g, co
                 w.t.prefix[tid] = before;
                 w.t.start[tid] = d.start;
                 w.t.tag[tid] = d.tag;
-                pol.keep_producer(w.t, tid, me, opi);
+                pol.keep_producer(w.t, tid, me, opi, id);
                 __syncthreads();
                 for (uint32_t wb = 0; wb < total; wb += kSubjThreads) {
                     const uint32_t x = wb + tid;
@@ -3327,7 +3349,7 @@ __device__ __forceinline__ bool subj_block_walk(P &pol, const DevSubjects &g, co
                     const uint32_t v = kind == kSubjEmitIds ? gld(g.sids, pos) : (gld(g.edges, pos) & kIdMask);
                     pol.element(v, valid && kind != kSubjChild, lane);
                     const uint2 from = pol.producer(w.t, jt);
-                    child(v, tg & 0xFFFFu, (tg >> 16) & 63u, level, valid && kind == kSubjChild, from.x, from.y);
+                    child(v, tg & 0xFFFFu, (tg >> 16) & 63u, level, valid && kind == kSubjChild && !pol.left_out(tg, v), from.x, from.y);
                 }
             }
             // (also the barrier behind the task list: every lane is done with it before the next round overwrites it)
@@ -3350,7 +3372,8 @@ struct SubjectsPolicy {  // LookupSubjects: 8-byte entries {id, slot | level << 
     uint32_t *s_wild;
     SubjEmit probe;
     __device__ __forceinline__ Entry entry(uint32_t id, uint32_t y, uint32_t, uint32_t) const { return make_uint2(id, y); }
-    __device__ __forceinline__ void keep_producer(Tasks &, uint32_t, uint32_t, uint32_t) const {}
+    __device__ __forceinline__ void keep_producer(Tasks &, uint32_t, uint32_t, uint32_t, uint32_t) const {}
+    __device__ __forceinline__ bool left_out(uint32_t, uint32_t) const { return false; }
     __device__ __forceinline__ uint2 producer(const Tasks &, uint32_t) const { return make_uint2(0u, 0u); }
     __device__ __forceinline__ void state(const SubjStep &d, uint32_t id, uint32_t, uint32_t, uint32_t lane) const {
         if (d.wild()) *s_wild = 1u;
@@ -3365,7 +3388,8 @@ struct ExplainPolicy {  // Explain: 16-byte entries that also carry {log index o
     SubjTest probe;
     unsigned long long *s_hit;  // min over the hits of (log index << 32 | op index)
     __device__ __forceinline__ Entry entry(uint32_t id, uint32_t y, uint32_t par, uint32_t opi) const { return make_uint4(id, y, par, opi); }
-    __device__ __forceinline__ void keep_producer(Tasks &t, uint32_t tid, uint32_t me, uint32_t opi) const {
+    __device__ __forceinline__ bool left_out(uint32_t, uint32_t) const { return false; }
+    __device__ __forceinline__ void keep_producer(Tasks &t, uint32_t tid, uint32_t me, uint32_t opi, uint32_t) const {
         t.parent[tid] = me;
         t.opi[tid] = opi;
     }
@@ -3379,12 +3403,32 @@ struct ExplainPolicy {  // Explain: 16-byte entries that also carry {log index o
     // overwrite a 2 of the same round.  That only decides whether a witness already found is returned; it is valid either way.)
     __device__ __forceinline__ bool level_done(uint32_t stop) const { return *s_hit != ~0ull && stop != 2u; }
 };
+struct RevokePolicy {  // Explain for revocation: Explain's tests with one relationship left out; 8-byte entries (no path is traced back); the first hit ends the walk
+    using Entry = uint2;
+    using Tasks = SubjTaskLds;
+    SubjTestMasked probe;
+    uint32_t *s_found;
+    __device__ __forceinline__ Entry entry(uint32_t id, uint32_t y, uint32_t, uint32_t) const { return make_uint2(id, y); }
+    // the row of (an op of the mask's class, the mask's resource) is the one row that can hold the relationship: its task says so in its tag
+    __device__ __forceinline__ void keep_producer(Tasks &t, uint32_t tid, uint32_t, uint32_t opi, uint32_t id) const {
+        if (t.tag[tid] != 0u && id == probe.m.rid && gld(probe.cls, opi) == probe.m.cls) t.tag[tid] |= kSubjTagMasked;
+    }
+    __device__ __forceinline__ bool left_out(uint32_t tag, uint32_t v) const { return (tag & kSubjTagMasked) != 0u && v == probe.m.sid; }
+    __device__ __forceinline__ uint2 producer(const Tasks &, uint32_t) const { return make_uint2(0u, 0u); }
+    __device__ __forceinline__ void state(const SubjStep &d, uint32_t, uint32_t, uint32_t, uint32_t) const {
+        if (d.one_emit()) *s_found = 1u;
+    }
+    __device__ __forceinline__ void element(uint32_t, bool, uint32_t) const {}
+    // as ExplainPolicy's: a hit stands whatever the log did at the level that produced it; an enumerated row beyond the limit still fails
+    __device__ __forceinline__ bool level_done(uint32_t stop) const { return *s_found != 0u && stop != 2u; }
+};
 struct ReachPolicy {  // Explain denial: 8-byte entries as LookupSubjects'; nothing is emitted or tested and no level ends the walk -- the log is the result
     using Entry = uint2;
     using Tasks = SubjTaskLds;
     SubjReach probe;
     __device__ __forceinline__ Entry entry(uint32_t id, uint32_t y, uint32_t, uint32_t) const { return make_uint2(id, y); }
-    __device__ __forceinline__ void keep_producer(Tasks &, uint32_t, uint32_t, uint32_t) const {}
+    __device__ __forceinline__ void keep_producer(Tasks &, uint32_t, uint32_t, uint32_t, uint32_t) const {}
+    __device__ __forceinline__ bool left_out(uint32_t, uint32_t) const { return false; }
     __device__ __forceinline__ uint2 producer(const Tasks &, uint32_t) const { return make_uint2(0u, 0u); }
     __device__ __forceinline__ void state(const SubjStep &, uint32_t, uint32_t, uint32_t, uint32_t) const {}
     __device__ __forceinline__ void element(uint32_t, bool, uint32_t) const {}
@@ -3530,6 +3574,60 @@ void launch_explain_local(hipStream_t s, const DevSubjects &g, const uint32_t *b
     const uint32_t prog_lds = prog_bytes <= kSubjLdsProgBytes ? 1u : 0u;
     hipLaunchKernelGGL(k_explain_local, dim3(n), dim3(kSubjThreads), prog_lds ? prog_bytes : 0u, s, g, buckets, items, (uint4 *)logs, cap, visited, prog_lds, traces,
                        counts, status);
+}
+
+// ---- Explain for revocation: k_revoke_local (engine_revoke.cpp).  One block walks ONE (item, relationship left out): k_explain_local's walk from the item's
+// resource, with RevokePolicy -- the terminal tests and the enumerated rows read every stored relationship but the mask's.  Nothing is traced back: the block
+// answers one word, found (the grant survives the delete), not found (the delete revokes it: the walk ran the closure dry within the 50 dispatch levels) or
+// stopped (the log overflowed before a hit, or a row beyond the limit: the host redoes the chunk or fails).  The log discipline and the depth arithmetic
+// are the shared walk's, so the answer is the one a Check gives once the relationship is gone.
+__global__ __launch_bounds__(kSubjThreads) void k_revoke_local(DevSubjects g, const uint32_t *__restrict__ buckets, const uint32_t *__restrict__ op_class,
+                                                               const uint4 *__restrict__ recs, uint2 *logs, uint32_t cap, uint32_t *visited_all, uint32_t prog_lds,
+                                                               uint32_t *__restrict__ found_out, uint32_t *status) {
+    __shared__ alignas(16) SubjWalkLds<SubjTaskLds> w;
+    __shared__ uint32_t s_found;
+    extern __shared__ uint4 s_dyn[];  // [programs | ops | side table] when prog_lds
+    const uint32_t tid = threadIdx.x, lane = lane_id(), wib = tid >> 6;
+    const uint32_t req = blockIdx.x;
+    SubjTables T = subj_tables(g);
+    if (prog_lds) (void)subj_stage_programs(g, s_dyn, T, tid);
+    const uint4 item = recs[2u * req];       // {resource id, target slot, subject key, subject id}
+    const uint4 mask = recs[2u * req + 1u];  // {class, resource id, subject id, 1: the class is a wildcard's}
+    uint32_t *__restrict__ visited = visited_all + (size_t)req * g.visited_words;
+    uint2 *const log = logs + (size_t)req * cap;
+    if (tid == 0) {
+        w.end = 1;
+        w.stop = 0;
+        s_found = 0;
+        log[0] = make_uint2(item.x, item.y | (1u << 16) | kSubjMarked);  // (walked whatever its id, as Explain's root)
+        (void)subj_first_visit<__HIP_MEMORY_SCOPE_WORKGROUP>(g, visited, item.y, item.x);
+    }
+    __syncthreads();
+    DevGraph dg{};  // (what subject_row_contains reads: the forward row descriptors and the hashed buckets)
+    dg.meta = g.meta;
+    dg.edges = g.edges;
+    dg.buckets = buckets;
+    RevokePolicy pol{SubjTestMasked{SubjTest{&dg, item.w}, op_class, SubjMask{mask.x, mask.y, mask.z, mask.w}}, &s_found};
+    const bool found = subj_block_walk(pol, g, T, item.z, log, cap, visited, w, tid, lane, wib);
+    __syncthreads();
+    if (tid != 0) return;
+    if (found) {
+        found_out[req] = kRevokeFound;
+    } else if (w.stop) {
+        *status = w.stop;
+        found_out[req] = kRevokeStopped;
+    } else {
+        found_out[req] = kRevokeNotFound;
+    }
+}
+
+void launch_revoke_local(hipStream_t s, const DevSubjects &g, const uint32_t *buckets, const uint32_t *op_class, const uint4 *recs, uint32_t n, void *logs,
+                         uint32_t cap, uint32_t *visited, uint32_t *found_out, uint32_t *status) {
+    if (!n) return;
+    const size_t prog_bytes = subj_prog_bytes(g);
+    const uint32_t prog_lds = prog_bytes <= kSubjLdsProgBytes ? 1u : 0u;
+    hipLaunchKernelGGL(k_revoke_local, dim3(n), dim3(kSubjThreads), prog_lds ? prog_bytes : 0u, s, g, buckets, op_class, recs, (uint2 *)logs, cap, visited, prog_lds,
+                       found_out, status);
 }
 
 // ---- Explain denial: k_reach_local (engine_denial.cpp).  One block walks ONE distinct (resource, permission) of the call with ReachPolicy: the forward closure

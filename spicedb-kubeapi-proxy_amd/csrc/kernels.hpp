@@ -216,6 +216,14 @@ constexpr uint32_t kExplainFound = 0, kExplainNotFound = 1, kExplainBadTrace = 2
 constexpr uint32_t kExplainRecWild = 1u;
 void launch_explain_local(hipStream_t s, const DevSubjects &g, const uint32_t *buckets, const uint4 *items, uint32_t n, void *logs, uint32_t cap, uint32_t *visited,
                           uint4 *traces, uint32_t *counts, uint32_t *status);
+// single-launch Explain for revocation (kernels.hip k_revoke_local): block b walks item recs[2b] = {resource id, target slot, subject key, subject id} as
+// k_explain_local does, with the stored relationship recs[2b + 1] = {class, resource id, subject id, 1 when the class is a `T:*` class} left out: no terminal
+// test counts it and no enumerated row yields it.  op_class: [g.nops] the class number of the relationships each op reads (any number no mask carries for an
+// op that reads none).  found_out[b] = kRevokeFound (the subject is still found), kRevokeNotFound (the closure ran dry without it) or kRevokeStopped (with
+// *status raised as for launch_explain_local).  logs: [n][cap] 8-byte entries; visited: [n][g.visited_words] zeroed by the caller.
+constexpr uint32_t kRevokeFound = 0, kRevokeNotFound = 1, kRevokeStopped = 2;
+void launch_revoke_local(hipStream_t s, const DevSubjects &g, const uint32_t *buckets, const uint32_t *op_class, const uint4 *recs, uint32_t n, void *logs,
+                         uint32_t cap, uint32_t *visited, uint32_t *found_out, uint32_t *status);
 // single-launch Explain denial (kernels.hip k_reach_local): block b walks the forward programs from roots[b] = {resource id, target slot} by the same walk,
 // following children only, and hands back the distinct states it reached, each at its least dispatch level: out.spans[b] = {first record, count} of
 // out.recs, records {object id, slot | level << 16} in no particular order.  out.total (zeroed by the caller) counts the records of ALL blocks, also of

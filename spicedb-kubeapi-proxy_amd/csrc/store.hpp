@@ -278,14 +278,19 @@ class Store {
     // counts the writes that can ADD a path to the graph: relationships whose subject carries a relation (`group:g#member`) or whose relation is an arrow's
     // tupleset (`pod#namespace`), bulk loads, schema loads.  A relationship with a plain subject on any other relation ends every path it is on, and a removal
     // (DELETE, expiry) only takes paths away: neither can make a Check end at the depth limit that did not before (engine_keep.cpp no_object_is_deep).
+    // A test clock set back (set_now) counts too.
     uint64_t path_adds() const { return path_adds_; }
     void settle_all();
     // A read-only twin for a background snapshot build: same schema, revision and clock, relationship tables SHARED
     // (copy on write), object tables reduced to their id counts, no change feed.  Take it with the store lock held.
     Store view(int64_t at = 0 /* the `now` the view's snapshot will be built for (0 = now()): its expiry window is taken here */);
 
-    // expiration clock (unix seconds).  now_override_ == 0 -> wall clock.
-    void set_now(int64_t t) { now_override_ = t; }
+    // expiration clock (unix seconds).  now_override_ == 0 -> wall clock.  A clock set BACK brings expired, not yet collected relationships back to life with
+    // no write: it counts as a path add (a revived nesting may close a cycle of groups).
+    void set_now(int64_t t) {
+        if (t && t < now()) path_adds_++;
+        now_override_ = t;
+    }
     int64_t now() const;
     bool live(const ClassTable &ct, uint64_t key, int64_t now) const {
         if (ct.expiry.empty()) return true;

@@ -4,25 +4,29 @@ A witness is a list of relationships (rtype, rid, rel, stype, sid, srel) -- a wi
   - at most 50 of them, every one in the test's own relationship set;
   - they chain: the first hop's resource is the item's resource object, each hop's subject object is the next hop's resource object, and the
     last hop names the item's subject (or the subject type's `*`); an item whose subject carries a relation may end at that object's own state;
-  - the hops ALONE, loaded into an empty store under the same schema, make both oracles' Check of the item answer HAS."""
+  - the hops ALONE, loaded into an empty store under the same schema, make both oracles' Check of the item answer HAS -- each hop written with the expiry
+    it has in the store (`expires`: {relationship: expires_at}) and both oracles at the store's clock (`now`), so a hop that has run out grants nothing."""
 from oracle import orc
 from oracle.pyoracle import HAS, PyOracle
 
 MAX_HOPS = 50
 
 
-def replay(schema, item, hops):
-    """(Python oracle's answer, C oracle's (permissionship, error)) for `item` on a store that holds only `hops`"""
+def replay(schema, item, hops, expires=None, now=0):
+    """(Python oracle's answer, C oracle's (permissionship, error)) for `item` on a store that holds only `hops`, at clock `now`"""
     py, c = PyOracle(schema), orc.Oracle(schema)
+    py.now = now
+    c.set_now(now)
+    at = expires or {}
     for h in hops:
-        py.touch(*h[:6])
+        py.touch(*h[:6], expires=at.get(tuple(h[:6]), 0))
     if hops:
-        c.touch(*[tuple(h[:6]) for h in hops])
+        c.write([(orc.OP_TOUCH, tuple(h[:6]), at.get(tuple(h[:6]), 0)) for h in hops])
     return py.check(*item), c.check(*item)
 
 
-def check_witness(schema, relationships, item, hops, replay_it=True):
-    """item: (rt, rid, perm, st, sid, srel); relationships: a set of 6-tuples, or a predicate over one"""
+def check_witness(schema, relationships, item, hops, replay_it=True, expires=None, now=0):
+    """item: (rt, rid, perm, st, sid, srel); relationships: a set of 6-tuples, or a predicate over one; expires, now: see replay()"""
     rt, rid, _perm, st, sid, srel = item
     has = relationships if callable(relationships) else (lambda h: h in relationships)
     assert len(hops) <= MAX_HOPS, len(hops)
@@ -38,6 +42,6 @@ def check_witness(schema, relationships, item, hops, replay_it=True):
         assert hops, "a plain subject is never granted by zero hops"
         assert hops[-1][3:6] in ((st, sid, ""), (st, "*", "")), f"the last hop does not name the subject: {hops}"
     if replay_it:
-        p, c = replay(schema, item, hops)
+        p, c = replay(schema, item, hops, expires, now)
         assert p == HAS, f"Python oracle: {p} for {item} on {hops}"
         assert c == (2, 0), f"C oracle: {c} for {item} on {hops}"

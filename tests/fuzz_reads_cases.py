@@ -14,6 +14,12 @@ CASES = {
     "combine-acyclic": (33, 120, dict(schema="combine", acyclic=True)),
     "combine-acyclic-recycle-compactions": (34, 100, dict(schema="combine", acyclic=True, recycle=True, compact_early=True)),
     "combine-cyclic-depth": (35, 60, dict(schema="combine", depth_case=True, read_share=0.9)),
+    # the schemas' expiring variants under a moving clock (fuzz_gpu.Clock); on the cyclic C4 graphs a smaller probe batch, and in the first fewer steps, for
+    # the oracle's time.  The recycle / compactions case keeps its twin's 140 steps: nestings that run out drop the two-hop rows, the garbage they leave makes
+    # the engine rebuild or adopt a background build every few steps, and at 80 steps only 19 or 20 of its snapshot changes were patches in place.
+    "c4-expiring": (62, 80, dict(expiring=True, probe=100)),
+    "c4-expiring-recycle-compactions": (77, 140, dict(expiring=True, recycle=True, compact_early=True, probe=100)),
+    "combine-acyclic-expiring": (82, 120, dict(schema="combine", acyclic=True, expiring=True)),
 }
 
 
@@ -33,7 +39,7 @@ def kinds_of(case):
     kw = CASES[case][2]
     if kw.get("depth_case"):
         return ["subjects", "multi"]
-    return ["subjects", "explain", "denial", "multi", "cursors"] + (["proof"] if kw.get("schema") == "combine" else [])
+    return ["subjects", "explain", "denial", "multi", "cursors", "revoke"] + (["proof"] if kw.get("schema") == "combine" else []) + (["watch"] if kw.get("expiring") else [])
 
 
 def assert_oracle_side_coverage(case, st):
@@ -56,6 +62,13 @@ def assert_oracle_side_coverage(case, st):
     else:
         assert st["denied_with_grants"] >= 20, st
     assert st["cursors_read_later"] >= 4 and st["derives"] >= 1 and st["cursors_closed"] >= 1 and st["cursors_left_open"] >= 1, st
+    assert st["revoke_with_cuts"] >= 20 and st["revoke_items"] > st["revoke_with_cuts"], st  # (granted items with a single delete that revokes them, and some with none)
+    if kw.get("expiring"):
+        from tests.fuzz_clock import assert_clock_coverage
+        assert_clock_coverage(st, kw.get("schema") == "combine")
+        assert st["cursors_read_after_clock_move"] >= 2, st  # (a cursor keeps the rows of its open across an expiry)
+        # a poll per direction whose expected difference holds a loss, behind a clock move with no accepted write in between
+        assert st["watch_polls"] >= 3 and st["watch_loss_behind_clock_res"] >= 1 and st["watch_loss_behind_clock_sub"] >= 1, st
 
 
 def assert_engine_side_coverage(case, st):

@@ -15,6 +15,9 @@ What a case cannot show, by the oracles' own definitions (expected values come f
     oracles need over a second per target there, as in the read campaign's depth case), and one namespace's viewer relation, the answered call there that crosses
     shards: the conditions on the share of non-empty rows, on empty and interned-only rows and on wildcard rows are the other cases'.
 
+The `*-expiring-*` cases run the schemas' expiring variants under a moving clock (fuzz_gpu.Clock): a clock move is a script step that every rank applies to its
+own engine before the next read, followed by the clock's probe batch as a Check step; the dry run verifies every rank's patched snapshot behind every move.
+
 A seed whose stream does not exercise what its case is for fails the conditions on a CPU, before the case is replayed on a GPU."""
 import importlib.util
 import os
@@ -29,6 +32,9 @@ CASES = {
     "combine-acyclic-w8": (33, 100, 8, dict(schema="combine", acyclic=True)),
     "combine-acyclic-recycle-compactions-w4": (43, 100, 4, dict(schema="combine", acyclic=True, recycle=True, compact_early=True)),
     "combine-cyclic-depth-w5": (35, 60, 5, dict(schema="combine", depth_case=True, read_share=0.9)),
+    # the schemas' expiring variants under a moving clock (fuzz_gpu.Clock): a clock step is a script step every rank applies to its own engine
+    "c4-expiring-w5": (98, 60, 5, dict(expiring=True, exchange="alltoall", probe=60)),  # (60 steps, a probe batch of 60: the oracle's time on the cyclic graph)
+    "combine-acyclic-expiring-w8": (93, 100, 8, dict(schema="combine", acyclic=True, expiring=True)),
 }
 # the cases whose stream outruns the LookupSubjects loop's burst hint too (a native call whose levels exceed 2 and the call's before it)
 SUBJECTS_HINT_OUTRUN = ("c4-cyclic-w2", "c4-recycle-compactions-w5", "c4-cyclic-w8-xcap8", "combine-acyclic-w8", "combine-acyclic-recycle-compactions-w4")
@@ -72,6 +78,11 @@ def assert_oracle_side_coverage(case, st):
         assert st["lookup_calls_failed"] >= 1 and st["lookup_rows_nonempty"] >= 1 and st["subj_calls_failed"] >= 1 and st["subj_calls_answered"] >= 1, st
     else:  # (see the header: nothing fails on a monotone schema, and nothing ends at the depth limit without cycles)
         assert st["lookup_calls_failed"] == 0 and st["subj_calls_failed"] == 0 and st["subj_depth"] == 0, st
+    if kw.get("expiring"):
+        from tests.fuzz_clock import assert_clock_coverage
+        assert_clock_coverage(st, combine)
+        for k in ("check", "lookup", "subjects"):  # a read round of each loop behind a clock move with no accepted write in between
+            assert st["reads_behind_clock_" + k] >= 1, (k, st)
 
 
 def assert_cpu_engine_side_coverage(case, st):
@@ -101,7 +112,10 @@ def assert_gpu_side_coverage(case, st):
             assert r["ids_recycled"] >= 5, r
         want = [("check", ERR_FAILED_PRECONDITION), ("lookup", ERR_FAILED_PRECONDITION)] if combine else []
         assert sorted(r["refusals"]) == want, r
-    calls = st["calls"]  # (step, kind, follows a write, levels, retries, entries_exchanged, host_syncs, export_capacity)
+    calls = st["calls"]  # (step, kind, follows a write, levels, retries, entries_exchanged, host_syncs, export_capacity, behind a clock move)
+    if kw.get("expiring"):  # a native call of each loop behind a clock move with no write in between: the rank's snapshot followed the clock alone
+        for kind in ("check", "lookup", "subjects"):
+            assert any(c[1] == kind and c[8] and not c[2] for c in calls), (kind, "no native call behind a clock move")
     for kind in ("check", "lookup", "subjects"):
         assert sum(c[5] for c in calls if c[1] == kind) > 0, (kind, "no entry crossed a shard")
     if kw.get("xcap"):

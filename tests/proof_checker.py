@@ -29,15 +29,20 @@ from oracle.pyoracle import NO, MAX_DEPTH, PyOracle, Relation, parse_schema
 class ProofChecker:
     """The oracles over one relationship set, built once; check() holds one proof to the contract."""
 
-    def __init__(self, schema, relationships):
+    def __init__(self, schema, relationships, now=0):
+        """relationships: 6-tuples, (6-tuple..., expires_at) 7-tuples or {6-tuple: expires_at}; now: the clock of both oracles.  S is what is live then, and
+        every relationship is written with its expiry."""
         self.defs = parse_schema(schema)
-        self.S = {tuple(r[:6]) for r in relationships}
+        at = dict(relationships) if isinstance(relationships, dict) else {tuple(r[:6]): (r[6] if len(r) > 6 else 0) for r in relationships}
+        self.S = {r for r, exp in at.items() if exp == 0 or exp > now}
         self.py, self.c = PyOracle(schema), orc.Oracle(schema)
-        for r in self.S:
-            self.py.touch(*r)
-        todo = sorted(self.S)
+        self.py.now = now
+        self.c.set_now(now)
+        for r, exp in at.items():
+            self.py.touch(*r, expires=exp)
+        todo = sorted(at.items())
         for k in range(0, len(todo), 500):  # (a write holds at most 1 000 updates)
-            self.c.touch(*todo[k:k + 500])
+            self.c.write([(orc.OP_TOUCH, r, exp) for r, exp in todo[k:k + 500]])
         self.rows = {}
         for r in self.S:
             self.rows.setdefault(r[:3], set()).add(r[3:6])

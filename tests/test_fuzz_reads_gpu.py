@@ -10,6 +10,11 @@ other read paths answer on the snapshot patched in place -- each held to the ora
      as include/aclgpu.h states them, and access_review;
   f. lookup, subject and mixed cursors held open across later writes, compactions and recycled ids: the ids stay what they were at every page size, names are
      answered or refused, derived cursors and counts equal the set algebra of the remembered ids; some cursors are left for the engine to close.
+  g. Explain for revocation: the cut set of granted monotone items equals the brute force (one relationship out, every item asked, back) and goes through
+     tests/revoke_checker.py;
+  h. the `*-expiring` cases: the schemas' expiring variants under a clock that moves forwards and back between the writes (fuzz_gpu.Clock) -- a probe batch of
+     Check items behind every move, every kind above at the current clock with the hops' expiries in the checkers' replays, cursors read across clock moves,
+     and a resource-direction and a subject-direction watch set polled against the difference of the oracle's rows (tests/watch_records.py).
 tests/fuzz_reads_cases.py holds the cases and the coverage conditions; tests/test_fuzz_reads_cpu.py runs the same cases without an engine.
 The second test is the expiring-keys campaign (run_expiry), which now also asks LookupSubjects and Explain about live and expired idempotency keys."""
 import pytest

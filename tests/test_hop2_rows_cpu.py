@@ -142,3 +142,29 @@ def test_writes_keep_or_drop_the_rows(aclgpu):
     nest.append((7, 8))
     rebuilt()
     e.close()
+
+
+def test_an_expiry_drops_the_rows_with_a_patch_and_a_build_brings_them_back(aclgpu):
+    """The host half of tests/test_hop2_walk_gpu.py test_an_expiring_nesting_under_two_hop_rows: a nesting under a two-hop row runs out (and comes back when
+    the clock is set back) with no write -- the snapshot follows by a patch that drops the rows, verified against the store at every clock; a build at a clock
+    between the two expiries composes rows over the live nestings again."""
+    from tests.test_hop2_walk_gpu import N_USER, _fuzz_tool, expiring_family
+    g, ups, _lost = expiring_family()
+    t0 = 1_700_000_000
+    e = aclgpu.Engine(_fuzz_tool().SCHEMA_C4_EXPIRING, store_only=True)
+    e.set_now(t0)
+    g.load(e)
+    e.write([(aclgpu.OP_TOUCH, r, t0 + d) for r, d in ups])
+    assert e.selfcheck_snapshot_code() == 0
+    rows = e.stats()["hop2_rows"]
+    assert rows == two_hop_count(u32([p for p, _ in g.nest]), u32([c for _, c in g.nest])) > 0
+    e.set_now(t0 + 50)
+    assert e.selfcheck_snapshot_code() == 2 and e.stats()["hop2_rows"] == rows  # (nothing crossed: current)
+    for d in (150, 250, 150):
+        e.set_now(t0 + d)
+        assert e.selfcheck_snapshot_code() == 1 and e.stats()["hop2_rows"] == 0, d  # patched, verified against the store; the rows are dropped
+    e.add_edges("pod", "creator", "user", "", u32([0]), u32([N_USER - 1]))
+    assert e.selfcheck_snapshot_code() == 0
+    live = [(p, c) for p, c in g.nest if (p, c) != (0, 2)]  # (T[0] -> X[0] is expired at +150 s)
+    assert e.stats()["hop2_rows"] == two_hop_count(u32([p for p, _ in live]), u32([c for _, c in live])) > 0
+    e.close()

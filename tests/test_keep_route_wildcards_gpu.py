@@ -390,3 +390,71 @@ def test_the_unknown_subject_becomes_known_and_the_wildcards_leave(aclgpu, recur
         for s in SUBJECTS + ("phantom",):
             for perm in PERMS:
                 both_forms(s, perm)
+
+
+def test_a_clock_set_back_closes_a_ring_of_groups_behind_the_depth_sweep(aclgpu):
+    """"None is deep" (engine_keep.cpp no_object_is_deep) must not outlive a clock that is set back.  A ring of three groups whose closing nesting expires at T,
+    200 of 600 pods viewed through the ring.  Past T the ring is open: the one-user CheckBulkPermissions goes forward, then sweeps (none deep) and takes the reverse
+    route.  Then the clock is set back below T WITH NO WRITE: the expired, not yet collected nesting is alive again and closes the ring, so the pods behind it answer
+    the depth error for whoever is not found first -- by both oracles.  The same call and the keep call must say so too: permissionship, error and keep byte of every
+    pair.  (The sweep is reached by call order, as everywhere in this file: the ACL_DEPTH_SWEEP knob is read once per process.)"""
+    schema = """definition user {}
+definition group { relation member: user | group#member with expiration }
+definition pod { relation viewer: user | group#member
+ permission view = viewer }"""
+    t_exp = 1_700_000_100
+    rels = ["group:r0#member@group:r1#member", "group:r1#member@group:r2#member", "group:r1#member@user:u1", "group:g3#member@user:u2"]
+    rels += [f"pod:p{i}#viewer@group:r0#member" for i in range(0, 600, 3)] + [f"pod:p{i}#viewer@user:u2" for i in range(1, 600, 3)]
+    rels += [f"pod:p{i}#viewer@group:g3#member" for i in range(2, 600, 6)]
+    closing = "group:r2#member@group:r0#member"
+    o, py = orc.Oracle(schema), pyoracle.PyOracle(schema)
+    with aclgpu.Engine(schema) as e:
+        def at(now):
+            e.set_now(now)
+            o.set_now(now)
+            py.now = now
+
+        def expected(u):
+            items = [("pod", f"p{i}", "view", "user", u, "") for i in range(600)]
+            want = [tuple(o.check(*q)) for q in items]
+            as_pair = {pyoracle.HAS: GRANTED, pyoracle.NO: DENIED, pyoracle.ERR: DEPTH}
+            assert [as_pair[py.check(*q)] for q in items] == want, ("the two oracles differ", u)
+            return items, want
+
+        def same(u, calls):
+            items, want = expected(u)
+            for k in range(calls):
+                p, er = e.check_bulk(items)
+                got = list(zip(p, er))
+                wrong = [i for i in range(600) if got[i] != want[i]]
+                assert not wrong, (u, f"call {k}: {len(wrong)} of 600 pairs differ from the oracles, first {items[wrong[0]][1]}: {got[wrong[0]]} for {want[wrong[0]]}", e.stats()["keep_route_calls"])
+            keep = np.asarray(e.check_bulk_keep(items, list(range(601)))).astype(bool)
+            assert keep.tolist() == [w_ == GRANTED for w_ in want], u
+            return want
+
+        at(t_exp - 100)
+        ups = [(orc.OP_TOUCH, r) for r in rels] + [(orc.OP_TOUCH, closing, t_exp)]
+        o.write(ups)
+        e.write(ups)
+        for r in rels:
+            py.touch(*orc.parse_rel(r))
+        py.touch(*orc.parse_rel(closing), expires=t_exp)
+        assert sum(w_ == DEPTH for w_ in expected("u2")[1]) == 200  # (the ring is closed: what the clock set back must bring back)
+        # ---- past T: the ring is open, nothing is deep; forward + note, sweep + walk, walk
+        at(t_exp + 10)
+        st0 = e.stats()
+        for u in ("u2", "stranger"):
+            want = same(u, 3)
+            assert DEPTH not in want and (u == "stranger" or 250 < sum(w_ == GRANTED for w_ in want) < 600)
+        st1 = e.stats()
+        assert st1["depth_sweeps"] > st0["depth_sweeps"] and st1["keep_route_calls"] > st0["keep_route_calls"], (st0, st1)
+        # ---- back below T, no write: the closing nesting is alive again
+        at(t_exp - 50)
+        for u in ("u2", "stranger", "u1"):
+            want = same(u, 2)
+            assert sum(w_ == DEPTH for w_ in want) == (0 if u == "u1" else 200), u  # (u1 is IN the ring: found before the limit)
+        # ---- and forward again: open, shallow
+        at(t_exp + 20)
+        for u in ("u2", "stranger"):
+            assert DEPTH not in same(u, 2)
+    o.close()

@@ -264,6 +264,17 @@ def test_long_random_write_streams_keep_the_snapshot_exact(aclgpu):
     # the same stream on the schema with exclusions, intersections, wildcard classes and a non-monotone userset subject (fuzz_gpu.SCHEMA_COMBINE)
     codes = fz.run_patcher(7, 400, schema="combine")
     assert codes[1] > 380 and codes["dropped"] == 0
+    # the two schemas' expiring variants under a clock that moves forwards and back between the writes (fuzz_gpu.Clock): nestings, tuplesets, wildcards and bans
+    # run out and come back with no write, relationships expired for 24 h are collected inside the writes, and ReadRelationships equals the C oracle's after
+    # every step.  A background build whose two halves an expiry passed between: the hook's second half replays the crossing onto the build and adopts it
+    # (verified against the store) -- it does not drop it, so "dropped_after_expiry" stays 0 here; the drop is the device path's (engine_snapshot.cpp).
+    for seed, schema in ((8, "c4"), (9, "combine")):
+        codes = fz.run_patcher(seed, 400, schema=schema, expiring=True)
+        assert codes[1] > 340 and codes[0] + codes[1] + codes[2] == 400 and codes["rebuilt_outside_adoption"] == 0, codes  # (the rest: clock moves that crossed nothing)
+        assert codes["adopted"] >= 1 and codes["adopted_after_expiry"] >= 1 and codes["adopted"] + codes["dropped"] >= 5, codes
+        assert codes["clock_forward"] >= 10 and codes["clock_back"] >= 3 and codes["expired_nestings"] >= 3 and codes["expired_tuplesets"] >= 3 and codes["collected_due"] >= 5, codes
+        if schema == "combine":
+            assert codes["expired_bans"] >= 1 and codes["expired_wildcards"] >= 1, codes
 
 
 def test_object_ids_are_recycled_and_the_snapshot_stays_exact(aclgpu, monkeypatch):

@@ -10,6 +10,7 @@ import pytest
 
 from oracle import orc
 from oracle.pyoracle import PyOracle
+from tests.watch_records import expected_records, records_of
 
 pytestmark = pytest.mark.gpu
 
@@ -102,19 +103,15 @@ class World:
         return out
 
     def expected(self):
-        recs, after = [], {}
         wid = self.e.find(self.st, WILD)
-        for w in sorted(self.resource):
-            after[w] = self.row_of(self.resource[w])
-            before = after[w] if self.held[w] is None else self.held[w]
-            ch = [(i, 1) for i in self.ids(after[w] - before)] + [(i, 0) for i in self.ids(before - after[w])]
-            recs += [(w, i, g, self.m.WATCH_CHANGE_WILDCARD if i == wid else 0) for i, g in sorted(ch)]
+        after = {w: self.row_of(self.resource[w]) for w in sorted(self.resource)}
+        recs = expected_records(self.held, after, lambda n: self.e.find(self.st, n), lambda i: self.m.WATCH_CHANGE_WILDCARD if i == wid else 0)
         return recs, after
 
     def poll_and_compare(self, tag=None):
         want, after = self.expected()
         rev, recs = self.ws.poll()
-        got = [(int(r["watcher"]), int(r["resource_id"]), int(r["gained"]), int(r["reserved"])) for r in recs]
+        got = records_of(recs, reserved=True)
         assert got == want, tag
         assert rev == self.e.revision
         self.held = after
@@ -582,5 +579,40 @@ def test_refusals_and_the_poll_loop(aclgpu, aclgpu_lib):
         assert ei.value.code == aclgpu.ERR_DEADLINE_EXCEEDED
         w.rows_match()
         assert w.poll_and_compare("after the deadline") == [(w0, w.e.find("user", "u3"), 1, 0)]
+    finally:
+        w.close()
+
+
+def test_a_ban_that_runs_out_grants_with_no_write(aclgpu):
+    """`view = (viewer + creator + namespace->view) - banned` with `banned: user with expiration` (tools/fuzz_gpu.py SCHEMA_COMBINE_EXPIRING): a ban's expiry
+    GRANTS.  One pod watched in the subject direction; the bans of a direct viewer and of a viewer through the namespace run out with no write -- the poll (the
+    device path's confirmation, k_refine_*) reports both as gained, against both oracles; a ban without an expiry stays.  The clock set back: both lost again."""
+    import importlib.util
+    import os
+    spec = importlib.util.spec_from_file_location("fuzz_gpu", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "fuzz_gpu.py"))
+    fz = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(fz)
+    users = [f"u{i}" for i in range(20)]
+    t0 = 1_700_000_000
+    w = World(aclgpu, fz.SCHEMA_COMBINE_EXPIRING, users)
+    try:
+        w.set_now(t0)
+        ups = [(OP_TOUCH, ("pod", "p0", "namespace", "namespace", "n0", ""))]
+        ups += [(OP_TOUCH, ("pod", "p0", "viewer", "user", f"u{i}", "")) for i in range(10)]
+        ups += [(OP_TOUCH, ("namespace", "n0", "viewer", "user", f"u{i}", "")) for i in range(10, 15)]
+        ups += [(OP_TOUCH, ("pod", "p0", "banned", "user", "u3", ""), t0 + 100), (OP_TOUCH, ("pod", "p0", "banned", "user", "u12", ""), t0 + 100),
+                (OP_TOUCH, ("pod", "p0", "banned", "user", "u5", "")), (OP_TOUCH, ("pod", "p0", "banned", "user", "u17", ""), t0 + 100)]
+        w.write(ups)
+        ws = w.add("p0")
+        assert len(w.poll_and_compare("baseline")) == 12  # (15 viewers, three of them banned)
+        w.rows_match()
+        rev = w.e.revision
+        w.set_now(t0 + 150)
+        assert w.poll_and_compare("the bans ran out") == [(ws, i, 1, 0) for i in sorted((w.e.find("user", "u3"), w.e.find("user", "u12")))]
+        w.rows_match()
+        w.set_now(t0 + 50)
+        assert w.poll_and_compare("the clock set back") == [(ws, i, 0, 0) for i in sorted((w.e.find("user", "u3"), w.e.find("user", "u12")))]
+        w.rows_match()
+        assert w.e.revision == rev  # (no write in between)
     finally:
         w.close()

@@ -7,6 +7,7 @@ import pytest
 
 from oracle import orc
 from oracle.pyoracle import LookupFailed, PyOracle
+from tests.watch_records import expected_records, records_of
 
 pytestmark = pytest.mark.gpu
 
@@ -67,19 +68,13 @@ class World:
 
     def expected(self, py=True):
         """the records the next poll must return, and what every watcher holds then"""
-        recs, after = [], {}
-        for w in sorted(self.subject):
-            after[w] = self.lookup(self.subject[w], py)
-            before = after[w] if self.held[w] is None else self.held[w]
-            ch = [(self.e.find(self.rt, n), 1) for n in after[w] - before] + [(self.e.find(self.rt, n), 0) for n in before - after[w]]
-            assert all(i is not None for i, _g in ch)
-            recs += [(w, i, g) for i, g in sorted(ch)]
-        return recs, after
+        after = {w: self.lookup(self.subject[w], py) for w in sorted(self.subject)}
+        return expected_records(self.held, after, lambda n: self.e.find(self.rt, n)), after
 
     def poll_and_compare(self, tag=None, py=True):
         want, after = self.expected(py)
         rev, recs = self.ws.poll()
-        got = [(int(r["watcher"]), int(r["resource_id"]), int(r["gained"])) for r in recs]
+        got = records_of(recs)
         assert got == want, tag
         assert rev == self.e.revision and not recs["reserved"].any()
         self.held = after

@@ -18,6 +18,19 @@ The oracle is the checker (tests / tools only).  Exit code 1 and a dump of the f
   f. lookup, subject and mixed cursors held open across later writes, compactions and recycled ids, with derived cursors and counts over them.
 --reads --dry is the oracle's half alone (no GPU).  --expiry also asks LookupSubjects and Explain about live and expired idempotency keys.
 
+  g. Explain for revocation: the cut set of granted monotone items against the brute force over the relationships, each through tests/revoke_checker.py;
+  h. (--expiring) a resource-direction and a subject-direction watch set on pod#view, polled against the difference of the oracle's rows since the last poll.
+
+--expiring (run, run_reads, run_patcher, run_sharded; with --dry too) is each campaign on the schema's expiring variant (SCHEMA_C4_EXPIRING / SCHEMA_COMBINE_EXPIRING:
+`with expiration` on every relation but the creators and pod#auditor) under a test clock (class Clock).  Both sides start at 1 700 000 000; two TOUCH / CREATE
+updates in five carry an expiry (now + 1 s ... 200 000 s, now and then now - 5: born expired; on a relation without the trait both sides must refuse the request
+with the same code); one step in four is a clock move in place of a write -- forward by 1 s ... 90 000 s, one time in five BACK by 1 ... 4 000 s.  The backward
+rule: the oracles do not model the collection of relationships that expired 24 h ago (Store::gc_expired, inside the next write), so one the store has collected
+would come back to life in the oracle if the clock fell below its expiry; the clock therefore never goes more than 6 h below the highest value it has had, which
+keeps every collected relationship expired on both sides.  Around every move the oracle answers a fixed probe batch of Check items before and after, the engine
+after; the oracle's read difference across the move says what ran out (nestings, tuplesets, bans, wildcards).  The pool that deletes draw from is read back from
+the oracle behind every move and every accepted write.  Without --expiring every stream is draw for draw what it was.
+
 --sharded W (run_sharded) holds the loops of the type-hash sharded graph to the oracles under the same kind of stream.  Phase 1, no GPU: one pass with the oracles
 alone writes the script -- every write with its outcome, every read with its expected answer by name.  Phase 2: W logical shards of one GPU (one engine per rank over
 a replicated store, one thread each) replay it; a rank records a wrong answer as (step, rank, kind, request, got, want) and goes on, the first record is printed:
@@ -69,6 +82,176 @@ definition pod {
   permission vetted = creator + namespace.all(view) & viewer
 }
 """
+
+
+# The two schemas with `with expiration` on every alternative of group#member, namespace#viewer, namespace#banned, pod#namespace, pod#viewer, pod#banned and
+# group#banned (run(expiring=True) and its kin); pod#creator, namespace#creator and pod#auditor stay without the trait: a write that gives one of them an
+# expiry is refused, by the engine and by the oracle with the same code.
+SCHEMA_C4_EXPIRING = """
+definition user {}
+definition group {
+  relation member: user with expiration | group#member with expiration
+}
+definition namespace {
+  relation viewer: user with expiration | group#member with expiration
+  relation creator: user
+  permission view = viewer + creator
+}
+definition pod {
+  relation namespace: namespace with expiration
+  relation viewer: user with expiration | group#member with expiration
+  relation creator: user
+  permission view = viewer + creator + namespace->view
+}
+"""
+
+SCHEMA_COMBINE_EXPIRING = """
+definition user {}
+definition group {
+  relation member: user with expiration | group#member with expiration
+  relation banned: user with expiration
+  permission active = member - banned
+}
+definition namespace {
+  relation viewer: user with expiration | group#member with expiration | user:* with expiration
+  relation creator: user
+  relation banned: user with expiration | group#member with expiration
+  permission view = (viewer + creator) - banned
+}
+definition pod {
+  relation namespace: namespace with expiration
+  relation viewer: user with expiration | group#member with expiration | group#active with expiration
+  relation creator: user
+  relation auditor: user | group#member
+  relation banned: user with expiration | user:* with expiration
+  permission view = (viewer + creator + namespace->view) - banned
+  permission audit = auditor & namespace->view
+  permission edit = creator + (viewer & auditor) - banned
+  permission hidden = view - (auditor & creator)
+  permission everywhere = namespace.all(view)
+  permission vetted = creator + namespace.all(view) & viewer
+}
+"""
+
+CLOCK_START = 1_700_000_000
+CLOCK_BACK_LIMIT = 6 * 3600   # a clock set back stays within 6 h of the highest value it has had (see Clock)
+COLLECT_AFTER = 86400         # Store::gc_expired: a relationship expired this long is collected inside the next write
+CLOCK_STATS = ("clock_forward", "clock_back", "lost_by_clock", "gained_by_clock", "gained_by_clock_back", "expired_nestings", "expired_tuplesets", "expired_bans",
+               "expired_wildcards", "collected_due", "writes_with_expiry", "expiry_refused")
+
+
+def schema_text_of(schema: str, expiring: bool = False) -> str:
+    from aclgpu import workloads
+    if schema == "combine":
+        return SCHEMA_COMBINE_EXPIRING if expiring else SCHEMA_COMBINE
+    return SCHEMA_C4_EXPIRING if expiring else workloads.SCHEMA_C4
+
+
+def read_live(o) -> set:
+    """the relationships the oracle reads at its clock, as texts"""
+    return set(f"{a}:{b}#{c}@{d}:{x}" + (f"#{y}" if y else "") for t in ("group", "namespace", "pod") for a, b, c, d, x, y, *_ in o.read(rtype=t))
+
+
+class Clock:
+    """The test clock of an expiring run: both sides start at CLOCK_START, every draw comes from the write stream's generator (and only when the run is an
+    expiring one, so every other case's stream stays draw for draw what it was).
+      * write_batch gives a TOUCH / CREATE an expiry with probability 0.4: now + 1 s ... 200 000 s, one time in ten now - 5 (born expired).  On a relation
+        without the trait (the creators, pod#auditor) about one such write in seven keeps the expiry: both sides must refuse the request with the same code.
+      * move(): forward by 1 s ... 90 000 s, one time in five BACK by 1 ... 4 000 s.  The oracles do not model the collection of relationships that expired 24 h
+        ago (Store::gc_expired, inside the next write): one the store has collected would come back to life in the oracle if the clock fell below its expiry.  So
+        the clock never goes more than 6 h below the highest value it has had -- every collected relationship stays expired on both sides.
+    around(): the probe batch (about 200 Check items, chosen once per run from a generator of their own) is answered by the oracle before and after a move and by
+    the engines after it; the answers and the oracle's read difference across the move feed the CLOCK_STATS counters.  The batch is chosen at the first move:
+    random Check items, half of them granted on the graph of that moment (most random items are denied whatever the clock says)."""
+
+    def __init__(self, rng, seed, names, combine, o, engines, stats, probe: int = 200):
+        self.rng, self.o, self.engines, self.stats, self.combine = rng, o, [e for e in engines if e is not None], stats, combine
+        self.now = self.high = CLOCK_START
+        self.expiries = {}      # relationship text -> expiry, of the accepted writes that carried one and are neither deleted nor rewritten nor counted as collected
+        self.moved_last = False  # the step before was a clock move (no accepted write since)
+        self.probe, self._probe_of = None, (random.Random(f"probe/{seed}"), names, probe)
+        for k in CLOCK_STATS:
+            stats.setdefault(k, 0)
+        for x in [o] + self.engines:
+            x.set_now(self.now)
+
+    def expiry_for(self, text, refusable=True):
+        """the expiry a TOUCH / CREATE of `text` carries (0: none); refusable: a relation without the trait may keep it"""
+        rng = self.rng
+        if rng.random() >= 0.4:
+            return 0
+        at = self.now - 5 if rng.random() < 0.1 else self.now + rng.choice([1, 5, 60, 3600, 86400, 200000])
+        rel = text.split("#", 1)[1].split("@", 1)[0]
+        if rel in ("creator", "auditor") and (not refusable or rng.random() >= 0.15):
+            return 0
+        return at
+
+    def accepted(self, ups, delete_op):
+        """an accepted write batch: what it leaves with an expiry, and how many relationships expired for 24 h the store collects inside it"""
+        for u in ups:
+            self.expiries.pop(u[1], None)
+            if u[0] != delete_op and len(u) > 2 and u[2]:
+                self.expiries[u[1]] = u[2]
+        due = [t for t, at in self.expiries.items() if at <= self.now - COLLECT_AFTER]
+        for t in due:
+            del self.expiries[t]
+        self.stats["collected_due"] += len(due)
+        self.moved_last = False
+
+    def filtered(self, f):
+        """an accepted DeleteRelationships by filter `f`: what it removed is not there to collect"""
+        from oracle import orc
+        keys = ("rtype", "rid", "rel", "stype", "sid", "srel")
+        for t in [t for t in self.expiries if all(f.get(k) is None or f[k] == v for k, v in zip(keys, orc.parse_rel(t)))]:
+            del self.expiries[t]
+        self.moved_last = False
+
+    def draw_move(self) -> int:
+        rng = self.rng
+        if rng.random() < 0.2:
+            d = -rng.choice([1, 20, 200, 4000])
+            return max(d, self.high - CLOCK_BACK_LIMIT - self.now)
+        return rng.choice([1, 1, 3, 10, 61, 3601, 50000, 90000])
+
+    def move(self, step, live=None, check=None):
+        """one clock step on every side -> (delta, relationships the oracle read before and not after, probe answers after).  check(probe, want, where): how
+        the caller's engine answers the probe batch (None: the oracle alone)."""
+        o, st = self.o, self.stats
+        d = self.draw_move()
+        if self.probe is None:
+            pr, names, n = self._probe_of
+            has, rest = [], []
+            for q in dict.fromkeys(rand_query(pr, names, self.combine) for _ in range(20 * n)):
+                side = has if tuple(o.check(*q)) == (2, 0) else rest
+                if len(side) < n // 2:
+                    side.append(q)
+            self.probe = has + rest
+        before = read_live(o)
+        was = [tuple(o.check(*q)) for q in self.probe]
+        self.now += d
+        self.high = max(self.high, self.now)
+        for x in [o] + self.engines:
+            x.set_now(self.now)
+        after = read_live(o)
+        want = [tuple(o.check(*q)) for q in self.probe]
+        st["clock_forward" if d > 0 else "clock_back"] += d != 0
+        lost = sum(a == (2, 0) and b != (2, 0) for a, b in zip(was, want))
+        gained = sum(a != (2, 0) and b == (2, 0) for a, b in zip(was, want))
+        st["lost_by_clock"] += lost
+        st["gained_by_clock" if d > 0 else "gained_by_clock_back"] += gained
+        for t in before - after:
+            head, subj = t.split("@", 1)
+            st["expired_nestings"] += head.startswith("group:") and head.endswith("#member") and subj.startswith("group:")
+            st["expired_tuplesets"] += head.endswith("#namespace")
+            st["expired_bans"] += head.endswith("#banned")
+            st["expired_wildcards"] += subj.endswith(":*")
+        if live is not None:
+            live.clear()
+            live.update(after)
+        self.moved_last = True
+        if check is not None:
+            check(self.probe, want, f"step {step} (clock {'+' if d > 0 else ''}{d} s, now {self.now})")
+        return d, before - after, want
 
 
 def make_universe(rng, universe: int = 1):
@@ -149,34 +332,51 @@ def open_engine(schema_text: str, recycle: bool, compact_early: bool, **engine_k
         os.environ.pop("ACL_ID_QUARANTINE_MS", None)
 
 
-def load_initial(rand_tuple, o, e, live: set, universe: int = 1):
-    """the starting graph: 2500 draws of rand_tuple per universe, written to the oracle and (unless e is None) to the engine"""
+def load_initial(rand_tuple, o, e, live: set, universe: int = 1, clock=None):
+    """the starting graph: 2500 draws of rand_tuple per universe, written to the oracle and (unless e is None) to the engine; under a Clock two in five of its
+    relationships carry an expiry where the relation has the trait"""
     import aclgpu
     from oracle import orc
     init = list(dict.fromkeys(rand_tuple() for _ in range(2500 * universe)))
+    if clock is not None:
+        init = [(t, clock.expiry_for(t, refusable=False)) for t in init]
+        init = [(t, at) if at else (t,) for t, at in init]
+    else:
+        init = [(t,) for t in init]
     for i in range(0, len(init), 500):
-        o.write([(orc.OP_TOUCH, t) for t in init[i:i + 500]])
+        o.write([(orc.OP_TOUCH,) + u for u in init[i:i + 500]])
         if e is not None:
-            e.write([(aclgpu.OP_TOUCH, t) for t in init[i:i + 500]])
-    live.update(init)
+            e.write([(aclgpu.OP_TOUCH,) + u for u in init[i:i + 500]])
+    if clock is not None:
+        clock.accepted([(aclgpu.OP_TOUCH,) + u for u in init], aclgpu.OP_DELETE)
+        live.update(read_live(o))
+    else:
+        live.update(u[0] for u in init)
 
 
-def write_batch(rng, step, rand_tuple, o, e, live: set, burst: int, stats: dict) -> bool:
+def write_batch(rng, step, rand_tuple, o, e, live: set, burst: int, stats: dict, clock=None) -> bool:
     """One write batch (TOUCH / CREATE / DELETE) on both sides, which accept it or reject it with the same code; e is None: the oracle alone.
+    clock: a Clock -- some TOUCH / CREATE updates carry an expiry (Clock.expiry_for), and `live` is read back from the oracle behind an accepted batch.
     -> True when it was accepted (`live` follows it)."""
     import aclgpu
     from oracle import orc
     ups = []
     pool = sorted(live) if live else []  # (once per batch: a delete picks from the relationships that exist)
+
+    def upsert(op):
+        t = rand_tuple()
+        at = clock.expiry_for(t) if clock is not None else 0
+        return (op, t, at) if at else (op, t)
+
     for _ in range(rng.randrange(1, burst)):
         q = rng.random()
-        if q < 0.5: ups.append((aclgpu.OP_TOUCH, rand_tuple()))
-        elif q < 0.5 + 0.1 / max(1, burst // 25): ups.append((aclgpu.OP_CREATE, rand_tuple()))
+        if q < 0.5: ups.append(upsert(aclgpu.OP_TOUCH))
+        elif q < 0.5 + 0.1 / max(1, burst // 25): ups.append(upsert(aclgpu.OP_CREATE))
         elif pool: ups.append((aclgpu.OP_DELETE, rng.choice(pool) if rng.random() < 0.9 else rand_tuple()))
-    ups = list({t: (op, t) for op, t in ups}.values())  # one update per relationship in a request
+    ups = list({u[1]: u for u in ups}.values())  # one update per relationship in a request
     eo = ee = None
     try:
-        o.write([({aclgpu.OP_TOUCH: orc.OP_TOUCH, aclgpu.OP_CREATE: orc.OP_CREATE, aclgpu.OP_DELETE: orc.OP_DELETE}[op], t) for op, t in ups])
+        o.write([({aclgpu.OP_TOUCH: orc.OP_TOUCH, aclgpu.OP_CREATE: orc.OP_CREATE, aclgpu.OP_DELETE: orc.OP_DELETE}[u[0]],) + tuple(u[1:]) for u in ups])
     except orc.OracleError as x:
         eo = x.code
     if e is not None:
@@ -186,15 +386,22 @@ def write_batch(rng, step, rand_tuple, o, e, live: set, burst: int, stats: dict)
             ee = x.code
         assert eo == ee, f"step {step}: write outcome differs: oracle {eo}, engine {ee}: {ups}"
     stats["writes"] += 1
+    if clock is not None:
+        stats["writes_with_expiry"] += any(len(u) > 2 for u in ups)
+        stats["expiry_refused"] += eo is not None and any(len(u) > 2 and u[1].split("#", 1)[1].split("@", 1)[0] in ("creator", "auditor") for u in ups)
     if eo is None:
-        for op, t in ups:
-            (live.discard if op == aclgpu.OP_DELETE else live.add)(t)
+        for u in ups:
+            (live.discard if u[0] == aclgpu.OP_DELETE else live.add)(u[1])
+        if clock is not None:  # (a relationship born expired is not there to delete: the pool is what the oracle reads)
+            clock.accepted(ups, aclgpu.OP_DELETE)
+            live.clear()
+            live.update(read_live(o))
     else:
         stats["write_errors"] += 1
     return eo is None
 
 
-def filter_delete(rng, step, names, combine: bool, o, e, live: set, stats: dict) -> int:
+def filter_delete(rng, step, names, combine: bool, o, e, live: set, stats: dict, clock=None) -> int:
     """DeleteRelationships by one random filter on both sides (e is None: the oracle alone) -> how many relationships it removed; `live` is read back"""
     users, groups, nss, pods = names
     f = rng.choice([dict(rtype="pod", rid=rng.choice(pods)), dict(rtype="group", rel="member", stype="user", sid=rng.choice(users)),
@@ -204,38 +411,52 @@ def filter_delete(rng, step, names, combine: bool, o, e, live: set, stats: dict)
     if e is not None:
         n2 = e.delete_by_filter(**f)
         assert n1 == n2, f"step {step}: delete_by_filter {f}: oracle removed {n1}, engine {n2}"
-    now = set(f"{a}:{b}#{c}@{d}:{x}" + (f"#{y}" if y else "") for t in ("group", "namespace", "pod") for a, b, c, d, x, y, _ in o.read(rtype=t))
+    now = read_live(o)
     live.clear()
     live.update(now)
     stats["filter_deletes"] += 1
+    if clock is not None and n1:
+        clock.filtered(f)
     return n1
 
 
 def run(seed: int, steps: int, big: int = 70000, verbose: bool = True, burst: int = 25, universe: int = 1, compact_early: bool = False, schema: str = "c4",
-        recycle: bool = False, acyclic: bool = False) -> dict:
-    import aclgpu
-    from aclgpu import workloads
+        recycle: bool = False, acyclic: bool = False, expiring: bool = False, engine: bool = True, probe: int = 200) -> dict:
+    """The Check campaign (the header's first paragraph).  expiring: the schema's expiring variant under a Clock -- writes with an expiry, one step in four a
+    clock move with the probe batch answered around it.  engine=False: the oracle's half alone (no GPU): what the stream covers."""
     from oracle import orc
     combine = schema == "combine"
-    schema_text = SCHEMA_COMBINE if combine else workloads.SCHEMA_C4
+    schema_text = schema_text_of(schema, expiring)
 
     rng = random.Random(seed)
     names = users, groups, nss, pods = make_universe(rng, universe)
     rand_tuple = make_rand_tuple(rng, names, combine, recycle, acyclic)
 
-    e = open_engine(schema_text, recycle, compact_early)
+    e = open_engine(schema_text, recycle, compact_early) if engine else None
     o = orc.Oracle(schema_text)
     live = set()
-    load_initial(rand_tuple, o, e, live, universe)
     stats = {"writes": 0, "write_errors": 0, "filter_deletes": 0, "checks": 0, "lookups": 0, "single_checks": 0}
-    e.batcher_start(4096, 100)
+    clock = Clock(rng, seed, names, combine, o, [e], stats, probe) if expiring else None  # (before the first write: the starting graph is written at the clock's start)
+    load_initial(rand_tuple, o, e, live, universe, clock)
+    if e is not None:
+        e.batcher_start(4096, 100)
+
+    def probe_check(qs, want, where):
+        perms, errs = e.check_bulk(qs)
+        for i, q in enumerate(qs):
+            assert (perms[i], errs[i]) == want[i], f"{where}: probe check {q} (item {i}): engine {(perms[i], errs[i])}, oracle {want[i]}"
+        stats["checks"] += len(qs)
+
     t0 = time.time()
     for step in range(steps):
+        if clock is not None and rng.random() < 0.25:  # ---- the clock moves: no write, and the next read sees every relationship whose liveness changed
+            clock.move(step, live, probe_check if e is not None else None)
+            continue
         r = rng.random()
         if r < 0.45:  # ---- a write batch: both sides accept it or reject it with the same code
-            write_batch(rng, step, rand_tuple, o, e, live, burst, stats)
+            write_batch(rng, step, rand_tuple, o, e, live, burst, stats, clock)
         elif r < 0.5:  # ---- DeleteRelationships by filter
-            filter_delete(rng, step, names, combine, o, e, live, stats)
+            filter_delete(rng, step, names, combine, o, e, live, stats, clock)
         elif r < 0.56 and not combine:  # ---- PostFilter's shape: ONE user's pairs -- CheckBulkPermissions itself twice (the second call may sweep the type for depth
             # errors and take the reverse walk: engine_keep.cpp no_object_is_deep; with a cycle behind some resource the calls stay forward and carry its depth errors),
             # then the keep mask of the same pairs.  Every permissionship, every error and every keep byte against the oracle.
@@ -244,12 +465,12 @@ def run(seed: int, steps: int, big: int = 70000, verbose: bool = True, burst: in
             k_ = rng.choice([520, 900, 2500])
             qs = [(rt, rng.choice(ids) if rng.random() < 0.98 else "n0/ghost", perm, "user", u, "") for _ in range(k_)]
             want = {q: o.check(*q) for q in set(qs)}
-            for rep in range(2):
+            for rep in range(2 if e is not None else 0):
                 perms, errs = e.check_bulk(qs)
                 for i, q in enumerate(qs):
                     assert (perms[i], errs[i]) == tuple(want[q]), f"step {step}: one-user check {q} (item {i} of {k_}, call {rep}): engine {(perms[i], errs[i])}, oracle {want[q]}"
-            keep = e.check_bulk_keep(qs, list(range(k_ + 1)))
-            for i, q in enumerate(qs):
+            keep = e.check_bulk_keep(qs, list(range(k_ + 1))) if e is not None else []
+            for i, q in enumerate(qs[:len(keep)]):
                 assert bool(keep[i]) == (tuple(want[q]) == (2, 0)), f"step {step}: keep mask of {q} (item {i}): engine {keep[i]}, oracle {want[q]}"
             stats["checks"] += 3 * k_
             stats["one_user_calls"] = stats.get("one_user_calls", 0) + 3
@@ -259,12 +480,14 @@ def run(seed: int, steps: int, big: int = 70000, verbose: bool = True, burst: in
             qs = (qs * (n // len(qs) + 1))[:n]
             want = {q: o.check(*q) for q in set(qs)}
             if n == 1 and rng.random() < 0.5:  # the micro-batcher's single check
-                got = [e.check_one(*qs[0])]
+                got = [e.check_one(*qs[0])] if e is not None else []
                 stats["single_checks"] += 1
-            else:
+            elif e is not None:
                 perms, errs = e.check_bulk(qs)
                 got = list(zip(perms, errs))
-            for i, q in enumerate(qs):
+            else:
+                got = []
+            for i, q in enumerate(qs[:len(got)]):
                 assert tuple(got[i]) == tuple(want[q]), f"step {step}: check {q} (item {i} of {n}): engine {got[i]}, oracle {want[q]}"
             stats["checks"] += n
         else:  # ---- LookupResources: one subject, or a batch of subjects in one walk
@@ -280,12 +503,14 @@ def run(seed: int, steps: int, big: int = 70000, verbose: bool = True, burst: in
                     return ("err", ex.code)
 
             for u in subs[:3]:
-                a, b = out(e.lookup, rt, perm, "user", u), out(o.lookup, rt, perm, "user", u)
+                b = out(o.lookup, rt, perm, "user", u)
+                a = out(e.lookup, rt, perm, "user", u) if e is not None else b
                 assert a == b, f"step {step}: lookup {rt}#{perm}@user:{u}: engine {a[0]} {str(a[1])[:200]}, oracle {b[0]} {str(b[1])[:200]}"
                 stats["lookups_failed"] = stats.get("lookups_failed", 0) + int(a[0] == "err")
             if len(subs) > 3:
-                ids = [e.intern("user", u) for u in subs]
                 wants = [out(o.lookup, rt, perm, "user", u) for u in subs]
+            if len(subs) > 3 and e is not None:
+                ids = [e.intern("user", u) for u in subs]
                 batch = out(lambda: [0] if e.lookup_ids_batch(rt, perm, "user", "", ids) is None else [1])
                 if any(w_[0] == "err" for w_ in wants):  # one failing lookup fails the batch call
                     assert batch[0] == "err", f"step {step}: batched lookup {rt}#{perm}: the oracle fails {[u for u, w_ in zip(subs, wants) if w_[0] == 'err'][:3]}, the engine answered"
@@ -297,9 +522,11 @@ def run(seed: int, steps: int, big: int = 70000, verbose: bool = True, burst: in
             stats["lookups"] += len(subs)
         if verbose and step % 50 == 49:
             print(f"step {step + 1}/{steps}: {stats}, {len(live)} relationships, {time.time() - t0:.1f} s", file=sys.stderr, flush=True)
-    st = e.stats()
-    stats.update({k: int(st[k]) for k in ("snapshot_builds", "snapshot_patches", "snapshot_compactions", "local_passes", "rev_local_passes", "ids_recycled", "keep_route_calls", "depth_sweeps") if k in st})
-    e.close()
+    stats["seconds"] = round(time.time() - t0, 1)
+    if e is not None:
+        st = e.stats()
+        stats.update({k: int(st[k]) for k in ("snapshot_builds", "snapshot_patches", "snapshot_compactions", "local_passes", "rev_local_passes", "ids_recycled", "keep_route_calls", "depth_sweeps") if k in st})
+        e.close()
     return stats
 
 
@@ -341,10 +568,13 @@ class _Reads:
     """The read rounds of run_reads: every kind computes what the oracles expect from the generator's own names and the oracle's live relationships, and --
     unless the run is a dry one (e is None) -- holds the engine's answer to it.  Every draw comes from `rr`, never from the write stream's generator."""
 
-    def __init__(self, rr, names, schema_text, combine, recycle, o, e, live, stats, depth_case, cyclic):
+    def __init__(self, rr, names, schema_text, combine, recycle, o, e, live, stats, depth_case, cyclic, clock=None):
         from oracle.pyoracle import parse_schema
         self.rr, self.names, self.schema, self.combine, self.recycle, self.o, self.e, self.live, self.stats = rr, names, schema_text, combine, recycle, o, e, live, stats
-        self.depth_case, self.cyclic = depth_case, cyclic
+        self.depth_case, self.cyclic, self.clock = depth_case, cyclic, clock
+        self.clock_moves = 0     # moves with every clock move (an expiring run)
+        self.expiry = {}         # the live relationships' expiries (an expiring run: rels() reads them from the oracle)
+        self.watch = None        # kind h: the two watch sets, once opened
         self.defs = parse_schema(schema_text)
         self.nonmono = nonmono_members(self.defs)
         self.targets = [(t, m) for t, d in self.defs.items() for m in d.members]  # every relation and permission, in slot order
@@ -362,9 +592,30 @@ class _Reads:
     def rels(self):
         """the live relationships as 6-tuples (cached until the next accepted write)"""
         from oracle import orc
-        if self._rels[0] != self.version:
-            self._rels = (self.version, [orc.parse_rel(t) for t in sorted(self.live)])
+        key = (self.version, self.clock_moves)
+        if self._rels[0] != key:
+            if self.clock is None:
+                self._rels = (key, [orc.parse_rel(t) for t in sorted(self.live)])
+            else:  # (what the oracle reads at its clock, with the expiries the checkers carry into their replays)
+                rows = sorted(x for t in ("group", "namespace", "pod") for x in self.o.read(rtype=t))
+                self._rels = (key, [x[:6] for x in rows])
+                self.expiry = {x[:6]: x[6] for x in rows}
         return self._rels[1]
+
+    def now(self):
+        return self.clock.now if self.clock is not None else 0
+
+    def replay_at(self):
+        """what a witness replay carries besides the hops: their expiries and the clock (an expiring run; otherwise nothing, as before)"""
+        return dict(expires=self.expiry, now=self.now()) if self.clock is not None else {}
+
+    def proof_over(self):
+        """the relationships a ProofChecker is built over, with their expiries and the clock in an expiring run"""
+        return (self.rels_with_expiry(), self.now()) if self.clock is not None else (self.rels(),)
+
+    def rels_with_expiry(self):
+        rels = self.rels()
+        return {r: self.expiry.get(r, 0) for r in rels}
 
     def names_of(self, t):
         """every name of type `t` the generator knows: the universe, `stranger`, and the names in the live relationships"""
@@ -439,6 +690,8 @@ class _Reads:
         """per resource: (ids, wildcard, excluded) by name, or "DEPTH".  C4: the C oracle's Check over every name; combine: the contract of
         tests/subjects_contract.py through the Python oracle"""
         names = [n for n in self.names_of(st)]
+        if st == rt:  # (a resource the call interns is a name of the subject type too -- one nobody has written holds its own `st#srel` state and nothing else)
+            names = sorted(set(names) | set(rids))
         if not self.combine:
             return [({s for s in names if self.o.check(rt, rid, perm, st, s, srel) == (2, 0)}, False, set()) for rid in rids]
         from tests.subjects_contract import SubjectsContract
@@ -589,7 +842,7 @@ class _Reads:
             else:
                 assert int(flags[i]) == aclgpu.EXPLAIN_WITNESS, f"{where}: granted by a monotone permission, flags {int(flags[i])}"
                 try:
-                    X.check_witness(self.schema, relset, q, self.hop_names(hops), replay_it=replayed < 32)
+                    X.check_witness(self.schema, relset, q, self.hop_names(hops), replay_it=replayed < 32, **self.replay_at())
                 except AssertionError as x:
                     raise AssertionError(f"{where}: {x}") from None
                 replayed += 1
@@ -612,9 +865,9 @@ class _Reads:
         st_["proof_items"] += len(qs)
         st_["proofs"] += len(granted)
         if e is None:
-            P.ProofChecker(self.schema, self.rels())  # (the dry run pays for the checker's oracles as the real one does)
+            P.ProofChecker(self.schema, *self.proof_over())  # (the dry run pays for the checker's oracles as the real one does)
             return True
-        chk = P.ProofChecker(self.schema, self.rels())
+        chk = P.ProofChecker(self.schema, *self.proof_over())
         perm, err, flags, off, raw, aoff, araw = e.explain_proof_ids(self.items(qs))
         for i, q in enumerate(qs):
             where = f"step {step} (Explain proof) {q} (item {i})"
@@ -635,7 +888,7 @@ class _Reads:
         import aclgpu
         from tests import denial_checker as D
         rr, e, st_ = self.rr, self.e, self.stats
-        orcs = D.Oracles(self.schema, self.rels())
+        orcs = D.Oracles(self.schema, self.rels_with_expiry(), self.now())
         cand = [q for q in self.explain_items(120) if (q[0], q[2]) not in self.nonmono]
         denied = []
         for q in dict.fromkeys(cand):
@@ -646,7 +899,7 @@ class _Reads:
         if not denied:
             return False
         # the restatement's own answer: which of them have a grant at all, and -- in a dry run -- the lists the checker is timed on
-        restated = [D.grants_of(orcs.defs, D.closure(orcs.defs, orcs.rels, q[:3]), q[3], q[5]) for q in denied]
+        restated = [D.grants_of(orcs.defs, D.closure(orcs.defs, orcs.rels, q[:3], self.now()), q[3], q[5]) for q in denied]
         st_["denied_items"] += len(denied)
         st_["denied_with_grants"] += sum(bool(g) for g in restated)
         if e is None:
@@ -664,6 +917,103 @@ class _Reads:
                 D.check_grants(orcs, q, grants, seed=step)
             except AssertionError as x:
                 raise AssertionError(f"{where}: {x}") from None
+        return True
+
+    # ---- g. Explain for revocation
+    def round_revoke(self, step):
+        """granted monotone items of the stream: the engine's cut set of each -- the single deletes that revoke it -- is the brute force's (one relationship out,
+        every item asked, the relationship back, for EVERY live relationship, by the C oracle), and goes through tests/revoke_checker.py (every cut revokes by both
+        oracles, with the expiries and the clock of the store)"""
+        import aclgpu
+        from tests import revoke_checker as R
+        rr, e, o, st_ = self.rr, self.e, self.o, self.stats
+        cand = [q for q in dict.fromkeys(self.explain_items(150)) if (q[0], q[2]) not in self.nonmono and tuple(o.check(*q)) == (2, 0)]
+        items = cand[:12]
+        if not items:
+            return False
+        from tests import denial_checker as D
+        ck = R.Checker(self.schema, self.rels_with_expiry(), self.now())
+        # (the brute force over every relationship of the OBJECTS some item's Check looks at -- tests/denial_checker.py closure(), the items are monotone: a
+        # relationship of an object no Check reaches cannot change an answer; on the cyclic graphs the C oracle needs a millisecond per denied Check)
+        objects = set()
+        for q in items:
+            objects |= {s[:2] for s in D.closure(ck.orcs.defs, ck.orcs.rels, q[:3], self.now())}
+        want = ck.brute(items, only=[r for r in ck.orcs.rels if r[:2] in objects])
+        ck._cuts.update(want)
+        assert list(want) == items, f"step {step} (Explain revoke): the checker's oracles grant {len(want)} of {len(items)} items the stream's oracle grants"
+        st_["revoke_items"] += len(items)
+        st_["revoke_with_cuts"] += sum(bool(c) for c in want.values())
+        st_["revoke_cuts"] += sum(len(c) for c in want.values())
+        if e is None:
+            return True
+        perm, err, flags, off, raw = e.explain_revoke_ids(self.items(items))
+        for i, q in enumerate(items):
+            where = f"step {step} (Explain revoke) {q} (item {i})"
+            assert (int(perm[i]), int(err[i]), int(flags[i])) == (2, 0, aclgpu.EXPLAIN_REVOKE), f"{where}: engine {(int(perm[i]), int(err[i]), int(flags[i]))}, the oracles grant it"
+            cuts = self.hop_names(raw[off[i]:off[i + 1]])
+            assert len(set(cuts)) == len(cuts) and set(cuts) == want[q], f"{where}: engine only {sorted(set(cuts) - want[q])[:3]}, brute force only {sorted(want[q] - set(cuts))[:3]}"
+            try:
+                ck.check(q, cuts)
+            except AssertionError as x:
+                raise AssertionError(f"{where}: {x}") from None
+        return True
+
+    # ---- h. watch sets (expiring runs)
+    NOBODY = "nobody-names-this-subject"
+
+    def watch_rows(self):
+        """the oracle's rows of both sets now: {user: pods} by LookupResources (None: a lookup fails), {pod: users, `*` among them} by Check per subject"""
+        w = self.watch
+        res = {}
+        for u in w["users"]:
+            out = self.lookup_expected("pod", "view", "user", u)
+            if out[0] == "err":
+                return None, None
+            res[u] = out[1]
+        users = self.names_of("user")
+        sub = {}
+        for p in w["pods"]:
+            row = {u for u in users if tuple(self.o.check("pod", p, "view", "user", u)) == (2, 0)}
+            if tuple(self.o.check("pod", p, "view", "user", self.NOBODY)) == (2, 0):
+                row.add("*")
+            sub[p] = row
+        return res, sub
+
+    def round_watch(self, step):
+        """One resource-direction set (4 users) and one subject-direction set (4 pods) on pod#view, opened at the first round and polled at every later one: the
+        records are the difference of the oracle's rows since the last poll (tests/watch_records.py) -- behind writes, and behind clock moves with no write."""
+        import aclgpu
+        from tests.watch_records import expected_records, records_of
+        rr, e, st_ = self.rr, self.e, self.stats
+        if self.watch is None:
+            users, pods = rr.sample(self.names[0], 4), rr.sample(self.resources_with_relationships("pod"), 4)
+            self.watch = w = dict(users=users, pods=pods, res=None, sub=None)
+            if e is not None:
+                w["res"], w["sub"] = e.watch_set("pod", "view", "user"), e.subject_watch_set("pod", "view", "user")
+                w["wres"], w["wsub"] = [w["res"].add(u) for u in users], [w["sub"].add(p) for p in pods]  # (the watchers' ids, in the order of the names)
+            w["held_res"], w["held_sub"] = {k: set() for k in w.get("wres", range(4))}, {k: set() for k in w.get("wsub", range(4))}  # (the empty rows of the adds)
+        w = self.watch
+        res, sub = self.watch_rows()
+        if res is None:
+            return False
+        wres, wsub = w.get("wres", range(4)), w.get("wsub", range(4))
+        after_res, after_sub = {wres[k]: res[u] for k, u in enumerate(w["users"])}, {wsub[k]: sub[p] for k, p in enumerate(w["pods"])}
+        behind_clock = self.clock is not None and self.clock.moved_last
+        for d, held, after in (("res", w["held_res"], after_res), ("sub", w["held_sub"], after_sub)):
+            lost = sum(len(held[k] - after[k]) for k in after)
+            st_["watch_changes_" + d] += lost + sum(len(after[k] - held[k]) for k in after)
+            st_["watch_loss_behind_clock_" + d] += bool(lost) and behind_clock
+        st_["watch_polls"] += 1
+        if e is not None:
+            where = f"step {step} (watch sets{', behind a clock move' if behind_clock else ''})"
+            wid = e.find("user", "*")
+            want = expected_records(w["held_res"], after_res, lambda n: e.intern("pod", n))
+            got = records_of(w["res"].poll()[1])
+            assert got == want, f"{where}: resource direction: engine only {sorted(set(got) - set(want))[:4]}, oracle only {sorted(set(want) - set(got))[:4]}"
+            want = expected_records(w["held_sub"], after_sub, lambda n: wid if n == "*" else e.intern("user", n), lambda i: aclgpu.WATCH_CHANGE_WILDCARD if i == wid else 0)
+            got = records_of(w["sub"].poll()[1], reserved=True)
+            assert got == want, f"{where}: subject direction: engine only {sorted(set(got) - set(want))[:4]}, oracle only {sorted(set(want) - set(got))[:4]}"
+        w["held_res"], w["held_sub"] = after_res, after_sub
         return True
 
     # ---- e. multi-target LookupResources
@@ -756,7 +1106,8 @@ class _Reads:
             keys = [("user", "", u) for u in rr.sample(users, 3)] + ([("group", "member", g) for g in rr.sample(groups, 2)] if kind == "mixed" else [])
             w = [self.lookup_expected(rt, perm, s, n, r) for s, r, n in keys]
             want, flags = (None if any(x[0] == "err" for x in w) else [x[1] for x in w]), [False] * len(keys)
-        held = dict(kind=kind, row_type=st if kind == "subjects" else rt, want=want, version=self.version, reads=0, cur=None, ids=None, names=None, flags=flags)
+        held = dict(kind=kind, row_type=st if kind == "subjects" else rt, want=want, version=self.version, clock=self.clock_moves, reads=0, cur=None, ids=None, names=None,
+                    flags=flags)
         if e is None:
             return held if want is not None else None
         try:
@@ -784,10 +1135,11 @@ class _Reads:
         return held
 
     def cursor_read(self, step, h):
-        """a cursor opened before at least one accepted write: its rows are what they were"""
+        """a cursor opened before at least one accepted write or clock move: its rows are what they were"""
         import aclgpu
         st_ = self.stats
         st_["cursors_read_later"] += 1
+        st_["cursors_read_after_clock_move"] += self.clock_moves > h["clock"]
         h["reads"] += 1
         if self.e is None:
             return
@@ -829,7 +1181,7 @@ class _Reads:
 
     def round_cursors(self, step):
         rr, st_ = self.rr, self.stats
-        old = [h for h in self.cursors if h["version"] < self.version]
+        old = [h for h in self.cursors if h["version"] < self.version or h["clock"] < self.clock_moves]
         if old:
             for h in old:
                 self.cursor_read(step, h)
@@ -840,7 +1192,7 @@ class _Reads:
                 if h["reads"] >= 3 and (h["reads"] >= 6 or rr.random() < 0.3):
                     if h["cur"] is not None:
                         h["cur"].close()
-                    self.cursors.remove(h)
+                    self.cursors[:] = [c for c in self.cursors if c is not h]  # (by identity: a pair's dicts refer to each other)
                     st_["cursors_closed"] += 1
             return True
         if len(self.cursors) >= 3:
@@ -860,17 +1212,19 @@ class _Reads:
 
 
 def run_reads(seed: int, steps: int, schema: str = "c4", acyclic: bool = False, recycle: bool = False, compact_early: bool = False, universe: int = 1, engine: bool = True,
-              verbose: bool = True, depth_case: bool = False, read_share: float = 0.75) -> dict:
+              verbose: bool = True, depth_case: bool = False, read_share: float = 0.75, expiring: bool = False, probe: int = 200) -> dict:
     """The read paths the Check campaign does not reach, on the same kind of live graph: between run()'s writes (TOUCH / CREATE / DELETE batches, filter
     deletes) a step is, with probability `read_share`, one read round -- LookupSubjects, Explain witness, Explain proof (combine schema), Explain denial,
-    multi-target LookupResources with access_review, or cursors held open across the writes (paged, named, derived, counted) -- each held to the oracles.
+    Explain for revocation, multi-target LookupResources with access_review, or cursors held open across the writes (paged, named, derived, counted) -- each
+    held to the oracles.  expiring: the schema's expiring variant under a Clock -- one step in four moves the clock instead of writing (the probe batch around it),
+    every round kind runs against the oracle at the current clock, the checkers replay with the hops' expiries, cursors are read across clock moves, and a
+    `watch` round polls a resource-direction and a subject-direction watch set against the difference of the oracle's rows.
     engine=False: the oracle's half alone, same stream, same expected values, no GPU: what a case costs on the oracle side and whether its stream covers what
     it is for.  depth_case: kinds a and e only, one LookupSubjects target a round and three in all (a cyclic combine graph: the Python oracle needs over a second
     per target there), picked by turns with and without a Check that ends at the depth limit.  -> stats."""
-    from aclgpu import workloads
     from oracle import orc
     combine = schema == "combine"
-    schema_text = SCHEMA_COMBINE if combine else workloads.SCHEMA_C4
+    schema_text = schema_text_of(schema, expiring)
     rng = random.Random(seed)
     rr = random.Random(f"reads/{seed}")  # (the write stream's generator is never drawn from by a read)
     names = make_universe(rng, universe)
@@ -878,22 +1232,35 @@ def run_reads(seed: int, steps: int, schema: str = "c4", acyclic: bool = False, 
     e = open_engine(schema_text, recycle, compact_early) if engine else None
     o = orc.Oracle(schema_text)
     live = set()
-    load_initial(rand_tuple, o, e, live, universe)
     stats = {k: 0 for k in ("writes", "write_errors", "filter_deletes", "writes_accepted", "rounds", "skipped", "subj_rows", "subj_nonempty", "subj_empty", "subj_depth",
                             "subj_wildcard", "subj_interned_only", "subj_first_seen", "explain_items", "witnesses", "replayed", "proof_items", "proofs", "denied_items",
                             "denied_with_grants", "multi_rows", "multi_failing_targets", "cursors_opened", "cursors_read_later", "cursors_read_after_compaction",
-                            "cursors_read_after_recycling", "page_names_refused", "cursors_closed", "derives")}
-    reads = _Reads(rr, names, schema_text, combine, recycle, o, e, live, stats, depth_case, not acyclic)
-    kinds = ["subjects", "multi"] if depth_case else ["subjects", "explain", "explain", "denial", "multi", "cursors", "cursors"] + (["proof"] if combine else [])
+                            "cursors_read_after_recycling", "page_names_refused", "cursors_closed", "derives", "cursors_read_after_clock_move", "revoke_items",
+                            "revoke_with_cuts", "revoke_cuts", "watch_polls", "watch_changes_res", "watch_changes_sub", "watch_loss_behind_clock_res",
+                            "watch_loss_behind_clock_sub")}
+    clock = Clock(rng, seed, names, combine, o, [e], stats, probe) if expiring else None
+    load_initial(rand_tuple, o, e, live, universe, clock)
+    reads = _Reads(rr, names, schema_text, combine, recycle, o, e, live, stats, depth_case, not acyclic, clock)
+    kinds = ["subjects", "multi"] if depth_case else ["subjects", "explain", "explain", "denial", "multi", "cursors", "cursors", "revoke"] + (["proof"] if combine else []) + \
+        (["watch"] if expiring else [])
+
+    def probe_check(qs, want, where):
+        perms, errs = e.check_bulk(qs)
+        for i, q in enumerate(qs):
+            assert (perms[i], errs[i]) == want[i], f"{where}: probe check {q} (item {i}): engine {(perms[i], errs[i])}, oracle {want[i]}"
     for k in dict.fromkeys(kinds):
         stats["rounds_" + k], stats["seconds_" + k] = 0, 0.0
     todo = []
     t0 = time.time()
     for step in range(steps):
-        if rng.random() < 0.9:
-            accepted = write_batch(rng, step, rand_tuple, o, e, live, 25, stats)
+        if clock is not None and rng.random() < 0.25:  # (no write: the read round behind it sees the relationships whose liveness changed)
+            clock.move(step, live, probe_check if e is not None else None)
+            reads.clock_moves += 1
+            accepted = False
+        elif rng.random() < 0.9:
+            accepted = write_batch(rng, step, rand_tuple, o, e, live, 25, stats, clock)
         else:
-            accepted = filter_delete(rng, step, names, combine, o, e, live, stats) > 0
+            accepted = filter_delete(rng, step, names, combine, o, e, live, stats, clock) > 0
         if accepted:
             reads.version += 1
             stats["writes_accepted"] += 1
@@ -901,7 +1268,8 @@ def run_reads(seed: int, steps: int, schema: str = "c4", acyclic: bool = False, 
             if not todo:  # every enabled kind once (cursors twice) in a shuffled order, then again
                 # (the kinds whose oracle side is dear -- LookupSubjects, denial, multi-target lookups outside the depth case -- run four rounds, then the cheap ones go on)
                 todo = [k for k in kinds if not (k == "subjects" and depth_case and reads.subject_targets >= 3) and
-                        not (k in ("subjects", "denial", "multi") and not depth_case and stats["rounds_" + k] >= 4)]
+                        not (k in ("subjects", "denial", "multi", "revoke") and not depth_case and stats["rounds_" + k] >= 4) and
+                        not (k == "watch" and stats["rounds_watch"] >= 9)]  # (the first watch round opens the sets, eight polls follow)
                 rr.shuffle(todo)
             kind = todo.pop()
             reads.round_no += 1
@@ -918,18 +1286,25 @@ def run_reads(seed: int, steps: int, schema: str = "c4", acyclic: bool = False, 
     stats["cursors_left_open"] = len(reads.cursors)
     stats["seconds"] = round(time.time() - t0, 1)
     if e is not None:
+        if reads.watch is not None:
+            reads.watch["res"].close()
+            reads.watch["sub"].close()
         st = e.stats()
         stats.update({k: int(st[k]) for k in ("snapshot_builds", "snapshot_patches", "snapshot_compactions", "ids_recycled", "rev_multi_passes") if k in st})
         e.close()  # (with the cursors still held: the engine closes them)
     return stats
 
 
-def run_patcher(seed: int, steps: int, universe: int = 1, burst: int = 25, shard=None, schema: str = "c4") -> dict:
+def run_patcher(seed: int, steps: int, universe: int = 1, burst: int = 25, shard=None, schema: str = "c4", expiring: bool = False) -> dict:
     """No GPU: the same kind of write stream on a STORE-ONLY engine, and after every write the host snapshot is brought up to date the way a read
     would (patched in place, or rebuilt) and verified against the store (acl_selfcheck_snapshot: every relationship findable by the kernels'
-    search, nothing dead left, rows sorted, no unsound leaf flag).  -> how often it was patched (1), rebuilt (0) or current (2)."""
+    search, nothing dead left, rows sorted, no unsound leaf flag).  -> how often it was patched (1), rebuilt (0) or current (2).
+    expiring: the schema's expiring variant under a Clock -- two TOUCHes in five carry an expiry, one step in four moves the clock instead of writing, and after
+    every step ReadRelationships of the store equals the C oracle's; "rebuilt_outside_adoption": rebuilds at a step that adopted no background build,
+    "dropped_after_expiry" / "adopted_after_expiry": background builds dropped / adopted with an expiry passed (by the oracle's read difference) between their
+    two halves -- the hook's second half replays the crossings onto the build with the patcher and verifies the adopted snapshot against the store."""
     import aclgpu
-    from aclgpu import workloads
+    from oracle import orc
 
     rng = random.Random(seed)
     users = [f"u{i}" for i in range(160 * universe)]
@@ -946,40 +1321,81 @@ def run_patcher(seed: int, steps: int, universe: int = 1, burst: int = 25, shard
                    lambda: f"namespace:{rng.choice(nss)}#viewer@user:*", lambda: f"pod:{rng.choice(pods)}#viewer@group:{rng.choice(groups)}#active",
                    lambda: f"pod:{rng.choice(pods)}#auditor@group:{rng.choice(groups)}#member", lambda: f"pod:{rng.choice(pods)}#banned@user:*",
                    lambda: f"pod:{rng.choice(pods)}#banned@user:{rng.choice(users)}", lambda: f"pod:{rng.choice(pods)}#auditor@user:{rng.choice(users)}"]
-    e = aclgpu.Engine(SCHEMA_COMBINE if schema == "combine" else workloads.SCHEMA_C4, store_only=True)
+    e = aclgpu.Engine(schema_text_of(schema, expiring), store_only=True)
+    codes = {0: 0, 1: 0, 2: 0, "adopted": 0, "dropped": 0}
+    o = clock = None
+    if expiring:
+        o = orc.Oracle(schema_text_of(schema, True))
+        codes.update(rebuilt_outside_adoption=0, dropped_after_expiry=0, adopted_after_expiry=0)
+        clock = Clock(rng, seed, (users, groups, nss, pods), schema == "combine", o, [e], codes, probe=40)
+
+    def expires(t):  # -> () or (expiry,)
+        at = clock.expiry_for(t, refusable=False) if clock is not None else 0
+        return (at,) if at else ()
+
+    def same_read(where):
+        a, b = sorted(x for t in ("group", "namespace", "pod") for x in e.read(rtype=t)), sorted(x for t in ("group", "namespace", "pod") for x in o.read(rtype=t))
+        assert a == b, f"{where}: ReadRelationships differs: {sorted(set(a) ^ set(b))[:6]}"
+
     if shard:  # (rank, world): the snapshot of ONE shard of the type-hash layout -- it holds, and patches, only the rows of the types it owns
         e._check(e._L.acl_shard_configure(e._h, shard[0], shard[1]))
     live = set(dict.fromkeys(rng.choice(shapes)() for _ in range(2500 * universe)))
     init = sorted(live)
     for i in range(0, len(init), 500):
-        e.write([(aclgpu.OP_TOUCH, t) for t in init[i:i + 500]])
+        ups = [(aclgpu.OP_TOUCH, t) + expires(t) for t in init[i:i + 500]]
+        e.write(ups)
+        if o is not None:
+            o.write(ups)  # (the two sides' op codes are the same numbers)
+    assert (aclgpu.OP_TOUCH, aclgpu.OP_DELETE) == (orc.OP_TOUCH, orc.OP_DELETE)
     e.selfcheck_snapshot_code()
-    codes = {0: 0, 1: 0, 2: 0, "adopted": 0, "dropped": 0}
     pending_build = None
-    for _ in range(steps):
-        if rng.random() < 0.9:
+    expired_since_build = False
+    for step in range(steps):
+        adopted_here = False
+        if clock is not None and rng.random() < 0.25:
+            gone = clock.move(step, live)[1]
+            expired_since_build = expired_since_build or bool(gone)
+        elif rng.random() < 0.9:
             pool = sorted(live)
             ups = {}
             for _u in range(rng.randrange(1, burst)):
                 t = rng.choice(shapes)() if rng.random() < 0.55 or not pool else rng.choice(pool)
-                ups[t] = (aclgpu.OP_TOUCH if t not in live or rng.random() < 0.3 else aclgpu.OP_DELETE, t)
+                op = aclgpu.OP_TOUCH if t not in live or rng.random() < 0.3 else aclgpu.OP_DELETE
+                ups[t] = (op, t) + (expires(t) if op == aclgpu.OP_TOUCH else ())
             e.write(list(ups.values()))
-            for op, t in ups.values():
+            if o is not None:
+                o.write(list(ups.values()))
+                clock.accepted(list(ups.values()), aclgpu.OP_DELETE)
+            for op, t, *_ in ups.values():
                 (live.discard if op == aclgpu.OP_DELETE else live.add)(t)
         else:
-            e.delete_by_filter(**rng.choice([dict(rtype="pod", rid=rng.choice(pods)), dict(rtype="group", rel="member", stype="user", sid=rng.choice(users))]))
+            f = rng.choice([dict(rtype="pod", rid=rng.choice(pods)), dict(rtype="group", rel="member", stype="user", sid=rng.choice(users))])
+            n = e.delete_by_filter(**f)
+            if o is not None:
+                assert o.delete_by_filter(**f) == n, f"step {step}: delete_by_filter {f}"
+                clock.filtered(f)
             live = set(f"{a}:{b}#{c}@{d}:{x}" + (f"#{y}" if y else "") for t in ("group", "namespace", "pod") for a, b, c, d, x, y, *_ in e.read(rtype=t))
-        codes[e.selfcheck_snapshot_code()] += 1  # (raises when the snapshot does not describe the store)
+        code = e.selfcheck_snapshot_code()  # (raises when the snapshot does not describe the store)
+        codes[code] += 1
+        if o is not None:
+            same_read(f"step {step} (now {clock.now})")
         # a background compaction's two halves around the writes in between: build from a copy-on-write view now, adopt it some writes later
-        if pending_build is None and rng.random() < 0.02:
+        if pending_build is None and rng.random() < (0.06 if expiring else 0.02):
             e.selfcheck_compaction(0)
-            pending_build = rng.randrange(0, 30)
+            pending_build = rng.randrange(0, 8 if expiring else 30)
+            expired_since_build = False
         elif pending_build is not None:
             if pending_build == 0:
-                codes["adopted" if e.selfcheck_compaction(1) else "dropped"] += 1  # (phase 1 verifies the adopted snapshot against the store)
+                adopted_here = bool(e.selfcheck_compaction(1))  # (phase 1 verifies the adopted snapshot against the store)
+                codes["adopted" if adopted_here else "dropped"] += 1
+                if expiring:
+                    codes["dropped_after_expiry"] += not adopted_here and expired_since_build
+                    codes["adopted_after_expiry"] += adopted_here and expired_since_build
                 pending_build = None
             else:
                 pending_build -= 1
+        if expiring:
+            codes["rebuilt_outside_adoption"] += code == 0
     e.close()
     return codes
 
@@ -1044,19 +1460,19 @@ SHARD_CHECK_SIZES = (1, 7, 64, 900, 3000)
 
 
 def sharded_script(seed: int, steps: int, schema: str = "c4", acyclic: bool = False, recycle: bool = False, universe: int = 1, depth_case: bool = False,
-                   read_share: float = 0.75, verbose: bool = False) -> dict:
+                   read_share: float = 0.75, verbose: bool = False, expiring: bool = False, probe: int = 200) -> dict:
     """Phase 1 of run_sharded (no GPU, no engine): one pass over run_reads' kind of stream with the oracles alone -> the ordered script every rank replays.
     script["init"]: the starting graph's write steps; script["steps"]: in order
       ("write", step, updates, the oracle's outcome code or None) | ("filter", step, filter, removed)
-      ("check", step, [item], [(permissionship, error)])
+      ("clock", step, now) -- an expiring script (script["now0"]: the clock every rank starts at): every rank sets its own engine's clock before the next read
+      ("check", step, [item], [(permissionship, error)]) -- with a fifth field "probe": the Clock's probe batch, answered right behind a clock step
       ("lookup", step, rtype, permission, [user], [("ok", names) | ("err", code)], [follow-up]) -- a follow-up is ("check", items, want) or ("lookup", [user], [outcome]):
           asked behind a call that must fail, the next call on that engine has to answer
       ("subjects", step, [(rtype, permission, stype, srel, [resource], [(ids, wildcard, excluded) | "DEPTH"])])
     and script["stats"], what the stream covers.  Every draw of a read comes from a generator of its own: the write stream is run_reads' for the same seed."""
-    from aclgpu import workloads
     from oracle import orc
     combine = schema == "combine"
-    schema_text = SCHEMA_COMBINE if combine else workloads.SCHEMA_C4
+    schema_text = schema_text_of(schema, expiring)
     rng = random.Random(seed)
     rr = random.Random(f"sharded/{seed}")
     names = make_universe(rng, universe)
@@ -1066,13 +1482,15 @@ def sharded_script(seed: int, steps: int, schema: str = "c4", acyclic: bool = Fa
     init, script = [], []
     rec = _TapEngine(o, init)
     live = set()
-    load_initial(rand_tuple, o, rec, live, universe)
-    rec.sink = script
     stats = {k: 0 for k in ("writes", "write_errors", "filter_deletes", "writes_accepted", "writes_read_before_next", "rounds", "skipped", "rounds_check", "rounds_lookup",
                             "rounds_subjects", "check_items", "check_depth_items", "check_has_items", "check_first_seen_items", "check_outruns_expected", "lookup_rows", "lookup_calls",
                             "lookup_calls_failed", "lookup_rows_nonempty", "subj_rows", "subj_nonempty", "subj_empty", "subj_depth", "subj_wildcard", "subj_interned_only",
-                            "subj_first_seen", "subj_no_relationships", "subj_calls", "subj_calls_failed", "subj_calls_answered", "subj_answered_over_arrow", "subj_wildcard_excluded")}
-    reads = _ScriptReads(rr, names, schema_text, combine, recycle, o, None, live, stats, depth_case, not acyclic)
+                            "subj_first_seen", "subj_no_relationships", "subj_calls", "subj_calls_failed", "subj_calls_answered", "subj_answered_over_arrow", "subj_wildcard_excluded",
+                            "reads_behind_clock_check", "reads_behind_clock_lookup", "reads_behind_clock_subjects")}
+    clock = Clock(rng, seed, names, combine, o, [], stats, probe) if expiring else None
+    load_initial(rand_tuple, o, rec, live, universe, clock)
+    rec.sink = script
+    reads = _ScriptReads(rr, names, schema_text, combine, recycle, o, None, live, stats, depth_case, not acyclic, clock)
     lookup_perms = [("pod", "view"), ("namespace", "view"), ("group", "member")] + \
         ([("pod", "audit"), ("pod", "edit"), ("pod", "hidden"), ("group", "active"), ("pod", "everywhere"), ("pod", "vetted")] if combine else [])
     subject_rounds = 3 if depth_case else 4 if combine else 6  # (the contract's Python oracles are what a combine case costs: run_reads' budget; C4: 5, 1, 33 resources twice)
@@ -1093,10 +1511,16 @@ def sharded_script(seed: int, steps: int, schema: str = "c4", acyclic: bool = Fa
 
     for step in range(steps):
         rec.step = step
-        if rng.random() < 0.9:
-            accepted = write_batch(rng, step, rand_tuple, o, rec, live, 25, stats)
+        if clock is not None and rng.random() < 0.25:  # (every rank sets its engine's clock; the probe batch is a Check step of the script)
+            _d, _gone, want = clock.move(step, live)
+            reads.clock_moves += 1
+            script.append(("clock", step, clock.now))
+            script.append(("check", step, list(clock.probe), want, "probe"))
+            accepted = False
+        elif rng.random() < 0.9:
+            accepted = write_batch(rng, step, rand_tuple, o, rec, live, 25, stats, clock)
         else:
-            accepted = filter_delete(rng, step, names, combine, o, rec, live, stats) > 0
+            accepted = filter_delete(rng, step, names, combine, o, rec, live, stats, clock) > 0
         if accepted:
             reads.version += 1
             stats["writes_accepted"] += 1
@@ -1162,6 +1586,8 @@ def sharded_script(seed: int, steps: int, schema: str = "c4", acyclic: bool = Fa
             stats["rounds"] += 1
             stats["rounds_" + kind] += bool(done)
             stats["skipped"] += not done
+            if done and clock is not None and clock.moved_last:  # (a read round behind a clock move with no accepted write in between)
+                stats["reads_behind_clock_" + kind] += 1
             if done and unread_write:
                 stats["writes_read_before_next"] += 1
                 unread_write = False
@@ -1170,7 +1596,7 @@ def sharded_script(seed: int, steps: int, schema: str = "c4", acyclic: bool = Fa
         if verbose and step % 10 == 9:
             print(f"step {step + 1}/{steps}: {stats}, {len(live)} relationships, {time.time() - t0:.1f} s", file=sys.stderr, flush=True)
     stats["seconds_script"] = round(time.time() - t0, 1)
-    return dict(schema_text=schema_text, combine=combine, init=init, steps=script, stats=stats)
+    return dict(schema_text=schema_text, combine=combine, init=init, steps=script, stats=stats, now0=CLOCK_START if expiring else None)
 
 
 def step_names(st):
@@ -1202,6 +1628,8 @@ def sharded_dry_engines(script, world: int, recycle: bool, compact_early: bool) 
         e = open_engine(script["schema_text"], recycle, False, store_only=True)
         try:
             e._check(e._L.acl_shard_configure(e._h, rank, world))
+            if script.get("now0"):
+                e.set_now(script["now0"])
             for st in script["init"]:
                 e.write(st[2])
             e.selfcheck_snapshot_code()  # (the first build is not counted)
@@ -1224,6 +1652,9 @@ def sharded_dry_engines(script, world: int, recycle: bool, compact_early: bool) 
                             pending = None
                         else:
                             pending -= 1
+                elif st[0] == "clock":  # (the rank's patched snapshot is verified behind the move itself, and again at the read step that follows)
+                    e.set_now(st[2])
+                    codes[e.selfcheck_snapshot_code()] += 1
                 else:
                     for t, n in dict.fromkeys(step_names(st)):
                         e.intern(t, n)
@@ -1262,6 +1693,7 @@ def sharded_replay(script, host_driven: bool):
     def replay(se):
         e, rank = se.shard.e, se.shard.rank
         bad, calls, digests, refusals = [], [], [], []
+        behind_clock = [False]  # a clock move and no accepted write since: the calls noted meanwhile carry it
         tid = {t: e.type_id(t) for t in ("user", "group", "namespace", "pod")}
         rel = {}
 
@@ -1277,7 +1709,7 @@ def sharded_replay(script, host_driven: bool):
             return out
 
         def note(step, kind, follows_write, s):
-            calls.append((step, kind, follows_write, s["levels"], s["retries"], s["entries_exchanged"], s["host_syncs"], s["export_capacity"]))
+            calls.append((step, kind, follows_write, s["levels"], s["retries"], s["entries_exchanged"], s["host_syncs"], s["export_capacity"], behind_clock[0]))
 
         def check(step, qs, want, ids, follows_write, kind="check"):
             items = items_of(qs, ids)
@@ -1356,6 +1788,8 @@ def sharded_replay(script, host_driven: bool):
                     if gex != wex:
                         bad.append((step, rank, "subjects excluded", (rt, r, pm, s_t, srel), sorted(gex ^ wex)[:5], "(symmetric difference)"))
 
+        if script.get("now0"):
+            e.set_now(script["now0"])
         for st in script["init"]:
             e.write(st[2])
         follows_write = False  # (the first read follows the starting graph's load: a built snapshot, not a patched one)
@@ -1364,7 +1798,13 @@ def sharded_replay(script, host_driven: bool):
                 d = sharded_apply_write(e, st)
                 if d is not None:
                     bad.append((st[1], rank, st[0]) + d)
-                follows_write = follows_write or (st[3] is None if st[0] == "write" else st[3] > 0)
+                accepted = st[3] is None if st[0] == "write" else st[3] > 0
+                follows_write = follows_write or accepted
+                behind_clock[0] = behind_clock[0] and not accepted
+                continue
+            if st[0] == "clock":  # (no write: the next read of this rank patches every relationship whose liveness changed)
+                e.set_now(st[2])
+                behind_clock[0] = True
                 continue
             ids = {}
             for k in step_names(st):
@@ -1384,6 +1824,8 @@ def sharded_replay(script, host_driven: bool):
                 for req in st[2]:
                     subjects(st[1], req, ids, follows_write)
             follows_write = False
+            if not (st[0] == "check" and len(st) > 4):  # (the probe batch behind a move leaves the mark for the step's own read round)
+                behind_clock[0] = False
         est = e.stats()
         return dict(rank=rank, bad=bad, calls=calls, digests=digests, refusals=refusals, owns=[t for t in ("group", "namespace", "pod") if se.shard.owner_of_type(t) == rank],
                     **{k: int(est[k]) for k in ("snapshot_builds", "snapshot_patches", "snapshot_compactions", "ids_recycled", "overflow_retries") if k in est})
@@ -1392,7 +1834,8 @@ def sharded_replay(script, host_driven: bool):
 
 
 def run_sharded(seed: int, steps: int, world: int, schema: str = "c4", acyclic: bool = False, recycle: bool = False, compact_early: bool = False, universe: int = 1,
-                engine: bool = True, verbose: bool = True, depth_case: bool = False, read_share: float = 0.75, exchange: str = "allgather", xcap: int = 0) -> dict:
+                engine: bool = True, verbose: bool = True, depth_case: bool = False, read_share: float = 0.75, exchange: str = "allgather", xcap: int = 0,
+                expiring: bool = False, probe: int = 200) -> dict:
     """The read campaign's kind of write stream under the loops of the type-hash sharded graph.  Phase 1 (sharded_script) computes, with the oracles alone, the script
     of writes and reads with their expected outcomes; phase 2 replays it on `world` logical shards of one GPU (sharded.run_logical_shards: one Engine per rank, a
     replicated store, one thread each), every rank holding every answer to the script by name:
@@ -1403,7 +1846,7 @@ def run_sharded(seed: int, steps: int, world: int, schema: str = "c4", acyclic: 
     The host-driven protocol refuses schemas with `-` / `&` / .all() (ShardCall::begin): there the native loops alone answer and the refusal's code is recorded once.
     engine=False: phase 1, and the script's writes on one store-only engine per rank whose patched host snapshot is verified against the store at every read step.
     xcap: ACL_SHARD_XCAP around the replay (a first export block of that many entries: grow-and-redo).  -> stats; raises AssertionError on the first record."""
-    script = sharded_script(seed, steps, schema, acyclic, recycle, universe, depth_case, read_share, verbose)
+    script = sharded_script(seed, steps, schema, acyclic, recycle, universe, depth_case, read_share, verbose, expiring, probe)
     stats = script["stats"]
     t0 = time.time()
     if not engine:
@@ -1441,7 +1884,7 @@ def run_sharded(seed: int, steps: int, world: int, schema: str = "c4", acyclic: 
         if d is not None:
             bad.append((f"read step {d}", out["rank"], "interned ids differ from rank 0's", None, out["digests"][d], outs[0]["digests"][d]))
     stats["ranks"] = [{k: v for k, v in out.items() if k not in ("bad", "calls", "digests")} for out in outs]
-    stats["calls"] = outs[0]["calls"]  # (step, kind, follows a write, levels, retries, entries_exchanged, host_syncs, export_capacity) of rank 0's native calls
+    stats["calls"] = outs[0]["calls"]  # (step, kind, follows a write, levels, retries, entries_exchanged, host_syncs, export_capacity, behind a clock move) of rank 0's native calls
     stats["calls_equal_on_every_rank"] = all([c[:5] + c[7:] for c in out["calls"]] == [c[:5] + c[7:] for c in outs[0]["calls"]] for out in outs)
     if bad:
         bad.sort(key=lambda b: (b[0] if isinstance(b[0], int) else 1 << 30, b[1]))
@@ -1567,6 +2010,7 @@ if __name__ == "__main__":
     ap.add_argument("--schema", choices=["c4", "combine"], default="c4", help="combine: the C4 schema with exclusions, intersections, wildcards and a non-monotone userset subject")
     ap.add_argument("--recycle", action="store_true", help="ACL_ID_QUARANTINE_MS=0 and a stream of never-seen object names in the writes: ids of objects that lost their last relationship are taken over under the reads")
     ap.add_argument("--acyclic", action="store_true", help="group nesting without cycles: one-user CheckBulkPermissions calls take the reverse walk once the depth sweep has run")
+    ap.add_argument("--expiring", action="store_true", help="the schema with `with expiration` on its relations (SCHEMA_C4_EXPIRING / SCHEMA_COMBINE_EXPIRING), writes with an expiry and a clock that moves forwards and back between the writes; with --reads, --patcher, --sharded W and --dry too")
     ap.add_argument("--reads", action="store_true", help="the read campaign (run_reads): LookupSubjects, Explain witness / proof / denial, multi-target lookups and cursors held across the writes")
     ap.add_argument("--dry", action="store_true", help="with --reads: the oracle's half alone, no engine and no GPU")
     ap.add_argument("--depth-case", action="store_true", help="with --reads: LookupSubjects and multi-target lookups only, four LookupSubjects targets in all (cyclic combine graphs)")
@@ -1578,11 +2022,12 @@ if __name__ == "__main__":
     a = ap.parse_args()
     try:
         print(run_sharded(a.seed, a.steps, a.sharded, schema=a.schema, acyclic=a.acyclic, recycle=a.recycle, compact_early=a.compact_early, universe=a.universe,
-                          engine=not a.dry, depth_case=a.depth_case, read_share=a.read_share, exchange=a.exchange, xcap=a.xcap) if a.sharded
-              else run_patcher(a.seed, a.steps, a.universe, a.burst, schema=a.schema) if a.patcher else run_expiry(a.seed, a.steps) if a.expiry
+                          engine=not a.dry, depth_case=a.depth_case, read_share=a.read_share, exchange=a.exchange, xcap=a.xcap, expiring=a.expiring) if a.sharded
+              else run_patcher(a.seed, a.steps, a.universe, a.burst, schema=a.schema, expiring=a.expiring) if a.patcher else run_expiry(a.seed, a.steps) if a.expiry
               else run_reads(a.seed, a.steps, schema=a.schema, acyclic=a.acyclic, recycle=a.recycle, compact_early=a.compact_early, universe=a.universe, engine=not a.dry,
-                             depth_case=a.depth_case) if a.reads
-              else run(a.seed, a.steps, burst=a.burst, universe=a.universe, compact_early=a.compact_early, schema=a.schema, recycle=a.recycle, acyclic=a.acyclic))
+                             depth_case=a.depth_case, expiring=a.expiring) if a.reads
+              else run(a.seed, a.steps, burst=a.burst, universe=a.universe, compact_early=a.compact_early, schema=a.schema, recycle=a.recycle, acyclic=a.acyclic,
+                       expiring=a.expiring, engine=not a.dry))
     except AssertionError as x:
         print("MISMATCH:", x)
         sys.exit(1)

@@ -643,7 +643,7 @@ int acl_selfcheck_compaction(acl_engine_t *h, int phase, int *adopted_out) {
     if (phase == 0) {
         const auto tv0 = std::chrono::steady_clock::now();
         Store view = h->store.view(now);
-        if (getenv("ACL_DEBUG_REBUILD"))
+        if (debug_rebuild())
             fprintf(stderr, "[aclgpu] view() took %.3f ms with %zu expiring relationships\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tv0).count(),
                     h->store.expiring_relationships());
         c->shard = h->shard;

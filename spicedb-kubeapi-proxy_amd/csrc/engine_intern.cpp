@@ -237,9 +237,8 @@ void intern_items(acl_engine_t *h, const Items &its, size_t n, acl_item_t *out, 
                 }
                 p.rt = m.rti; p.st = m.sti; p.pm = m.pmi; p.sr = m.sri;
                 const Pending *prev = i > g0 && pend[i - g0 - 1].ok ? &pend[i - g0 - 1] : (i == g0 && have_last ? &last : nullptr);
-                static const bool kRepeat = !getenv("ACL_INTERN_REPEAT") || atoi(getenv("ACL_INTERN_REPEAT")) != 0;  // (A/B knob)
-                p.same_res = kRepeat && prev && prev->rt == p.rt && same_name(prev->rid, p.rid);
-                p.same_sub = kRepeat && prev && prev->st == p.st && same_name(prev->sid, p.sid);
+                p.same_res = prev && prev->rt == p.rt && same_name(prev->rid, p.rid);
+                p.same_sub = prev && prev->st == p.st && same_name(prev->sid, p.sid);
                 p.hit_res = !p.same_res && cached(i, F_RID, p.rt, &p.kr, &p.res);  // (packed requests: this dictionary entry was resolved earlier in the call)
                 p.hit_sub = !p.same_sub && cached(i, F_SID, p.st, &p.ks, &p.sub);
                 if (p.hit_res) p.same_res = false;

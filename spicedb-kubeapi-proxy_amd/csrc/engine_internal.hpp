@@ -437,15 +437,8 @@ struct acl_engine {
     uint32_t local_cap_limit = 0;  // test knob (ACL_LOCAL_CAP): private frontier entries per block, at most
     uint64_t compaction_slack = 65536;  // words of garbage a snapshot may hold on top of an eighth of its rows before a background build starts
     uint32_t spin_max = 64;  // (every block pays a system-scope release of its answers: worth it up to 64 blocks -- 1 item 21.3 -> 17.6 us, 64 items 23.0 -> 20.6 us; at 256 items it already loses, 23 -> 27 us, profiles/r05_spin_wait_ab.txt) host batches up to this size wait for their kernel by spinning on a pinned word its last block stores, not in hipStreamSynchronize (ACL_SPIN_MAX; 0 = off)
-    uint32_t hostmap_max = 0xFFFFFFFFu;  // host batches up to this size: the kernel reads the items from, and writes the answers to, pinned host memory (no copies; ACL_HOSTMAP_MAX, A/B knob)
     unsigned intern_threads = 32; // host threads (the caller included) of bulk string interning, at most
-    uint32_t local_wide_min = 65536;  // batches from this size on run the wide (12-wave) instantiation (a unit pools more requests: shorter tail)
-    uint32_t host_skew_pct = 8;  // a lone caller's host-mapped launch: first unit this many percent larger than the mean, last one as much smaller (ACL_HOST_SKEW_PCT;
-                                 // worth 1-3 % of such a call -- the items do NOT arrive in block order, or 16 % would have hidden half the transfer: profiles/r04_host_skew.txt)
     uint32_t host_split = 2;   // streams the slices of one large host batch are spread over (ACL_HOST_SPLIT, 1 = off; engine_pass.cpp check_pass_local_host)
-    uint32_t local_upw = 1;    // single-launch pass over a large batch: work units per resident wave.  1 = every wave one unit of n / waves requests (no
-                               // second round of per-level latency chains); 2 balances C4's uneven requests 3 % better but costs C2 a whole second round
-    uint32_t local_static_pct = 100, local_dyn_unit = 32;  // chip-filling single-launch passes: share of the batch in static (one per block) units; hand-out unit size
     uint64_t cfg_frontier_entries = 0;
     // evaluation contexts: per replica (DevState), one lock and one condition variable for all
     std::mutex pool_mu;
@@ -482,7 +475,6 @@ struct acl_engine {
     uint32_t max_sub_batch = 1u << 20;
     uint32_t local_max_items = 1u << 20;  // batches up to this size take the single-launch path (k_check_local) first; 0 = never.  Measured on C4
                                           // (profiles/r02_walk_vs_levels.txt): faster than the level loop at every batch size, 1.5x at 262 144 items
-    bool rev_rows_device = false;  // k_rev_local's result rows through a device buffer + one DMA copy instead of kernel writes to host memory (A/B)
     bool shard_a2a = true;  // native sharded Check: per-destination blocks through the communicator's all_to_all when it has one (ACL_SHARD_A2A=0: all-gather)
     bool rev_sink_on = true;   // a lookup's result slot that nothing above leads back into is marked, not expanded (Snapshot::rev_sink; ACL_REV_SINK=0: A/B and tests)
     bool rev_lds_rows = true;  // k_rev_local keeps the result slot's rows in LDS when they fit (ACL_REV_LDS_ROWS=0: always in HBM; A/B and tests)

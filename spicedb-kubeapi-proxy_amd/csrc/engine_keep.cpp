@@ -371,10 +371,9 @@ struct KeepCall {
     // names it has just hashed -- one block of 64 behind the block whose slots it asks for, the names' bytes still in this thread's cache -- so that the test
     // after the walk is a bit test per pair.  A walk that is back with FEW allowed objects stops that: the rest is tested through the tags, no table involved.
     void resolve_block(size_t lo, size_t le) {
-        static const bool kResolveInPass = !getenv("ACL_KEEP_RESOLVE") || atoi(getenv("ACL_KEEP_RESOLVE")) != 0;  // (A/B knob)
         if (le == lo) return;
         const bool back = walk_done.load(std::memory_order_acquire);
-        if (kResolveInPass && (back ? many_a.load(std::memory_order_relaxed) : !guess_few)) {
+        if (back ? many_a.load(std::memory_order_relaxed) : !guess_few) {
             if (!resolved_any.load(std::memory_order_relaxed)) resolved_any.store(true, std::memory_order_relaxed);
             uint32_t rid_loc[kPairBlock];
             for (size_t i = lo; i < le; i++) {

@@ -55,18 +55,13 @@ static int lookup_pass_local(acl_engine *h, PassCtx *c, const DevReverse &r, uin
     if (words > 0xFFFFFFFFull || r.nslots > kRevLdsSlots || r.nrops > kRevLdsOps) return kTakeLevelLoop;
     const bool direct = !d_dst && words && h->is_pinned(bitmaps, m * words * sizeof(uint32_t));
     const size_t ostride = d_dst ? dstride : direct ? words : cw;
-    // Result rows: written by the kernel straight into host memory (each block as it finishes), or -- rev_rows_device, A/B knob
-    // ACL_REV_ROWS=device -- into a device buffer that one DMA copy brings over afterwards.
-    const bool via_device = h->rev_rows_device && ostride && !d_dst;
+    // Result rows: written by the kernel straight into host memory (each block as it finishes)
     RevPass p;
-    int rc = rev_pass_begin(h, c, m, m, (direct || d_dst) ? 0 : m * std::max<size_t>(cw, 1) * 4, !via_device && !d_dst, &p);
+    int rc = rev_pass_begin(h, c, m, m, (direct || d_dst) ? 0 : m * std::max<size_t>(cw, 1) * 4, !d_dst, &p);
     if (rc) return rc;
     void *d_rows = p.d_rows;
     if (d_dst) d_rows = d_dst;
-    else if (via_device) {
-        HIP_TRY(c->d_rows.ensure(m * ostride));
-        d_rows = c->d_rows.p;
-    } else if (direct) HIP_TRY(hipHostGetDevicePointer(&d_rows, bitmaps, 0));
+    else if (direct) HIP_TRY(hipHostGetDevicePointer(&d_rows, bitmaps, 0));
     // Rows that do not fit the block's LDS (a type of more than 1 M objects; reference pkg/authz/lookups.go:49-65 asks for the whole type): the heavy terminal
     // rows are deferred to a chip-wide launch and the rows are copied / counted / cleared by a third one (kernels.hip RevDefer; ACL_REV_BIG_ROWS=0: one block
     // does it all, as in round 5 -- A/B)
@@ -109,7 +104,6 @@ static int lookup_pass_local(acl_engine *h, PassCtx *c, const DevReverse &r, uin
                      (uint32_t)cw, p.d_counts, p.d_status, lds_row_words, (p.spin || use_big) ? c->d_done.p : nullptr, p.d_done_flag, p.done_val, use_big ? &big : nullptr,
                      pruned ? &useful : nullptr);
     ev_end(c);
-    if (via_device) HIP_TRY(hipMemcpyAsync(direct ? (void *)bitmaps : (void *)p.h_rows, c->d_rows.p, m * ostride * 4, hipMemcpyDeviceToHost, c->stream));
     rc = rev_pass_end(c, p, counts);
     const uint32_t *flag = p.flag;
     if (*flag && use_big) c->big_bytes_zeroed = 0;  // (a block gave up half-way: marks of rows nobody folded may be left)

@@ -146,32 +146,22 @@ uint32_t next_done_val(PassCtx *c) {
 // Small batch: ONE launch (k_check_local) seeds, walks every level and writes the answers.  Requests per wave: one while the
 // batch fits the chip's wave slots (latency), more beyond that.  The waves' private frontier regions are carved from
 // the context's frontier buffers.
+constexpr uint32_t kLocalWideMin = 65536;  // batches from this size on run the wide (12-wave) instantiation: a unit pools more requests, shorter tail (profiles/r03_wide_threshold.txt)
+constexpr uint32_t kHostSkewPct = 8;  // a lone caller's host-mapped launch: first unit this many percent larger than the mean, last one as much smaller (profiles/r04_host_skew.txt)
 // Geometry of a single-launch pass over n requests: requests per unit, blocks to launch, private frontier entries per block.
 struct LocalGeom {
     uint32_t rpw, nblocks, nunits, cap;
-    uint32_t nstatic = 0, rdyn = 0;  // != 0: static units for the head of the batch, small hand-out units for its tail
-    bool wide = false;               // 12 waves per block and unit (kLocalWide) (chip-filling batches) instead of 4
+    bool wide = false;  // 12 waves per block and unit (kLocalWide) (chip-filling batches) instead of 4
 };
 static LocalGeom local_geom(acl_engine *h, PassCtx *c, uint32_t n) {
     LocalGeom G{};
-    G.wide = n >= h->local_wide_min;
+    G.wide = n >= kLocalWideMin;
     const uint32_t blocks = (uint32_t)(G.wide ? c->dev->local_blocks_wide : c->dev->local_blocks);  // what is resident at once; a unit is walked by one block (4 or 12 waves)
     // latency: while the batch has fewer requests than the chip has blocks, every request gets a block of its own; beyond that
-    // every block gets ONE unit of n / blocks requests (`upw` > 1: several smaller ones, a second round of per-level chains)
-    G.rpw = n <= blocks ? 1u : std::min<uint32_t>(std::max<uint32_t>((n + blocks * h->local_upw - 1) / (blocks * h->local_upw), 1), local_unit_max(G.wide));
+    // every block gets ONE unit of n / blocks requests (profiles/r02_walk_units_per_wave.txt, profiles/r03_static_dynamic_units_ab.txt)
+    G.rpw = n <= blocks ? 1u : std::min<uint32_t>(std::max<uint32_t>((n + blocks - 1) / blocks, 1), local_unit_max(G.wide));
     G.nunits = (n + G.rpw - 1) / G.rpw;
     G.nblocks = std::max<uint32_t>(std::min<uint32_t>(G.nunits, blocks), 1);
-    // Chip-filling batches: requests differ 100-fold in work, a block's unit is the sum of ~128 of them, and the slowest of 2 048 such sums sets
-    // the launch (waves resident 76 % of it, profiles/r02_pmc_walk_final.txt).  So only `local_static_pct` of the batch goes out as one big unit
-    // per resident block; the rest is cut into units of `local_dyn_unit` requests that blocks draw from a counter as they finish -- spread over
-    // the tail, so the counter's same-address cost (~12 ns per draw) never sees all blocks at once.
-    if (h->local_static_pct < 100 && h->local_upw == 1 && G.nunits == blocks && G.rpw >= 2 * h->local_dyn_unit) {
-        const uint32_t rs = std::max<uint32_t>(h->local_dyn_unit, (uint32_t)((uint64_t)G.rpw * h->local_static_pct / 100));
-        G.rpw = rs;
-        G.nstatic = blocks;
-        G.rdyn = h->local_dyn_unit;
-        G.nunits = G.nstatic + (n - G.nstatic * rs + G.rdyn - 1) / G.rdyn;
-    }
     // (a block that needs more than 256 K entries is walking something the whole chip should walk: the level loop takes the batch)
     G.cap = (uint32_t)std::min<uint64_t>(c->frontier_entries / G.nblocks, 1u << 18);
     if (h->local_cap_limit) G.cap = std::min(G.cap, h->local_cap_limit);
@@ -213,7 +203,7 @@ static int local_enqueue(acl_engine *h, PassCtx *c, const DevGraph &g0, const ui
     HIP_TRY(hipMemsetAsync(d_over, 0, 3 * sizeof(uint32_t), c->stream));  // [2]: deepest level (a per-destination export counter of the sharded walk: unused here)
     ev_begin(c, 2);
     launch_check_local(c->stream, g, d_items, n, G.rpw, G.nblocks, G.nunits > G.nblocks ? d_over + 1 : nullptr, c->d_fbuf[0].p, c->d_fbuf[1].p, G.cap, d_over, c->d_has.p,
-                       c->d_err.p, d_perm, d_errout, d_over + 2, G.nstatic, G.rdyn, G.wide);
+                       c->d_err.p, d_perm, d_errout, d_over + 2, G.wide);
     ev_end(c);
     HIP_TRY(hipMemcpyAsync(c->h_status, d_over, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     return ACL_OK;
@@ -251,7 +241,7 @@ static int check_pass_local_host(acl_engine *h, PassCtx *c, const acl_item_t *it
     // launch each, back to back on the context's stream, every one reading its slice of the items from -- and answering into -- the caller's
     // pinned memory, ONE synchronisation for all (round 4: this retired the copying pipeline -- look-ahead H2D, lanes, kernels chained on the
     // device through events, a completer thread -- that served only such batches).
-    const bool wide0 = n >= h->local_wide_min;
+    const bool wide0 = n >= kLocalWideMin;
     const uint64_t per_launch = (uint64_t)(wide0 ? c->dev->local_blocks_wide : c->dev->local_blocks) * local_unit_max(wide0);
     uint32_t npass = (uint32_t)std::max<uint64_t>(1, ((uint64_t)n + per_launch - 1) / per_launch);
     // CONCURRENT slices: the items of a launch cross PCIe while its blocks wait for their seeds (4 MB per 262 144 items: ~80 us in which a lone
@@ -275,7 +265,7 @@ static int check_pass_local_host(acl_engine *h, PassCtx *c, const acl_item_t *it
     const uint32_t chunk = npass == 1 ? n : (uint32_t)((((uint64_t)n + npass - 1) / npass + 63) / 64 * 64);
     LocalGeom G = local_geom(h, c, std::min(n, chunk));
     G.cap /= nstreams;
-    if (G.cap < 256 || n > h->hostmap_max || G.nunits > G.nblocks || npass > 15) return kTakeLevelLoop;
+    if (G.cap < 256 || G.nunits > G.nblocks || npass > 15) return kTakeLevelLoop;
     for (uint32_t k = 1; k < nstreams; k++)
         if (!c->aux[k - 1]) HIP_TRY(hipStreamCreateWithFlags(&c->aux[k - 1], hipStreamNonBlocking));
     *attempted = true;
@@ -323,8 +313,8 @@ static int check_pass_local_host(acl_engine *h, PassCtx *c, const acl_item_t *it
         hipStream_t st = lane ? c->aux[lane - 1] : c->stream;
         if (nstreams == 1) ev_begin(c, 2);
         launch_check_local(st, g, (const uint4 *)d_in + off, m, Gk.rpw, Gk.nblocks, nullptr, c->d_fbuf[0].p + region, c->d_fbuf[1].p + region, Gk.cap, (uint32_t *)d_flag + k,
-                           c->d_has.p + off, c->d_err.p + off, (uint8_t *)d_perm + off, (int32_t *)d_errp + off, nullptr, 0, 0, Gk.wide,
-                           lone && Gk.nunits > 1 ? Gk.rpw * h->host_skew_pct / 100 : 0u, spin ? c->d_done.p : nullptr, spin ? (uint32_t *)d_flag + 15 : nullptr, done_val,
+                           c->d_has.p + off, c->d_err.p + off, (uint8_t *)d_perm + off, (int32_t *)d_errp + off, nullptr, Gk.wide,
+                           lone && Gk.nunits > 1 ? Gk.rpw * kHostSkewPct / 100 : 0u, spin ? c->d_done.p : nullptr, spin ? (uint32_t *)d_flag + 15 : nullptr, done_val,
                            npass == 1 && n <= 4 ? (const uint4 *)items : nullptr);
         if (nstreams == 1) ev_end(c);
     }
@@ -351,8 +341,8 @@ static int check_pass_local_host(acl_engine *h, PassCtx *c, const acl_item_t *it
 
 // would check_pass_local_host take a batch of n items?  (what the submit pipeline asks before it decides who runs a ticket)
 bool hostmap_takes(acl_engine *h, size_t n) {
-    if (!(n <= h->local_max_items && n <= h->max_sub_batch && h->shard.world == 1 && n <= h->hostmap_max)) return false;
-    const bool wide = n >= h->local_wide_min;
+    if (!(n <= h->local_max_items && n <= h->max_sub_batch && h->shard.world == 1)) return false;
+    const bool wide = n >= kLocalWideMin;
     return n <= 15 * (uint64_t)(wide ? h->dev0().local_blocks_wide : h->dev0().local_blocks) * local_unit_max(wide);  // (up to 15 sub-passes of one unit per resident block; replicas are alike)
 }
 

@@ -75,7 +75,7 @@ static void compaction_start(acl_engine *h) {
     // rare: the worker's last uploads and this thread's patch upload meet in the runtime, so the build tended to finish exactly between this
     // read's adoption check and this call (4 of 5 builds were dropped in the dual-write run, and the tables ran out of spare ids meanwhile).
     if (c->state.load() == 1 || c->state.load() == 2) return;
-    if (getenv("ACL_DEBUG_REBUILD")) fprintf(stderr, "[aclgpu] background build starts at revision %llu (previous state %d)\n", (unsigned long long)h->store.revision(), c->state.load());
+    if (debug_rebuild()) fprintf(stderr, "[aclgpu] background build starts at revision %llu (previous state %d)\n", (unsigned long long)h->store.revision(), c->state.load());
     if (c->worker.joinable()) c->worker.join();
     // one set of fresh arrays + an upload stream per replica (created on that replica's device)
     while (c->per.size() < h->devs.size()) c->per.push_back(std::make_unique<Compaction::PerDevice>());
@@ -121,7 +121,6 @@ static void refresh_local_blocks(acl_engine *h) {  // (the single-launch kernel'
     for (auto &d : h->devs) {
         d->local_blocks = local_grid_blocks(d->device, (h->snap.progs.size() + h->snap.ops.size()) * 32);
         d->local_blocks_wide = local_grid_blocks(d->device, (h->snap.progs.size() + h->snap.ops.size()) * 32, true);
-        if (const char *ev = getenv("ACL_LOCAL_BLOCKS_WIDE")) d->local_blocks_wide = std::max(1, atoi(ev));  // A/B knob: resident blocks the wide walk plans its units for
     }
 }
 
@@ -131,7 +130,7 @@ static bool compaction_adopt(acl_engine *h, int64_t now) {
     Compaction *c = h->compaction.get();
     if (!c || c->state.load() != 2) {
         if (c && c->state.load() == 3) {
-            if (getenv("ACL_DEBUG_REBUILD")) fprintf(stderr, "[aclgpu] background build failed: %s\n", c->error.c_str());
+            if (debug_rebuild()) fprintf(stderr, "[aclgpu] background build failed: %s\n", c->error.c_str());
             c->state.store(0);
         }
         return false;
@@ -141,7 +140,7 @@ static bool compaction_adopt(acl_engine *h, int64_t now) {
     if (c->shard.rank != h->shard.rank || c->shard.world != h->shard.world || c->per.size() < h->devs.size()) return false;
     std::vector<Patch> patches;
     const uint64_t from = c->snap.revision;
-    if (getenv("ACL_DEBUG_REBUILD")) fprintf(stderr, "[aclgpu] adopting the background build of revision %llu at revision %llu\n", (unsigned long long)from, (unsigned long long)h->store.revision());
+    if (debug_rebuild()) fprintf(stderr, "[aclgpu] adopting the background build of revision %llu at revision %llu\n", (unsigned long long)from, (unsigned long long)h->store.revision());
     if (!patch_forward(h->store, now, &c->snap, h->shard, &patches, (size_t)1 << 19)) return false;  // (a bulk load meanwhile: the synchronous path decides)
     bool rev_ok = c->with_reverse && patch_reverse(h->store, now, from, &c->snap, h->shard, &patches);
     for (size_t i = 0; i < h->devs.size(); i++) {  // the catch-up patch reaches every replica's fresh arrays before any of them is swapped in
@@ -253,7 +252,7 @@ int ensure_snapshot(acl_engine *h) {
             return ACL_OK;
         }
     }
-    if (getenv("ACL_DEBUG_REBUILD"))
+    if (debug_rebuild())
         fprintf(stderr, "[aclgpu] synchronous rebuild: snap_valid=%d dev_valid=%d window=[%lld,%lld) now=%lld garbage=%llu of %zu store_rev=%llu snap_rev=%llu\n",
                 (int)h->snap_valid, (int)h->all_dev_valid(), (long long)h->snap.valid_lo, (long long)h->snap.valid_hi, (long long)now,
                 (unsigned long long)h->snap.garbage_words, h->snap.edges.size() + h->snap.buckets.size(), (unsigned long long)h->store.revision(),

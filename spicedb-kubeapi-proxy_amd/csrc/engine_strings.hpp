@@ -180,7 +180,7 @@ struct InternPool {
     // The workers stay on the NUMA node of the thread that creates the pool (the first large string batch's caller): the name tables were
     // filled from that side, and on a two-socket host a worker that lands on the other socket pays a remote access for every slot it probes --
     // the same binary measured 0.34 ms or 0.55 ms per 65 536-item call depending on where the scheduler had put the threads
-    // (profiles/r03_string_path_ab.txt).  ACL_INTERN_PIN=0: leave them to the scheduler.
+    // (profiles/r03_string_path_ab.txt).
     static bool node_cpus(cpu_set_t *out) {
         const int cpu = sched_getcpu();
         if (cpu < 0) return false;
@@ -222,9 +222,8 @@ struct InternPool {
     }
     explicit InternPool(unsigned nthreads) {
         for (unsigned i = 0; i < nthreads; i++) threads.emplace_back([this, i] { loop(i); });
-        const char *ev = getenv("ACL_INTERN_PIN");
         cpu_set_t set;
-        if (!(ev && atoi(ev) == 0) && node_cpus(&set))
+        if (node_cpus(&set))
             for (auto &t : threads) (void)pthread_setaffinity_np(t.native_handle(), sizeof(set), &set);
     }
     ~InternPool() {

@@ -1486,7 +1486,7 @@ struct NoNext {
 // 100-fold in work (a first-level hit against a full five-level miss), and a wave that walked its own 43 requests alone
 // finished anywhere between 0.5x and 1.6x the mean -- a third of the wave-time was idle waiting for the slowest
 // (profiles/r02_pmc_walk.txt); a unit of 4 x 43 requests varies half as much, and inside it the work is shared per level.
-// Block b starts on unit b; further units (batches beyond 256 requests per resident block, or `upw` > 1) are handed out through
+// Block b starts on unit b; further units (batches beyond 256 requests per resident block) are handed out through
 // `next_unit`, one atomic per BLOCK-unit -- per wave-unit the same counter cost ~12 ns per unit in same-address contention
 // (profiles/r02_walk_units_per_wave.txt).
 struct InlineItems {  // up to four 16-byte items passed by value (kernel arguments)
@@ -2912,18 +2912,16 @@ static void launch_check_local_w(hipStream_t s, const DevGraph &g, const uint4 *
 }
 void launch_check_local(hipStream_t s, const DevGraph &g, const uint4 *items, uint32_t n, uint32_t rpw, uint32_t nblocks, uint32_t *next_unit, uint4 *buf0,
                         uint4 *buf1, uint32_t cap, uint32_t *overflow, uint8_t *has, uint8_t *err, uint8_t *perm_out, int32_t *err_out, uint32_t *max_level,
-                        uint32_t nstatic, uint32_t rdyn, bool wide, uint32_t skew, uint32_t *done_ctr, uint32_t *done_flag, uint32_t done_val, const uint4 *inline_items_host) {
+                        bool wide, uint32_t skew, uint32_t *done_ctr, uint32_t *done_flag, uint32_t done_val, const uint4 *inline_items_host) {
     InlineItems inl{};
     if (inline_items_host && n <= 4) {  // (host memory: copied into the launch's arguments)
         for (uint32_t i = 0; i < n; i++) inl.v[i] = inline_items_host[i];
         items = nullptr;
     }
-    uint32_t nunits = (n + rpw - 1) / rpw;
-    if (nstatic && rdyn && (uint64_t)nstatic * rpw < n) skew = 0;  // (static units only)
+    const uint32_t nunits = (n + rpw - 1) / rpw;
     skew = std::min(skew, std::min(rpw - 1u, (wide ? kLocalWide : kLocalNarrow) * 64u - rpw));  // the largest unit still fits the block: thread i seeds request first + i
     skew = nunits > 1 && nunits <= 4096 ? (skew << 8) / nunits : 0u;                             // (the kernel's fixed-point form: 1/256ths per unit; u (nunits - u) skew < 2^32)
-    if (nstatic && rdyn && (uint64_t)nstatic * rpw < n) nunits = nstatic + (n - nstatic * rpw + rdyn - 1) / rdyn;  // static units, then small ones
-    else nstatic = nunits, rdyn = rpw;
+    const uint32_t nstatic = nunits, rdyn = rpw;  // (every unit holds rpw requests: the kernel's hand-out units for a batch's tail lost, profiles/r03_static_dynamic_units_ab.txt)
     if (wide) launch_check_local_w<kLocalWide>(s, g, items, n, rpw, nblocks, nunits, nstatic, rdyn, next_unit, buf0, buf1, cap, overflow, has, err, perm_out, err_out, max_level, skew, done_ctr, done_flag, done_val, inl);
     else launch_check_local_w<kLocalNarrow>(s, g, items, n, rpw, nblocks, nunits, nstatic, rdyn, next_unit, buf0, buf1, cap, overflow, has, err, perm_out, err_out, max_level, skew, done_ctr, done_flag, done_val, inl);
 }

@@ -123,10 +123,8 @@ void launch_keep(hipStream_t s, uint32_t k_items, const uint32_t *item_off, cons
 void launch_check_local(hipStream_t s, const DevGraph &g, const uint4 *items, uint32_t n, uint32_t rpw, uint32_t nblocks, uint32_t *next_unit, uint4 *buf0,
                         uint4 *buf1, uint32_t cap, uint32_t *overflow, uint8_t *has, uint8_t *err, uint8_t *perm_out, int32_t *err_out,
                         uint32_t *max_level = nullptr /* device word (zeroed): atomicMax of the dispatch levels the units needed */,
-                        uint32_t nstatic = 0, uint32_t rdyn = 0 /* != 0: only the first nstatic units hold rpw requests, the rest of the batch is cut into units of rdyn
-                                                                   handed out through next_unit (which must then be given) */,
                         bool wide = false /* 12 waves per block (and unit) instead of 4: chip-filling batches */,
-                        uint32_t skew = 0 /* static units only: unit u holds rpw + skew ... rpw - skew requests, falling with u (items read across PCIe arrive in block order) */,
+                        uint32_t skew = 0 /* unit u holds rpw + skew ... rpw - skew requests, falling with u (items read across PCIe arrive in block order) */,
                         uint32_t *done_ctr = nullptr /* device word, zero between launches */, uint32_t *done_flag = nullptr /* pinned host word (device pointer): the last block to
                         finish stores done_val there, behind a system-scope release of every block's answers -- the host spins on it instead of synchronising the stream */,
                         uint32_t done_val = 0, const uint4 *inline_items_host = nullptr /* HOST pointer to the batch's items: a batch of <= 4 rides in the kernel's arguments

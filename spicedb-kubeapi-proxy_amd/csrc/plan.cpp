@@ -919,10 +919,14 @@ struct Patcher {
 
 void expiry_crossings(const Store &store, int64_t lo, int64_t hi, int64_t now, std::vector<Store::Change> *ch) { store.expiry_crossings(lo, hi, now, ch); }
 
+bool debug_rebuild() {
+    static const bool on = getenv("ACL_DEBUG_REBUILD") != nullptr;
+    return on;
+}
+
 // ACL_DEBUG_REBUILD: say why a snapshot could not be patched (the caller then rebuilds, or drops a background build)
 static bool unpatchable(const char *why, uint64_t a = 0, uint64_t b = 0) {
-    static const bool on = getenv("ACL_DEBUG_REBUILD") != nullptr;
-    if (on) fprintf(stderr, "[aclgpu] patch_forward declines: %s (%llu, %llu)\n", why, (unsigned long long)a, (unsigned long long)b);
+    if (debug_rebuild()) fprintf(stderr, "[aclgpu] patch_forward declines: %s (%llu, %llu)\n", why, (unsigned long long)a, (unsigned long long)b);
     return false;
 }
 

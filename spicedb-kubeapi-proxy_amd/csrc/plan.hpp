@@ -304,5 +304,7 @@ void build_reverse(Store &store, int64_t now, Snapshot *snap, ShardSpec shard = 
 // the largest fast row in buckets); ACL_DEBUG_ROWS=2: also one line per SLOW row (type#relation@subject type, subject id, buckets, two-choice
 // flag, seed, ids).  build_forward reports every build; acl_selfcheck_snapshot reports a patched snapshot (tests/test_hashed_rows_cpu.py).
 void debug_rows_report(const Store &store, const Snapshot &snap);
+// ACL_DEBUG_REBUILD (read once per process): stderr lines on why a snapshot is rebuilt, could not be patched, or a background build is dropped
+bool debug_rebuild();
 
 }  // namespace acl

@@ -56,11 +56,7 @@ void *slot_pages_alloc(size_t bytes) {
     char *p = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(raw) + kHuge - 1) & ~(uintptr_t)(kHuge - 1));
     if (p != raw) munmap(raw, (size_t)(p - raw));
     if (p + len != raw + len + kHuge) munmap(p + len, (size_t)(raw + len + kHuge - (p + len)));
-    static const bool kAsk = [] {
-        const char *e = getenv("ACL_SLOT_HUGE_PAGES");  // (A/B knob: 0 leaves the table on 4 KiB pages)
-        return !(e && atoi(e) == 0);
-    }();
-    if (kAsk) (void)madvise(p, len, MADV_HUGEPAGE);  // (advice only: refused on kernels without THP)
+    (void)madvise(p, len, MADV_HUGEPAGE);  // (advice only: refused on kernels without THP)
     return p;
 }
 void slot_pages_free(void *p, size_t bytes) {

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Check batch-size sweep on C4 (device-resident calls): kernel time by HIP events and wall time per call, for one setting of the engine's
-A/B knobs (read at acl_open: ACL_LOCAL_WIDE_MIN, ACL_LOCAL_STATIC_PCT, ...).  usage: python tools/batch_sweep.py [sizes...]"""
+switches (read at acl_open: ACL_LOCAL_MAX, ACL_HOP2, ... -- the table in INTEGRATION.md).  usage: python tools/batch_sweep.py [sizes...]"""
 import os
 import sys
 import time

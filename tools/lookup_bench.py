@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """LookupResources batch-size sweep on C3 (power users repeated to fill a batch): wall time per call and the kernel's HIP-event time.
-usage: python tools/lookup_bench.py [sizes...]     env: ACL_REV_LOCAL=0 (level loop), ACL_REV_ROWS=device (rows through a device buffer)"""
+usage: python tools/lookup_bench.py [sizes...]     env: ACL_REV_LOCAL=0 (level loop)"""
 import os
 import sys
 import time

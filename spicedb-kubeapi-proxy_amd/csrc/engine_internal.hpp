@@ -292,6 +292,7 @@ struct PassCtx {
     uint32_t rev_levels_hint = 4;
     uint32_t subj_levels_hint = 6;
     uint32_t levels_hint = 6;
+    uint32_t pool_shift = 0;     // the level loop's combine-node pool is this many times doubled (engine_pass.cpp levels_pass_merging)
     CallOpts opts;  // of the call that holds this context
     // measurement (merged into the engine's stats when the context is released)
     acl_stats_t stats{};

@@ -177,7 +177,7 @@ int combine_prepare(acl_engine *h, PassCtx *c, DevGraph *g, uint32_t n, uint32_t
         node_cap = std::max<uint64_t>(1024, (uint64_t)rpw * 8);
         regions = blocks;
     } else {
-        node_cap = std::min<uint64_t>(std::max<uint64_t>((uint64_t)1 << 20, (uint64_t)n * 16), (uint64_t)1 << 26);
+        node_cap = std::min<uint64_t>(std::max<uint64_t>((uint64_t)1 << 20, (uint64_t)n * 16) << c->pool_shift, (uint64_t)1 << 26);
     }
     const uint64_t cell_cap = node_cap * 4;
     if ((uint64_t)n + regions * cell_cap >= 0xFFFFFFF0ull) return fail(ACL_ERR_RESOURCE_EXHAUSTED, "combine cells beyond 2^32: lower max_sub_batch");
@@ -425,6 +425,26 @@ static int levels_pass(acl_engine *h, PassCtx *c, const DevGraph &g0, const uint
     }
 }
 
+// A merging pass over a slice whose combine nodes outgrow the pool (2^20 nodes, or 16 per item) is redone on the slice's halves: what runs out may be
+// the SUM of the items' nodes -- chains of cycles through permissions with `&` / `-`, or the many paths of an acyclic graph, cost thousands of nodes an
+// item (found by the random schemas of tests/schema_gen.py) -- which the oracles answer item by item.  A slice of at most kBigPoolItems items that
+// still runs out is redone with a pool of 2^24 nodes, and halved again under that pool down to one item.  An item that outgrows 2^24 nodes alone fails
+// the call; it has then been walked about 2 log2(n) times on the way down, and every failed attempt leaves its text as the last error until the call
+// returns.  Only this path halves: the sharded native loops and the passes of the other walks keep their one pool per pass.
+constexpr uint32_t kBigPoolItems = 64, kBigPoolShift = 4;
+static int levels_pass_merging(acl_engine *h, PassCtx *c, const DevGraph &g, const uint4 *d_items, uint32_t n, uint8_t *d_perm, int32_t *d_errout, uint32_t shift = 0) {
+    c->pool_shift = shift;
+    int rc = levels_pass(h, c, g, d_items, n, d_perm, d_errout, true);
+    c->pool_shift = 0;
+    if (rc != ACL_ERR_RESOURCE_EXHAUSTED || !h->snap.has_combine || c->h_status[2 * kLevelSlots] != 3) return rc;
+    if (n <= kBigPoolItems && shift == 0) return levels_pass_merging(h, c, g, d_items, n, d_perm, d_errout, kBigPoolShift);
+    if (n == 1) return rc;
+    const uint32_t half = n / 2;
+    rc = levels_pass_merging(h, c, g, d_items, half, d_perm, d_errout, shift);
+    if (rc) return rc;
+    return levels_pass_merging(h, c, g, d_items + half, n - half, d_perm + half, d_errout ? d_errout + half : nullptr, shift);
+}
+
 // one device pass over n (<= max_sub_batch) interned items already in HBM
 int check_pass(acl_engine *h, PassCtx *c, const uint4 *d_items, uint32_t n, uint8_t *d_perm, int32_t *d_errout, bool try_local) {
     HIP_TRY(c->d_has.ensure(std::max<size_t>(n, 4096)));
@@ -444,7 +464,7 @@ int check_pass(acl_engine *h, PassCtx *c, const uint4 *d_items, uint32_t n, uint
     c->stats.overflow_retries++;
     for (uint32_t off = 0; off < n; off += kDedupBatch) {
         const uint32_t m = std::min<uint32_t>(kDedupBatch, n - off);
-        rc = levels_pass(h, c, g, d_items + off, m, d_perm + off, d_errout ? d_errout + off : nullptr, true);
+        rc = levels_pass_merging(h, c, g, d_items + off, m, d_perm + off, d_errout ? d_errout + off : nullptr);
         if (rc) return rc;
     }
     return ACL_OK;
